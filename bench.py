@@ -3,14 +3,19 @@
 RBF-SVM label (BASELINE.json metric; workload = configs[2]: projection + RBF-SVM decision function,
 3 classes, ~2k support vectors, batch 65 536 frames of 64x64x128 resident in HBM per GPU).
 
-    python bench.py --gpus 1 --steps 5 --warmup 2
+    python bench.py --gpus 1 --steps 5 --warmup 2 [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
 A "step" is one pass of the hot path over the rank's resident batch (frames shard across ranks,
 weak scaling, no data-path collective; the per-frame labels are all-gathered over RCCL at the end
-of every step, inside the timed region).  Rank 0 prints the verbose rows as {"doc": ...} on one line and then,
-LAST, the contract line (one JSON object < 4 KB: metric, value, roofline, cpu_baseline, summary).
+of every step, inside the timed region).  A plain run fits the model, makes the batch, warms up, times
+--steps steps and prints the contract line (one JSON object < 4 KB: metric, value, ms_per_step, the
+in-situ roofline of the timed steps, summary).  --full also runs every secondary row (parity gate against
+the CPU oracle, CPU baseline, other ingests / grids / workloads, PMC traffic, probes), prints them as
+{"doc": ...} on a line of its own and then, LAST, the contract line with cpu_baseline and the parity gate.
+--dump-outputs DIR writes what the last timed step returned (rank 0) as DIR/<name>.npy; the inputs are
+a pure function of the arguments (while the batch fits in HBM), so two builds can be compared output for output.
 `python bench.py --gpus N` without a launcher starts its own N ranks.
 """
 import argparse
@@ -76,7 +81,16 @@ def parse():
     ap.add_argument("--dnn-train-steps", type=int, default=600, help="float32 Adam steps that give the CNN row's model real margins")
     ap.add_argument("--seed", type=int, default=1234)
     ap.add_argument("--doc-file", default=None, help="also write the verbose rows (and the contract line) to this JSON file")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also run every secondary row: parity gate against the CPU oracle, CPU baseline, uint8 / slice / Walabot-grid / "
+                         "general-rows / CNN / SGAN rows, GEMM-alone and projection-only timings, PMC traffic passes, stream probe. "
+                         "Without it the run times the headline step only and prints the contract line alone")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the arrays the last timed step returned as DIR/<name>.npy (float32 / float64, <= 64 MB in all)")
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return a
 
 
 def fit_model(rml, torch, X, Y, Z, ntrain, gamma, seed, dev):
@@ -119,6 +133,28 @@ def fit_model(rml, torch, X, Y, Z, ntrain, gamma, seed, dev):
 def sv_f64(model):
     # train.py:667 scaling: float32(code / 255), widened to float64 as libsvm sees it
     return (model["sv_u8"].astype(np.float32) / np.float32(255.0)).astype(np.float64)
+
+
+DUMP_LIMIT_BYTES = 60 * 10 ** 6        # under 64 MB in all, .npy headers included
+
+
+def dump_outputs(path, out, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: every array of one step's output dict as path/<name>.npy.  float32 / float64 arrays keep their dtype,
+    integer ones (labels) are written as float64 (exact).  When the arrays exceed ``limit`` together, every array keeps the same
+    fixed sample of its rows (seed 0, sorted) and the sampled row indices go beside it as <name>_rows.npy."""
+    arrs = {}
+    for k, t in out.items():
+        v = t.detach().cpu().numpy()
+        arrs[k] = v if v.dtype in (np.float32, np.float64) else v.astype(np.float64)
+    total = sum(v.nbytes for v in arrs.values())
+    scale = 1.0 if total <= limit else limit / (total + 8 * sum(len(v) for v in arrs.values()))
+    os.makedirs(path, exist_ok=True)
+    for k, v in arrs.items():
+        if scale < 1.0:
+            rows = np.sort(np.random.default_rng(0).choice(len(v), max(1, int(len(v) * scale)), replace=False))
+            v = v[rows]
+            np.save(os.path.join(path, k + "_rows.npy"), rows.astype(np.float64))
+        np.save(os.path.join(path, k + ".npy"), np.ascontiguousarray(v))
 
 
 class Window:
@@ -213,11 +249,13 @@ def run_workload(a, env, grid, frames, primary):
     if world > 1:
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
     dt = float(tmax.item())
+    if primary and rank == 0 and a.dump_outputs:
+        dump_outputs(a.dump_outputs, out)
 
     # ---- the same frames as uint8 volumes (the radar's native magnitudes): a separate
     #      roofline row, 1 byte per voxel.  Same model, same step, labels must be identical. -----------------
     u8 = None
-    if not a.no_u8 and a.ingest != "u8":
+    if a.full and not a.no_u8 and a.ingest != "u8":
         V8all = Vall.to(torch.uint8)
         win8 = Window(V8all, B, SLIDE, nslide)
 
@@ -289,7 +327,7 @@ def run_workload(a, env, grid, frames, primary):
     # ---- the reference-faithful projection: plane SLICES through a target voxel
     #      (predict.py:98-107), with the voxel derived on the GPU (common.py:49-80) or given -- separate roofline rows ----
     slice_rows = None
-    if not a.no_slice and a.ingest != "u8":
+    if a.full and not a.no_slice and a.ingest != "u8":
         slice_rows = {}
         ijk_dev = rml.derive_targets(V, 1)[:, 0, :].contiguous()           # for the "given" row: what an SDK would report
 
@@ -398,7 +436,7 @@ def run_workload(a, env, grid, frames, primary):
     #      "alone": the 128x128 kernel the pipeline runs beside the projection, one pipeline chunk; "alone_large_batch": the code
     #      rows of (up to) 65 536 frames through rml_svm_decision's own chunking (k_svm_gemm_ring: 256x256 tiles, chunks sized
     #      for whole rounds of one workgroup per CU), the rate a caller of decision_function on a large batch of rows gets
-    if groof is not None:
+    if a.full and groof is not None:
         for key, nb in (("alone", int(min(frames_per_launch, B))), ("alone_large_batch", int(min(65536, B)))):
             _, q, isum, isq, flags = rml.process_volumes(V[:nb], mode="max", scale=True, codes=True)
             if q.stride(0) % 16 == 0:
@@ -419,7 +457,7 @@ def run_workload(a, env, grid, frames, primary):
 
     # ---- configs[1]: the projection kernel alone (HBM-roofline check; float32 feature rows written) ------------
     proj_only = None
-    if primary:
+    if a.full and primary:
         proj_only = {}
         for nb in (4096, 16384):
             nb = int(min(nb, B))
@@ -439,25 +477,27 @@ def run_workload(a, env, grid, frames, primary):
             del feat_o
 
     # ---- parity gate on a slab of the very frames the GPU classified ----------------------
-    sys.path.insert(0, os.path.join(ROOT, "oracle"))
-    import oracle_c as OC
-    npar = min(a.parity if primary else min(a.parity, 1024), B)
-    vh = V[:npar].cpu().numpy().astype(np.float32)
-    threads = len(os.sched_getaffinity(0))
-    xz, yz, xy = OC.project_max(vh, threads=threads)
-    fh = OC.features(xz, yz, xy, scale=True)
-    ref = OC.svm(fh, sv_f64(model), model["dual_coef"], model["intercept"], model["n_support"], model["gamma"],
-                 "rbf", model["calib_a"], model["calib_b"], threads=threads)
-    parity = {
-        "frames": int(npar),
-        "label_vote_mismatch": int((out["label_vote"][:npar].cpu().numpy() != ref["label_vote"]).sum()),
-        "label_calib_mismatch": int((out["label_calib"][:npar].cpu().numpy() != ref["label_calib"]).sum()),
-        "dec_ovo_max_abs_err": float(np.abs(out["dec_ovo"][:npar].cpu().numpy() - ref["dec_ovo"]).max()),
-        "dec_ovr_max_abs_err": float(np.abs(out["dec_ovr"][:npar].cpu().numpy() - ref["dec_ovr"]).max()),
-        "proba_max_abs_err": float(np.abs(out["proba"][:npar].cpu().numpy() - ref["proba"]).max()),
-        "accuracy_vs_synth_class": float((out["label_calib"][:npar].cpu().numpy() ==
-                                          np.searchsorted(model["classes"], cls[:npar].cpu().numpy())).mean()),
-    }
+    parity = None
+    if a.full:
+        sys.path.insert(0, os.path.join(ROOT, "oracle"))
+        import oracle_c as OC
+        npar = min(a.parity if primary else min(a.parity, 1024), B)
+        vh = V[:npar].cpu().numpy().astype(np.float32)
+        threads = len(os.sched_getaffinity(0))
+        xz, yz, xy = OC.project_max(vh, threads=threads)
+        fh = OC.features(xz, yz, xy, scale=True)
+        ref = OC.svm(fh, sv_f64(model), model["dual_coef"], model["intercept"], model["n_support"], model["gamma"],
+                     "rbf", model["calib_a"], model["calib_b"], threads=threads)
+        parity = {
+            "frames": int(npar),
+            "label_vote_mismatch": int((out["label_vote"][:npar].cpu().numpy() != ref["label_vote"]).sum()),
+            "label_calib_mismatch": int((out["label_calib"][:npar].cpu().numpy() != ref["label_calib"]).sum()),
+            "dec_ovo_max_abs_err": float(np.abs(out["dec_ovo"][:npar].cpu().numpy() - ref["dec_ovo"]).max()),
+            "dec_ovr_max_abs_err": float(np.abs(out["dec_ovr"][:npar].cpu().numpy() - ref["dec_ovr"]).max()),
+            "proba_max_abs_err": float(np.abs(out["proba"][:npar].cpu().numpy() - ref["proba"]).max()),
+            "accuracy_vs_synth_class": float((out["label_calib"][:npar].cpu().numpy() ==
+                                              np.searchsorted(model["classes"], cls[:npar].cpu().numpy())).mean()),
+        }
 
     if slice_rows:
         nsl = int(min(512 if primary else 256, B, npar))
@@ -489,7 +529,7 @@ def run_workload(a, env, grid, frames, primary):
     #      scipy.ndimage.zoom(.,1.0) + concatenate (common.process_samples) -> sklearn CalibratedClassifierCV(SVC(rbf)).predict
     #      (SURVEY.md §8d), single-process and on all host cores; the C port of the oracle is kept as a second figure ---
     cpu = None
-    if not a.no_cpu:                    # rank 0, every N (north_star: "timed in the same run"); the other ranks wait at the next barrier
+    if a.full and not a.no_cpu:         # rank 0, every N (north_star: "timed in the same run"); the other ranks wait at the next barrier
         BS = _bench_support()
         gl = out["label_calib"][:npar].cpu().numpy()
         try:
@@ -514,7 +554,7 @@ def run_workload(a, env, grid, frames, primary):
 
     # ---- one observation per call: the grain the reference calls at (predict.py:98-119), host clock per call -------------------
     single = None
-    if rank == 0 and a.ingest != "u8":
+    if a.full and rank == 0 and a.ingest != "u8":
         def _lat(fn, n=200):
             for _ in range(10):
                 fn()
@@ -1092,12 +1132,12 @@ def main():
     # north_star: "Throughput ... at the Walabot Arena grid shape is reported": the reference's own grid
     # (22, 31, 176) (common.py:25-27, predict.log:13) as a second workload in the same run, same metric.
     wal = None
-    if not a.no_walabot and grid != (22, 31, 176):
+    if a.full and not a.no_walabot and grid != (22, 31, 176):
         wal = run_workload(a, env, (22, 31, 176), a.walabot_frames, primary=False)
 
     # roofline.traffic: HBM bytes per projection launch from THIS run's counters (two rocprofv3 PMC passes over a child
     # process that launches the same kernels on the same grids and frames per launch); null when that is not possible
-    if rank == 0 and world == 1 and not a.no_pmc:
+    if a.full and rank == 0 and world == 1 and not a.no_pmc:
         cfgs = []
         for tag, r in (("primary", res), ("walabot", wal)):
             if r is None:
@@ -1142,7 +1182,7 @@ def main():
                 r["roofline"]["traffic_note"] = "not measured at N > 1: the PMC passes run a single-process child; see the N = 1 line"
 
     gen_row = None
-    if not a.no_general:
+    if a.full and not a.no_general:
         gen_row = {}
         g1 = run_general(a, env, grid, a.general_frames)
         if not a.no_walabot and grid != (22, 31, 176):
@@ -1155,11 +1195,11 @@ def main():
                 gen_row["walabot_grid"] = g2
 
     dnn_row = None
-    if not a.no_dnn:
+    if a.full and not a.no_dnn:
         dnn_row = run_dnn(a, env)
 
     sgan_row = None
-    if not a.no_sgan:
+    if a.full and not a.no_sgan:
         try:
             sgan_row = run_sgan(a, env)
         except Exception as e:          # a library-side failure must not cost the headline line
@@ -1169,21 +1209,22 @@ def main():
         # second denominator of SURVEY.md §8d: what a pure streaming READ reaches on THIS box (rml_probe_stream: a persistent kernel of
         # non-temporal 16-byte loads folded by a max, the projection's own access pattern without its epilogue).  Round 4 used a
         # torch copy_ here, which is slower than the projection it was meant to bound.
-        try:
-            src = torch.zeros(1 << 30, dtype=torch.uint8, device=dev)
-            gbs = ctypes.c_double()
-            env["lib_mod"].check(env["lib_mod"].load().rml_probe_stream(env["lib_mod"].context(dev), env["lib_mod"].ptr(src), src.numel(), 20,
-                                                                          ctypes.byref(gbs), env["lib_mod"].stream_ptr(dev)), "rml_probe_stream")
-            del src
-            stream_gbs = float(gbs.value)
-            rows = [("primary", res)] + ([("walabot", wal)] if wal is not None else [])
-            for _, r in rows:
-                for rf_ in [r["roofline"]] + ([r["uint8_ingest"]["roofline"]] if r.get("uint8_ingest") else []) + \
-                        [sr["roofline"] for sr in (r.get("slice_rows") or {}).values()]:
-                    rf_["measured_stream_GBs"] = round(stream_gbs, 1)
-                    rf_["frac_of_measured_stream"] = round(rf_["achieved"] / stream_gbs, 4)
-        except Exception as e:
-            res["roofline"]["measured_stream_error"] = repr(e)[:160]
+        if a.full:
+            try:
+                src = torch.zeros(1 << 30, dtype=torch.uint8, device=dev)
+                gbs = ctypes.c_double()
+                env["lib_mod"].check(env["lib_mod"].load().rml_probe_stream(env["lib_mod"].context(dev), env["lib_mod"].ptr(src), src.numel(), 20,
+                                                                              ctypes.byref(gbs), env["lib_mod"].stream_ptr(dev)), "rml_probe_stream")
+                del src
+                stream_gbs = float(gbs.value)
+                rows = [("primary", res)] + ([("walabot", wal)] if wal is not None else [])
+                for _, r in rows:
+                    for rf_ in [r["roofline"]] + ([r["uint8_ingest"]["roofline"]] if r.get("uint8_ingest") else []) + \
+                            [sr["roofline"] for sr in (r.get("slice_rows") or {}).values()]:
+                        rf_["measured_stream_GBs"] = round(stream_gbs, 1)
+                        rf_["frac_of_measured_stream"] = round(rf_["achieved"] / stream_gbs, 4)
+            except Exception as e:
+                res["roofline"]["measured_stream_error"] = repr(e)[:160]
         # ---- the output.  The verbose material ("doc") goes on an EARLIER line; the contract keys, the compact roofline /
         #      cpu_baseline objects and a one-screen summary of every row are the LAST line ----
         doc = {"config_detail": res["config"], "roofline": res["roofline"], "gemm_roofline": res["gemm_roofline"],
@@ -1278,7 +1319,8 @@ def main():
         if sgan_row is not None and "value" in sgan_row:
             summ["sgan_configs4"] = {"v": sgan_row["value"], "ms": sgan_row["ms_per_step"], "same": sgan_row["replicas_identical"],
                                      "mfma": sgan_row["roofline"]["frac"]}
-        summ["parity_gate"] = "pass" if not fails else fails
+        if a.full:                      # the gate's checks all belong to --full: a plain run compares nothing
+            summ["parity_gate"] = "pass" if not fails else fails
         rf = res["roofline"]
         cb = res["cpu_baseline"]
         line = {
@@ -1298,10 +1340,11 @@ def main():
                                                      "label_mismatch_vs_gpu": cb.get("label_mismatch_vs_gpu")},
             "summary": summ,
         }
-        # TWO lines: the verbose rows first, on a line of their own ({"doc": ...}; --doc-file also writes them to a file), and
-        # LAST the self-contained contract object, kept under 4 KB so that whatever the driver keeps of stdout holds all of it
+        # With --full TWO lines: the verbose rows first, on a line of their own ({"doc": ...}; --doc-file also writes them to a file), and
+        # LAST the self-contained contract object (a plain run prints that one alone), kept under 4 KB so that whatever the driver keeps of stdout holds all of it
         # (round 4 printed one 22.6 KB object and the driver could not parse it).
-        print(json.dumps({"doc": doc}))
+        if a.full:
+            print(json.dumps({"doc": doc}))
         if a.doc_file:
             os.makedirs(os.path.dirname(os.path.abspath(a.doc_file)), exist_ok=True)
             with open(a.doc_file, "w") as f:

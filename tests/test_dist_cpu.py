@@ -167,6 +167,49 @@ def test_bench_helpers_resolve_every_name_they_call():
         assert callable(getattr(bench_support, name))
 
 
+def test_bench_dump_outputs_writes_float_arrays_and_a_fixed_sample_above_the_limit(tmp_path):
+    """--dump-outputs: one .npy per output array, float32 / float64 only (labels exact as float64); above the size limit every array
+    keeps the same seeded sample of rows, written beside it, and two dumps of the same outputs are identical."""
+    sys.path.insert(0, ROOT)
+    import bench
+    g = torch.Generator().manual_seed(7)
+    out = {"dec_ovo": torch.randn(1000, 3, generator=g, dtype=torch.float64), "proba": torch.rand(1000, 3, generator=g),
+           "label_calib": torch.randint(0, 3, (1000,), generator=g, dtype=torch.int32)}
+    bench.dump_outputs(str(tmp_path / "all"), out)
+    assert sorted(os.listdir(tmp_path / "all")) == ["dec_ovo.npy", "label_calib.npy", "proba.npy"]
+    for k, t in out.items():
+        v = np.load(tmp_path / "all" / (k + ".npy"))
+        assert v.dtype in (np.float32, np.float64) and v.dtype == (np.float64 if k == "label_calib" else t.numpy().dtype)
+        np.testing.assert_array_equal(v, t.numpy())
+    limit = 20000
+    for d in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / d), out, limit=limit)
+    assert sum(os.path.getsize(tmp_path / "s1" / f) - 128 for f in os.listdir(tmp_path / "s1")) <= limit   # 128 B: the .npy header
+    for k, t in out.items():
+        rows = np.load(tmp_path / "s1" / (k + "_rows.npy"))
+        v = np.load(tmp_path / "s1" / (k + ".npy"))
+        assert rows.dtype == np.float64 and 0 < len(rows) < 1000 and np.all(np.diff(rows) > 0)
+        np.testing.assert_array_equal(v, t.numpy()[rows.astype(np.int64)].astype(v.dtype))
+        np.testing.assert_array_equal(rows, np.load(tmp_path / "s1" / "dec_ovo_rows.npy"))          # one sample for every array
+        np.testing.assert_array_equal(v, np.load(tmp_path / "s2" / (k + ".npy")))
+
+
+def test_bench_options(monkeypatch):
+    """--full is off by default; --steps below 1 is refused before any GPU work."""
+    sys.path.insert(0, ROOT)
+    import bench
+    plain = ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "0"]
+    monkeypatch.setattr(sys, "argv", plain)
+    a = bench.parse()
+    assert a.full is False and a.dump_outputs is None and a.steps == 3
+    monkeypatch.setattr(sys, "argv", plain + ["--full", "--dump-outputs", "d"])
+    a = bench.parse()
+    assert a.full is True and a.dump_outputs == "d"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "0"], cwd=ROOT,
+                       stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=300)
+    assert r.returncode == 2 and b"--steps must be >= 1" in r.stderr and not r.stdout
+
+
 def test_bench_refuses_more_ranks_than_devices():
     """`bench.py --gpus 8` on a box with fewer devices must fail loudly instead of printing an n_gpus = 1 line; a launcher whose
     WORLD_SIZE disagrees with --gpus is refused the same way (neither reaches the GPU work)."""

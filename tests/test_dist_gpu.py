@@ -46,7 +46,7 @@ def _line(out):
 
 def test_two_rank_bench_on_one_device_matches_the_single_process_run():
     per_rank = 1024
-    common = ["--steps", "2", "--warmup", "1", "--train", "1500", "--no-cpu", "--no-pmc", "--no-u8", "--parity", "256",
+    common = ["--full", "--steps", "2", "--warmup", "1", "--train", "1500", "--no-cpu", "--no-pmc", "--no-u8", "--parity", "256",
               "--general-frames", "512", "--dnn-frames", "512", "--dnn-parity", "64"]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     env.pop("RML_BENCH_ONE_DEVICE", None)
@@ -78,7 +78,7 @@ def test_eight_rank_bench_on_one_device_dry_run():
     control flow (model broadcast, eight slabs, label all-gather, general rows, CNN row, SGAN replicas with graph replay and the
     flat-bucket all-reduce).  No rate is asked of it."""
     per_rank, world = 512, 8
-    common = ["--steps", "1", "--warmup", "1", "--train", "1500", "--no-cpu", "--no-pmc", "--no-u8", "--no-slice", "--parity", "128",
+    common = ["--full", "--steps", "1", "--warmup", "1", "--train", "1500", "--no-cpu", "--no-pmc", "--no-u8", "--no-slice", "--parity", "128",
               "--general-frames", "256", "--dnn-frames", "256", "--dnn-parity", "32", "--dnn-train-steps", "40"]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     env.pop("RML_BENCH_ONE_DEVICE", None)
@@ -142,7 +142,7 @@ def test_two_rank_bench_over_rccl_when_two_devices_are_visible():
     if torch.cuda.device_count() < 2:
         pytest.skip("needs two visible devices (RCCL refuses two ranks on one)")
     per_rank = 1024
-    common = ["--steps", "2", "--warmup", "1", "--train", "1500", "--no-cpu", "--no-pmc", "--no-u8", "--parity", "256",
+    common = ["--full", "--steps", "2", "--warmup", "1", "--train", "1500", "--no-cpu", "--no-pmc", "--no-u8", "--parity", "256",
               "--general-frames", "512", "--dnn-frames", "512", "--dnn-parity", "64"]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     env.pop("RML_BENCH_ONE_DEVICE", None)

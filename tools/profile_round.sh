@@ -20,7 +20,7 @@ R=$PWD
 export TMPDIR=/tmp
 mkdir -p $R/gpurun_out
 cd /tmp
-COMMON="--no-cpu --no-pmc --parity 512 --steps 5 --warmup 2"
+COMMON="--full --no-cpu --no-pmc --parity 512 --steps 5 --warmup 2"
 prof() {   # prof <name> <command...>
     local name=$1; shift
     # bench.py prints two lines (verbose rows, contract line): its rows are read from the --doc-file JSON ({"doc": ..., "line": ...})
@@ -41,7 +41,7 @@ prof headline_u8 python $R/bench.py $COMMON --ingest u8 --no-walabot --no-genera
 prof walabot_u8 python $R/bench.py $COMMON --ingest u8 --grid 22x31x176 --frames 262144 --no-general --no-dnn --no-sgan
 prof general_rows python $R/bench.py $COMMON --frames 8192 --no-walabot --no-u8 --no-dnn --no-sgan
 prof gemm_alone python $R/tools/gemm_ab.py exact --grid 64x64x128 --svs 2562 --frames 23808 --rounds 2
-prof dnn python $R/bench.py --no-cpu --no-pmc --parity 256 --steps 5 --warmup 2 --frames 8192 --no-walabot --no-u8 --no-slice --no-general --no-sgan
+prof dnn python $R/bench.py --full --no-cpu --no-pmc --parity 256 --steps 5 --warmup 2 --frames 8192 --no-walabot --no-u8 --no-slice --no-general --no-sgan
 python - <<PY
 import json
 d = json.load(open("$R/gpurun_out/${TAG}_bench_dnn.json"))["doc"]["dnn_forward"]

@@ -6,7 +6,7 @@ for rep in 1 2; do
     if [ $lib = base ]; then export RML_LIB=$PWD/radar-ml_amd/libradarml_hip_base.so; else unset RML_LIB; fi
     for g in "64x64x128 65536" "22x31x176 262144"; do
       set -- $g
-      python bench.py --no-cpu --no-pmc --parity 256 --steps 5 --warmup 2 --grid $1 --frames $2 --no-walabot --no-u8 --no-general --no-dnn --no-sgan 2>/dev/null | tail -1 | python -c "
+      python bench.py --full --no-cpu --no-pmc --parity 256 --steps 5 --warmup 2 --grid $1 --frames $2 --no-walabot --no-u8 --no-general --no-dnn --no-sgan 2>/dev/null | tail -1 | python -c "
 import sys, json
 d = json.loads(sys.stdin.read())['summary']
 for g, r in d.items():

@@ -19,7 +19,7 @@ for round in 1 2; do
   for arm in new prev; do
     if [ $arm = prev ]; then export RML_LIB=$PREV; else unset RML_LIB; fi
     echo "## round $round arm $arm" >> $OUT/bench.log
-    python bench.py --no-dnn --no-sgan --no-general --no-u8 --no-slice --no-cpu --no-pmc --steps 10 --warmup 3 --parity 512 2>/dev/null | tail -1 | python -c "
+    python bench.py --full --no-dnn --no-sgan --no-general --no-u8 --no-slice --no-cpu --no-pmc --steps 10 --warmup 3 --parity 512 2>/dev/null | tail -1 | python -c "
 import json,sys
 d=json.loads(sys.stdin.readline()); s=d['summary']
 print(json.dumps({k:(v['f32']['v'],v['f32']['e2e'],v['f32']['roof']) for k,v in s.items() if isinstance(v,dict) and 'f32' in v}))" >> $OUT/bench.log

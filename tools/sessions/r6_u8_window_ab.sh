@@ -18,7 +18,7 @@ done
 for rep in 1 2; do
   for lib in base new; do
     if [ $lib = base ]; then export RML_LIB=$PWD/radar-ml_amd/libradarml_hip_base.so; else unset RML_LIB; fi
-    python bench.py --no-cpu --no-pmc --parity 256 --steps 5 --warmup 2 --no-slice --no-general --no-dnn --no-sgan 2>/dev/null | tail -1 | python -c "
+    python bench.py --full --no-cpu --no-pmc --parity 256 --steps 5 --warmup 2 --no-slice --no-general --no-dnn --no-sgan 2>/dev/null | tail -1 | python -c "
 import sys, json
 d = json.loads(sys.stdin.read())['summary']
 for g, r in d.items():
