@@ -324,6 +324,20 @@ int rml_augment(rml_ctx* ctx, int op, const float* src, int64_t B, int H, int W,
 int rml_svm_kernel_matrix(rml_ctx* ctx, const rml_svm* m, int path, const float* feat, int64_t ld_feat, int64_t N,
                           double* kmat, int64_t ld_k, void* stream);
 
+/* Kernel matrices of ONE set of rows against itself, every requested kernel from one pass over the inner products
+ * (the Gram service of an SVC grid search with kernel='precomputed'):
+ *   RML_GRAM_LINEAR  K[i][j] = x_i . x_j
+ *   RML_GRAM_RBF     K[i][j] = exp(-gamma_k * (x_i.x_i + x_j.x_j - 2 x_i.x_j))   (libsvm's formula, no clamp)
+ * float64 products and sums of the float32 rows.  feat: DEVICE N x ld_feat float32.  kinds / gammas: HOST, nk entries
+ * (gamma ignored for LINEAR; otherwise finite and >= 0), 1 <= nk <= 8.  out: DEVICE; matrix k at out + k * stride_k, row i at
+ * + i * ld_out (ld_out >= N, stride_k >= N * ld_out); only [0,N) x [0,N) of each is written.  Every matrix is bit-exactly
+ * symmetric.  Deterministic run to run.  N == 0 is a no-op.  Uses the context's workspace; asynchronous on `stream`. */
+#define RML_GRAM_LINEAR 0
+#define RML_GRAM_RBF    1
+int rml_gram(rml_ctx* ctx, const float* feat, int64_t ld_feat, int64_t N, int64_t D,
+             int nk, const int* kinds, const double* gammas,
+             double* out, int64_t ld_out, int64_t stride_k, void* stream);
+
 /* Fused front door: volumes -> projection (mode, mask fixed at load: D must match) ->
  * SVM outputs, features never returned to the caller.  Workspace is owned by the ctx and
  * grows on demand. */

@@ -66,6 +66,8 @@ SIGNATURES = {
     "rml_svm_set_platt": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
     "rml_svm_pairwise_proba": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
     "rml_svm_kernel_matrix": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p]),
+    "rml_gram": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_int64, c_int64,
+                         c_void_p]),
     "rml_project_svm": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_int, c_int, c_void_p, c_float,
                                 c_uint32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "rml_derive_project_svm": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_int, c_float, c_uint32, c_void_p,
@@ -137,6 +139,7 @@ VOL_F32, VOL_U8 = 0, 1
 MODES = {"max": MODE_MAX, "slice": MODE_SLICE, "sum": MODE_SUM, "max_nan": MODE_MAX_NAN}
 KERNEL_RBF, KERNEL_LINEAR = 0, 1
 PATH_AUTO, PATH_F32, PATH_I8, PATH_F64, PATH_DIGITS = 0, 1, 2, 3, 4
+GRAM_LINEAR, GRAM_RBF = 0, 1
 PATHS = {"auto": PATH_AUTO, "f32": PATH_F32, "i8": PATH_I8, "f64": PATH_F64, "digits": PATH_DIGITS}
 
 

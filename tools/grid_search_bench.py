@@ -1,0 +1,182 @@
+"""SVC grid search on GPU kernel matrices (GridSearchSVC, rml_gram): one JSON line.
+
+    python tools/grid_search_bench.py [--sets 1458,7290] [--jobs 4,16] [--sklearn]
+
+Two seeded synthetic training sets at the reference's feature length D = 10 010 (three planes of the Walabot grid):
+  1458 x 10010  rows on the code grid, float32(c/255) (the reference's balanced training set, train.py:534)
+  7290 x 10010  off-grid rows (its 4-epoch augmented set, train.py:496-517)
+and the reference's grid (5 linear + 25 RBF points, 5 stratified folds).  Per set:
+  gram_ms        rml_gram of the six distinct kernels in one call, HIP events; gram_frac = N(N+1)D FLOP / time / 78.6 TF
+  d2h_ms         the six N x N float64 matrices to the host
+  host_s_jJ      the search on the host (libsvm fits on the precomputed matrices) with n_jobs = J
+  total_s        one end-to-end GridSearchSVC.fit (upload, Gram, copy, search, refit) at the largest n_jobs
+--sklearn also runs scikit-learn's GridSearchCV on the raw rows of the 1458 set, on the sub-grid stated in the output (the full grid
+runs for about an hour), and reports its time and whether best_params_ agree with GridSearchSVC on the same sub-grid.
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+F64_PEAK = 78.6e12
+D = 10010
+CS = [0.01, 0.1, 1, 10, 100]
+GAMMAS = [0.001, 0.01, 0.1, 1, 10]
+GRID = [{"C": CS, "kernel": ["linear"]}, {"C": CS, "gamma": GAMMAS, "kernel": ["rbf"]}]
+SUB_GRID = [{"C": [1, 10], "kernel": ["linear"]}, {"C": [1, 10], "gamma": [0.001, 0.01], "kernel": ["rbf"]}]
+
+
+def synth(N, on_grid, seed):
+    """three balanced, overlapping classes of sparse radar-like rows: a shared blob pattern, a weak per-class one, per-row noise"""
+    rng = np.random.default_rng(seed)
+    y = np.arange(N) % 3
+    common = np.zeros(D)
+    common[rng.choice(D, 600, replace=False)] = rng.uniform(60, 255, 600)
+    tmpl = np.tile(common, (3, 1))
+    for c in range(3):
+        idx = rng.choice(D, 150, replace=False)
+        tmpl[c, idx] += rng.uniform(5, 20, 150)
+    X = tmpl[y] * rng.uniform(0.5, 1.0, (N, 1)) + rng.normal(0, 40, (N, D)) * (rng.random((N, D)) < 0.1)
+    X = np.clip(X, 0, 255)
+    if on_grid:
+        return (np.rint(X).astype(np.float32) / np.float32(255.0)), y
+    return np.clip(X / 255.0 + rng.normal(0, 0.02, (N, D)), 0.0, 1.0).astype(np.float32), y
+
+
+def progress(msg):
+    print("[grid_search_bench %s] %s" % (time.strftime("%H:%M:%S"), msg), file=sys.stderr, flush=True)
+
+
+def base_svc():
+    from sklearn import svm
+    return svm.SVC(probability=True, class_weight="balanced", random_state=1234, cache_size=1000, verbose=False)
+
+
+def gram_timing(rml, X, kernels, reps=3):
+    import torch
+    from radar_ml_amd import _lib
+    lib, ctx = _lib.load(), _lib.context()
+    N = X.shape[0]
+    kinds = np.array([_lib.GRAM_LINEAR if k == "linear" else _lib.GRAM_RBF for k, _ in kernels], dtype=np.int32)
+    gammas = np.array([0.0 if g is None else g for _, g in kernels], dtype=np.float64)
+    Xd = torch.from_numpy(X).cuda()
+    out = torch.empty((len(kernels), N, N), dtype=torch.float64, device="cuda")
+    call = lambda: _lib.check(lib.rml_gram(ctx, _lib.ptr(Xd), D, N, D, len(kernels), kinds.ctypes.data, gammas.ctypes.data,
+                                           _lib.ptr(out), N, N * N, _lib.stream_ptr()), "rml_gram")
+    call()                                  # warm-up (workspace growth, code load)
+    torch.cuda.synchronize()
+    ms = []
+    for _ in range(reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        call()
+        e1.record()
+        e1.synchronize()
+        ms.append(e0.elapsed_time(e1))
+    t0 = time.perf_counter()
+    host = out.cpu().numpy()
+    d2h = (time.perf_counter() - t0) * 1e3
+    del out, Xd
+    torch.cuda.empty_cache()
+    return min(ms), d2h, [host[k] for k in range(len(kernels))]
+
+
+def run_set(rml, N, on_grid, jobs, seed):
+    from sklearn.model_selection import StratifiedKFold
+    import radar_ml_amd.train as T
+    X, y = synth(N, on_grid, seed)
+    kernels = [("linear", None)] + [("rbf", float(g)) for g in GAMMAS]
+    gram_ms, d2h_ms, mats = gram_timing(rml, X, kernels)
+    progress("%d rows: rml_gram %.2f ms, copy %.0f ms" % (N, gram_ms, d2h_ms))
+    flop = float(N) * (N + 1) * D
+    res = {"rows": N, "D": D, "on_code_grid": on_grid, "kernels": len(kernels), "gram_ms": round(gram_ms, 3),
+           "gram_tflops": round(flop / gram_ms / 1e9, 2), "gram_frac": round(flop / (gram_ms * 1e-3) / F64_PEAK, 3),
+           "d2h_ms": round(d2h_ms, 1)}
+    cached = dict(zip(kernels, mats))
+    real = T._gram
+    best = None
+    for j in sorted(jobs)[:-1]:
+        T._gram = lambda Xh, ks, device=None: [cached[k] for k in ks]
+        try:
+            t0 = time.perf_counter()
+            gs = T.GridSearchSVC(base_svc(), GRID, cv=StratifiedKFold(5).split(X, y), n_jobs=j).fit(X, y)
+            res["host_s_j%d" % j] = round(time.perf_counter() - t0, 2)
+            progress("%d rows: host search at n_jobs=%d: %.2f s" % (N, j, res["host_s_j%d" % j]))
+            best = gs.best_params_
+        finally:
+            T._gram = real
+    del mats, cached
+    j = max(jobs)
+    spent = [0.0]
+
+    def timed(Xh, ks, device=None):
+        t = time.perf_counter()
+        try:
+            return real(Xh, ks, device)
+        finally:
+            spent[0] += time.perf_counter() - t
+    T._gram = timed
+    try:
+        t0 = time.perf_counter()
+        gs = T.GridSearchSVC(base_svc(), GRID, cv=StratifiedKFold(5).split(X, y), n_jobs=j).fit(X, y)
+        total = time.perf_counter() - t0
+    finally:
+        T._gram = real
+    res["host_s_j%d" % j] = round(total - spent[0], 2)
+    res["device_s"] = round(spent[0], 2)
+    res["total_s"] = round(total, 2)
+    progress("%d rows: end to end at n_jobs=%d: %.2f s" % (N, j, total))
+    res["best_params"] = gs.best_params_
+    res["best_score"] = round(gs.best_score_, 4)
+    if best is not None:
+        res["best_params_agree_across_jobs"] = best == gs.best_params_
+    return res, X, y
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--sets", default="1458,7290", help="training set sizes to run (1458: code grid, 7290: off-grid)")
+    ap.add_argument("--jobs", default="4,16", help="n_jobs values of the host search")
+    ap.add_argument("--sklearn", action="store_true", help="also time scikit-learn's GridSearchCV on the 1458 set (sub-grid)")
+    args = ap.parse_args()
+    import torch
+    import radar_ml_amd as rml
+    assert torch.cuda.is_available(), "needs a GPU"
+    jobs = [int(j) for j in args.jobs.split(",")]
+    t_all = time.perf_counter()
+    out = {"metric": "svc_grid_search", "grid": "5 linear + 25 rbf, 5 folds", "f64_peak_tflops": F64_PEAK / 1e12, "sets": []}
+    keep = None
+    for n in [int(s) for s in args.sets.split(",")]:
+        r, X, y = run_set(rml, n, n == 1458, jobs, seed=n)
+        out["sets"].append(r)
+        if n == 1458:
+            keep = (X, y)
+    if args.sklearn and keep is not None:
+        from sklearn.model_selection import GridSearchCV, StratifiedKFold
+        X, y = keep
+        j = max(jobs)
+        t0 = time.perf_counter()
+        ref = GridSearchCV(base_svc(), SUB_GRID, n_jobs=j, cv=StratifiedKFold(5).split(X, y)).fit(X, y)
+        t_sk = time.perf_counter() - t0
+        progress("scikit-learn GridSearchCV on the sub-grid: %.1f s" % t_sk)
+        t0 = time.perf_counter()
+        ours = rml.GridSearchSVC(base_svc(), SUB_GRID, n_jobs=j, cv=StratifiedKFold(5).split(X, y)).fit(X, y)
+        t_ours = time.perf_counter() - t0
+        same_splits = all(np.array_equal(ours.cv_results_["split%d_test_score" % k], ref.cv_results_["split%d_test_score" % k])
+                          for k in range(5))
+        out["sklearn"] = {"rows": int(X.shape[0]), "grid": "C {1, 10} linear + C {1, 10} x gamma {0.001, 0.01} rbf, 5 folds",
+                          "n_jobs": j, "sklearn_s": round(t_sk, 2), "gridsearchsvc_s": round(t_ours, 2),
+                          "speedup": round(t_sk / t_ours, 1), "best_params_agree": ours.best_params_ == ref.best_params_,
+                          "split_scores_identical": bool(same_splits), "best_params": ref.best_params_}
+    out["wall_s"] = round(time.perf_counter() - t_all, 1)
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()

@@ -40,6 +40,11 @@ static void phase_a_arguments() {
     CHECK(rml_svm_decision(nullptr, nullptr, 0, &f, 1, nullptr, 0, nullptr, nullptr, nullptr, 1, &d, nullptr, nullptr, nullptr, nullptr, nullptr) < 0);
     CHECK(rml_project_svm(nullptr, nullptr, &f, RML_VOL_F32, 1, 2, 2, 4, RML_MODE_MAX, nullptr, 255.f, RML_MASK_ALL, &d, nullptr, nullptr, nullptr, nullptr, nullptr) < 0);
     CHECK(rml_linear_load(nullptr, &d, &d, 3, 4, nullptr, nullptr, &lm) < 0);
+    {
+        const int kd[2] = {RML_GRAM_LINEAR, RML_GRAM_RBF};
+        const double gm[2] = {0.0, 0.5};
+        CHECK(rml_gram(nullptr, &f, 1, 1, 1, 2, kd, gm, &d, 1, 1, nullptr) == RML_ERR_INVALID && strlen(rml_last_error()) > 0);
+    }
     CHECK(rml_profile_read(nullptr, &n, &d, &n) < 0);
     CHECK(rml_probe_stream(nullptr, &f, 1 << 20, 1, &d, nullptr) < 0);
     CHECK(rml_ctx_set_option(nullptr, RML_OPT_PROJECT_SHARE_CU, 1) < 0);
@@ -152,6 +157,29 @@ static void phase_a_thread_local_errors() {
 // ---- phase B (a device is present) -----------------------------------------------------------------------------------------
 #define HIPCK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { fprintf(stderr, "HIP error %s at line %d\n", hipGetErrorString(e_), __LINE__); ++g_fail; return; } } while (0)
 
+// rml_gram's argument validation on a live context: every bad argument is a status and a message, before any device work
+static void phase_b_gram_arguments(rml_ctx* ctx) {
+    float f = 0; double d = 0;
+    const int kd[2] = {RML_GRAM_LINEAR, RML_GRAM_RBF}, bad_kind[2] = {RML_GRAM_LINEAR, 7};
+    const double gm[2] = {0.0, 0.5}, g_nan[2] = {0.0, NAN}, g_inf[2] = {0.0, INFINITY}, g_neg[2] = {0.0, -1.0};
+    const int64_t N = 4, D = 8;
+    CHECK(rml_gram(ctx, nullptr, D, N, D, 2, kd, gm, &d, N, N * N, nullptr) == RML_ERR_INVALID);
+    CHECK(rml_gram(ctx, &f, D, N, D, 2, kd, gm, nullptr, N, N * N, nullptr) == RML_ERR_INVALID);
+    CHECK(rml_gram(ctx, &f, D, N, D, 2, nullptr, gm, &d, N, N * N, nullptr) == RML_ERR_INVALID);
+    CHECK(rml_gram(ctx, &f, D, N, D, 2, kd, nullptr, &d, N, N * N, nullptr) == RML_ERR_INVALID);
+    CHECK(rml_gram(ctx, &f, D - 1, N, D, 2, kd, gm, &d, N, N * N, nullptr) == RML_ERR_INVALID);
+    CHECK(rml_gram(ctx, &f, D, N, D, 2, kd, gm, &d, N - 1, N * N, nullptr) == RML_ERR_INVALID);
+    CHECK(rml_gram(ctx, &f, D, N, D, 2, kd, gm, &d, N, N * N - 1, nullptr) == RML_ERR_INVALID);
+    CHECK(rml_gram(ctx, &f, D, N, D, 0, kd, gm, &d, N, N * N, nullptr) == RML_ERR_INVALID);
+    CHECK(rml_gram(ctx, &f, D, N, D, 9, kd, gm, &d, N, N * N, nullptr) == RML_ERR_INVALID);
+    CHECK(rml_gram(ctx, &f, D, N, D, 2, bad_kind, gm, &d, N, N * N, nullptr) == RML_ERR_INVALID);
+    CHECK(rml_gram(ctx, &f, D, N, D, 2, kd, g_nan, &d, N, N * N, nullptr) == RML_ERR_INVALID);
+    CHECK(rml_gram(ctx, &f, D, N, D, 2, kd, g_inf, &d, N, N * N, nullptr) == RML_ERR_INVALID);
+    CHECK(rml_gram(ctx, &f, D, N, D, 2, kd, g_neg, &d, N, N * N, nullptr) == RML_ERR_INVALID);
+    CHECK(strlen(rml_last_error()) > 0);
+    CHECK(rml_gram(ctx, nullptr, D, 0, D, 2, kd, gm, nullptr, 0, 0, nullptr) == RML_OK);       // N == 0: a no-op
+}
+
 static void phase_b(rml_ctx* ctx) {
     const int X = 22, Y = 31, Z = 176, C = 3;
     const int64_t B = 9000, M = 300;                   // two pipeline chunks (8192 + 808)
@@ -222,6 +250,7 @@ int main(int argc, char** argv) {
         printf("phase B: skipped, rml_ctx_create(0) = %d (%s)\n", rc, rml_last_error());
         if (need_device) { fprintf(stderr, "a device was required\n"); ++g_fail; }
     } else {
+        phase_b_gram_arguments(ctx);
         phase_b(ctx);
         CHECK(rml_ctx_destroy(ctx) == RML_OK);
     }
