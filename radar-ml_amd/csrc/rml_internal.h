@@ -256,6 +256,8 @@ struct rml_svm_pack {
 };
 int rml_svm_pack_host(const double* sv, int64_t M, int64_t D, const double* dual_coef, const int32_t* n_support,
                       int n_classes, int kernel, double gamma, double code_scale, bool has_calib, rml_svm* m, rml_svm_pack* pk);
+// bytes of the workspace of one chunk of CH rows (no HIP call).  needs: bit 0 code rows, 1 float rows, 2 digit planes, 3 derived (i,j,k)
+size_t rml_svm_ws_bytes(const rml_svm* m, int64_t CH, unsigned needs);
 
 struct rml_linear {
     int64_t D = 0;

@@ -1527,29 +1527,36 @@ int launch_gemm_ring(const rml_svm* m, const RingArgs& ra, hipStream_t st) {
     return RML_OK;
 }
 
-int launch_gemm_big(const rml_svm* m, const GemmArgs& ga, hipStream_t st) {
+RingArgs ring_args_from(const GemmArgs& ga) {
     RingArgs ra{};
     ra.sv = ga.sv; ra.x = ga.x; ra.ld_sv = ga.ld_sv; ra.ld_x = ga.ld_x; ra.KT = ga.KT;
     ra.N = ga.N; ra.Mpad = ga.Mpad; ra.sv_rows = ga.sv_rows; ra.ST = ga.ST; ra.FT = ga.FT;
     ra.tile_exact = ga.tile_exact; ra.want = ga.want; ra.x_isum = ga.x_isum; ra.x_isq = ga.x_isq;
     ra.sv_term = ga.sv_term; ra.W = ga.W; ra.gs = ga.gs; ra.kernel = ga.kernel; ra.partial = ga.partial; ra.Npart = ga.Npart;
-    return launch_gemm_ring<0>(m, ra, st);
+    return ra;
 }
+int launch_gemm_big(const rml_svm* m, const GemmArgs& ga, hipStream_t st) { return launch_gemm_ring<0>(m, ring_args_from(ga), st); }
+// the epilogue half of SmallArgs: dot products at G[m * g_sm + n * g_sn] -> partial sums
+SmallArgs small_args_from(const GemmArgs& ga, int32_t* G, int64_t g_sm, int64_t g_sn) {
+    SmallArgs sa{};
+    sa.N = (int)ga.N; sa.Mpad = ga.Mpad; sa.tile_exact = ga.tile_exact; sa.G = G; sa.g_sm = g_sm; sa.g_sn = g_sn;
+    sa.x_isum = ga.x_isum; sa.x_isq = ga.x_isq; sa.sv_term = ga.sv_term; sa.W = ga.W; sa.gs = ga.gs; sa.kernel = ga.kernel;
+    sa.partial = ga.partial; sa.Npart = ga.Npart;
+    return sa;
+}
+inline bool ring_takes(const rml_ctx* ctx, const rml_svm* m, int64_t n) { return use_big_gemm(m, n, ctx->num_cu, ctx->opt.gemm_big); }  // (its one caller)
 
 // Rows per chunk of the chunked front doors.  Where the 256x256 ring kernel runs (an exact model, or the multi-digit path) a
 // chunk costs ceil(tiles / CUs) rounds of one workgroup per CU, so the chunk size is chosen for the WHOLE batch: among the
 // multiples of 256 rows in 4096..32768 the one with the fewest rounds in total (full chunks + the remainder) plus a small charge
 // per chunk, the larger chunk on a tie.  Otherwise `fallback`.  RML_OPT_CHUNK overrides.
-int64_t pick_chunk_opt(const rml_ctx* ctx, int64_t fallback) {
-    const int64_t v = ctx->opt.chunk;
-    return v >= 128 ? round_up(v, kTile) : fallback;
-}
-
-int64_t pick_chunk(const rml_ctx* ctx, const rml_svm* m, int64_t rows, int64_t fallback, int num_cu, bool dig = false) {
+int64_t pick_chunk_opt(const rml_ctx* ctx, int64_t fallback) { return ctx->opt.chunk >= 128 ? round_up(ctx->opt.chunk, kTile) : fallback; }
+int64_t pick_chunk(const rml_ctx* ctx, const rml_svm* m, int64_t rows, int64_t fallback, bool dig) {
     const int64_t env = pick_chunk_opt(ctx, 0);
+    const int num_cu = ctx->num_cu;
     int64_t ch = fallback;
     if (env) ch = env;
-    else if (dig || (m->exact && use_big_gemm(m, 32768, num_cu, ctx->opt.gemm_big))) {
+    else if (dig || (m->exact && ring_takes(ctx, m, 32768))) {
         const int64_t st2 = (m->Mpad + kBig - 1) / kBig;
         auto rounds = [&](int64_t n) { return n <= 0 ? (int64_t)0 : (((n + kBig - 1) / kBig) * st2 + num_cu - 1) / num_cu; };
         // cost in units of a twentieth of a round: a chunk also costs its launches and a fill / drain in which the CUs run in
@@ -1582,63 +1589,111 @@ struct ChunkWs {
     size_t bytes;
 };
 
+// what an entry point wants in a chunk workspace beside statistics, tile predicate and partial sums: code rows (+ the scratch of the
+// small / split-K kernels), float rows, their digit planes (+ the ring kernel's scratch tiles), derived (i,j,k) per frame
+struct ChunkNeeds { bool q, f32, dig, ijk; };
 constexpr int64_t kSplitRows = 2048;        // the split-K path serves chunks of at most this many rows
 
-ChunkWs carve(const rml_svm* m, int64_t CH, unsigned char* base, bool need_q, bool need_f32, bool need_dig = false, bool need_ijk = false) {
-    ChunkWs w{};
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off = (off + bytes + 255) & ~(size_t)255; return base ? base + o : (unsigned char*)nullptr; };
-    w.q = (uint8_t*)take(need_q ? (size_t)CH * m->Dq : 0);
-    w.f32 = (float*)take(need_f32 ? (size_t)CH * m->Df * 4 : 0);
-    w.isum = (int32_t*)take((size_t)CH * 4);
-    w.isq = (int64_t*)take((size_t)CH * 8);
-    w.nsq = (double*)take((size_t)CH * 8);
-    w.flags = (int32_t*)take((size_t)CH * 4);
-    w.tile_exact = (int32_t*)take((size_t)(CH / kTile + 1) * 4);
-    w.all_exact = (int32_t*)take(256);
+// base == NULL: the size only (every pointer NULL).  A part that is not needed takes no bytes and is NULL.
+ChunkWs carve(const rml_svm* m, int64_t CH, unsigned char* base, const ChunkNeeds& need) {
+    ChunkWs w{}; size_t off = 0;
+    auto take = [&](size_t bytes) { size_t o = off; off = (off + bytes + 255) & ~(size_t)255; return base && bytes ? base + o : (unsigned char*)nullptr; };
+    w.q = (uint8_t*)take(need.q ? (size_t)CH * m->Dq : 0);
+    w.f32 = (float*)take(need.f32 ? (size_t)CH * m->Df * 4 : 0);
+    w.isum = (int32_t*)take((size_t)CH * 4); w.isq = (int64_t*)take((size_t)CH * 8);
+    w.nsq = (double*)take((size_t)CH * 8); w.flags = (int32_t*)take((size_t)CH * 4);
+    w.tile_exact = (int32_t*)take((size_t)(CH / kTile + 1) * 4); w.all_exact = (int32_t*)take(256);
     w.partial = (double*)take((size_t)(m->Mpad / kTile) * CH * m->PT * 8);
     w.dig_plane = CH * m->Dq;
-    w.dig = (int8_t*)take(need_dig ? (size_t)4 * CH * m->Dq : 0);
-    w.dnsq = (double*)take(need_dig ? (size_t)CH * 8 : 0);
-    w.dflags = (int32_t*)take(need_dig ? (size_t)CH * 4 : 0);
-    w.stash = (int32_t*)take(need_dig ? (size_t)ring_grid((int)((CH + kBig - 1) / kBig), (int)((m->Mpad + kBig - 1) / kBig)) * 2 * kDigStashBytes : 0);
-    if (!need_dig) { w.dig = nullptr; w.dnsq = nullptr; w.dflags = nullptr; w.stash = nullptr; }
-    w.ijk = (int32_t*)take(need_ijk ? (size_t)CH * 12 : 0);
-    if (!need_ijk) w.ijk = nullptr;
-    w.gsmall = (int32_t*)take(need_q ? (size_t)RML_SMALL_FRAMES * m->Mpad * 4 : 0);
-    if (!need_q) w.gsmall = nullptr;
-    const bool need_split = need_q && CH <= kSplitRows;
-    w.gsplit = (int32_t*)take(need_split ? (size_t)m->Mpad * CH * 4 : 0);
-    if (!need_split) w.gsplit = nullptr;
+    w.dig = (int8_t*)take(need.dig ? (size_t)4 * CH * m->Dq : 0);
+    w.dnsq = (double*)take(need.dig ? (size_t)CH * 8 : 0); w.dflags = (int32_t*)take(need.dig ? (size_t)CH * 4 : 0);
+    w.stash = (int32_t*)take(need.dig ? (size_t)ring_grid((int)((CH + kBig - 1) / kBig), (int)((m->Mpad + kBig - 1) / kBig)) * 2 * kDigStashBytes : 0);
+    w.ijk = (int32_t*)take(need.ijk ? (size_t)CH * 12 : 0);
+    w.gsmall = (int32_t*)take(need.q ? (size_t)RML_SMALL_FRAMES * m->Mpad * 4 : 0);
+    w.gsplit = (int32_t*)take(need.q && CH <= kSplitRows ? (size_t)m->Mpad * CH * 4 : 0);
     w.bytes = off;
     return w;
 }
 
+// the only caller of carve: size -> rml_ws_reserve -> w[0..nbuf) back to back, then `extra` bytes of the caller's own at *extra_at
+int reserve_chunks(rml_ctx* ctx, const rml_svm* m, int64_t CH, const ChunkNeeds& need, hipStream_t st, ChunkWs* w, int nbuf,
+                   size_t extra = 0, void** extra_at = nullptr) {
+    const size_t each = carve(m, CH, nullptr, need).bytes;
+    void* ws = nullptr;
+    if (int rc = rml_ws_reserve(ctx, (size_t)nbuf * each + extra, &ws, st)) return rc;
+    unsigned char* base = static_cast<unsigned char*>(ws);
+    for (int i = 0; i < nbuf; ++i) w[i] = carve(m, CH, base + (size_t)i * each, need);
+    if (extra_at) *extra_at = base + (size_t)nbuf * each;
+    return RML_OK;
+}
+
 struct DecisionOut {
     double* dec_ovo; double* dec_ovr; double* proba; int32_t* label_vote; int32_t* label_calib;
-    DecisionOut at(int64_t r0, int C, int P) const {
-        DecisionOut o = *this;
-        if (o.dec_ovo) o.dec_ovo += r0 * P;
-        if (o.dec_ovr) o.dec_ovr += r0 * (C == 2 ? 1 : C);
-        if (o.proba) o.proba += r0 * C;
-        if (o.label_vote) o.label_vote += r0;
-        if (o.label_calib) o.label_calib += r0;
-        return o;
+    DecisionOut at(int64_t r0, int C, int P) const {       // the outputs of rows r0...
+        auto adv = [r0](auto* p, int64_t per_row) { return p ? p + r0 * per_row : p; };
+        return DecisionOut{adv(dec_ovo, P), adv(dec_ovr, C == 2 ? 1 : C), adv(proba, C), adv(label_vote, 1), adv(label_calib, 1)};
     }
 };
 
-// GEMM(s) + finish for one chunk whose operands are already in place.
+// The n rows of one chunk, already in place: code rows + their statistics (q NULL: none), per row "on the code grid?" (NULL: not
+// known per row), float rows of stride m->Df + squared norms (f32 NULL: none).  ws_rows: the first n rows of a chunk workspace.
+struct ChunkOps { int64_t n; const uint8_t* q; int64_t ld_q; const int32_t* isum; const int64_t* isq; const int32_t* flags; const float* f32; const double* nsq; };
+ChunkOps ws_rows(const rml_svm* m, const ChunkWs& w, int64_t n) { return ChunkOps{n, w.q, m->Dq, w.isum, w.isq, w.flags, w.f32, w.nsq}; }
+
+// What to do with a chunk.  The entry point fills the first group (a ChunkPlan{} asks for nothing: set what is meant, by name);
+// plan_chunk derives the second from it, and is the only place that does.
+struct ChunkPlan {
+    int policy;             // RML_PATH_AUTO (i8 on exact tiles, f64 elsewhere) / _F32 / _I8 / _F64 / _DIGITS (forced)
+    bool tiles_done;        // w.tile_exact is already decided (launch_tile_flags at plan_chunk's group): run_chunk launches no flag kernel
+    bool all_exact_known;   // every row is on the code grid by construction (uint8 volumes): no tile predicate at all
+    bool allow_big;         // the 256x256 ring kernel may take the exact tiles (not beside a persistent projection: it fills a CU)
+    bool dig_ready;         // the digit planes of the float rows are in w.dig
+    double* kmat; int64_t ld_k;     // kernel values K[n][m] of the chunk's rows instead of decisions (rml_svm_kernel_matrix), or NULL
+    int FT, ST, group; bool run_i8, run_gen, gen_f32, big, run_dig, small, split;      // derived: see plan_chunk
+};
+
+// No allocation, no lock, no HIP call: run_chunk is entered with a const ctx and from inside a stream capture.
+ChunkPlan plan_chunk(const rml_ctx* ctx, const rml_svm* m, ChunkPlan p, const ChunkOps& x, const ChunkWs& w) {
+    p.FT = (int)((x.n + kTile - 1) / kTile); p.ST = (int)(m->Mpad / kTile);             // sample tiles, SV tiles
+    p.run_i8 = m->exact && x.q && (p.policy == RML_PATH_AUTO || p.policy == RML_PATH_I8);
+    p.run_gen = x.f32 && p.policy != RML_PATH_I8; p.gen_f32 = (p.policy == RML_PATH_F32);
+    // large exact batches go to the 256x256 kernel; the tile predicate is then decided per pair of 128-sample tiles
+    p.big = p.allow_big && p.run_i8 && !p.kmat && ring_takes(ctx, m, x.n);
+    // general tiles whose rows fit the model's fixed-point range go to the multi-digit int8 kernel (digit planes in w.dig)
+    p.run_dig = p.dig_ready && w.dig && p.run_gen && !p.gen_f32 && !p.kmat && m->dig_ok;
+    p.group = (p.big || p.run_dig) ? 2 : 1;             // sample tiles per entry of the tile predicate
+    // a handful of rows: the matrix-vector kernels (the SV codes read once by the whole chip instead of by Mpad / 128 workgroups)
+    p.small = p.run_i8 && !p.kmat && x.n <= RML_SMALL_FRAMES && w.gsmall && (m->Mpad % kSmallSv) == 0;
+    // ... and batches whose 128 x 128 tiles are fewer than the CUs: the same tiles cut along K (exact: any order)
+    p.split = p.run_i8 && !p.kmat && !p.small && !p.big && w.gsplit && x.n <= kSplitRows && (int64_t)p.FT * p.ST < ctx->num_cu &&
+              m->Kq / kStepBytes >= 8;
+    return p;
+}
+
+// the tile predicate of a chunk at the plan's granularity; with all_exact ONE MORE block that writes the AND of every row flag there
+void launch_tile_flags(const rml_svm* m, const ChunkOps& x, const ChunkPlan& p, const ChunkWs& w, int32_t* all_exact, hipStream_t st) {
+    const int blocks = (p.FT + p.group - 1) / p.group + (all_exact ? 1 : 0);
+    hipLaunchKernelGGL(k_tile_flags, dim3(blocks), dim3(128 * p.group), 0, st, x.flags, x.n, p.FT, p.run_i8 ? (p.run_gen ? 0 : 2) : 1,
+                       (int)m->exact, w.tile_exact, all_exact, p.group);
+}
+void launch_tile_dig(const ChunkOps& x, const ChunkPlan& p, const ChunkWs& w, hipStream_t st) {
+    hipLaunchKernelGGL(k_tile_dig, dim3((p.FT + 1) / 2), dim3(256), 0, st, w.dflags, x.n, p.FT, w.tile_exact, (const int32_t*)nullptr);
+}
+// digit planes of the n float rows in w.f32
+void launch_digit_rows(const rml_svm* m, const ChunkWs& w, int64_t n, hipStream_t st) {
+    hipLaunchKernelGGL(k_digit_rows, dim3((unsigned)n), dim3(256), 0, st, w.f32, m->Df, m->D, m->Dq, w.dig_plane, w.dig, w.dnsq,
+                       w.dflags, m->dig_c0, 2147483648.0 / m->dig_s, (const int32_t*)nullptr);
+}
+
 // the epilogue of a chunk: partial sums of every SV tile -> decision values, votes, calibrated probabilities, labels
-int run_finish(const rml_svm* m, int64_t n, const int32_t* flags, const ChunkWs& w, const DecisionOut& out, hipStream_t st,
-               bool all_exact_known, bool forced_i8) {
+int run_finish(const rml_svm* m, const ChunkOps& x, const ChunkPlan& p, const ChunkWs& w, const DecisionOut& out, hipStream_t st) {
     FinishArgs fa{};
-    fa.partial = w.partial; fa.Npart = n; fa.ST = (int)(m->Mpad / kTile); fa.PT = m->PT; fa.N = n; fa.C = m->C; fa.P = m->P;
+    fa.partial = w.partial; fa.Npart = x.n; fa.ST = p.ST; fa.PT = m->PT; fa.N = x.n; fa.C = m->C; fa.P = m->P;
     fa.intercept = m->intercept; fa.calib = m->calib; fa.has_calib = m->has_calib;
-    fa.row_flags = all_exact_known ? nullptr : flags; fa.tile_exact = all_exact_known ? nullptr : w.tile_exact;
-    fa.forced_i8 = forced_i8;
-    fa.dec_ovo = out.dec_ovo; fa.dec_ovr = out.dec_ovr; fa.proba = out.proba;
-    fa.label_vote = out.label_vote; fa.label_calib = out.label_calib;
-    hipLaunchKernelGGL(k_svm_finish, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, fa);
+    fa.row_flags = p.all_exact_known ? nullptr : x.flags; fa.tile_exact = p.all_exact_known ? nullptr : w.tile_exact;
+    fa.forced_i8 = p.run_i8 && !p.run_gen;
+    fa.dec_ovo = out.dec_ovo; fa.dec_ovr = out.dec_ovr; fa.proba = out.proba; fa.label_vote = out.label_vote; fa.label_calib = out.label_calib;
+    hipLaunchKernelGGL(k_svm_finish, dim3((unsigned)((x.n + 255) / 256)), dim3(256), 0, st, fa);
     RML_HIP(hipGetLastError());
     return RML_OK;
 }
@@ -1659,11 +1714,8 @@ int launch_epi(const rml_svm* m, const SmallArgs& sa, int ST, int64_t n, hipStre
 
 // the exact path for n <= RML_SMALL_FRAMES rows: k_svm_dot_small + k_svm_epi_small (bit-identical partial sums: see the kernels)
 int launch_small(const rml_svm* m, const GemmArgs& ga, int32_t* G, hipStream_t st) {
-    SmallArgs sa{};
+    SmallArgs sa = small_args_from(ga, G, 1, ga.Mpad);
     sa.sv = ga.sv; sa.ld_sv = ga.ld_sv; sa.x = ga.x; sa.ld_x = ga.ld_x; sa.Kb = (int64_t)ga.KT * kStepBytes;
-    sa.N = (int)ga.N; sa.Mpad = ga.Mpad; sa.tile_exact = ga.tile_exact; sa.G = G; sa.g_sm = 1; sa.g_sn = ga.Mpad;
-    sa.x_isum = ga.x_isum; sa.x_isq = ga.x_isq; sa.sv_term = ga.sv_term; sa.W = ga.W; sa.gs = ga.gs; sa.kernel = ga.kernel;
-    sa.partial = ga.partial; sa.Npart = ga.Npart;
     const dim3 gd((unsigned)(ga.Mpad / kSmallSv));
     if (ga.N <= 1) hipLaunchKernelGGL(k_svm_dot_small<1>, gd, dim3(256), 0, st, sa);
     else if (ga.N <= 2) hipLaunchKernelGGL(k_svm_dot_small<2>, gd, dim3(256), 0, st, sa);
@@ -1677,10 +1729,8 @@ int launch_split(const rml_svm* m, const GemmArgs& ga, int32_t* G, int num_cu, h
     const int64_t ldg = (int64_t)ga.FT * kTile;
     // (a kernel, not hipMemsetAsync: the memset of a captured stream was not replayed with the graph -- the second replay added
     // onto the first one's sums, tests/test_capi_gpu.py)
-    {
-        const int64_t n16 = ga.Mpad * ldg / 4;             // Mpad and ldg are multiples of 128
-        hipLaunchKernelGGL(k_zero16, dim3((unsigned)((n16 + 255) / 256)), dim3(256), 0, st, reinterpret_cast<v4i*>(G), n16);
-    }
+    const int64_t n16 = ga.Mpad * ldg / 4;                 // Mpad and ldg are multiples of 128
+    hipLaunchKernelGGL(k_zero16, dim3((unsigned)((n16 + 255) / 256)), dim3(256), 0, st, reinterpret_cast<v4i*>(G), n16);
     SplitArgs sp{};
     sp.sv = ga.sv; sp.ld_sv = ga.ld_sv; sp.x = ga.x; sp.ld_x = ga.ld_x; sp.KT = ga.KT; sp.N = ga.N; sp.FT = ga.FT;
     sp.tile_exact = ga.tile_exact; sp.G = G; sp.ldg = ldg;
@@ -1691,78 +1741,57 @@ int launch_split(const rml_svm* m, const GemmArgs& ga, int32_t* G, int num_cu, h
     sp.per = (ga.KT + KS - 1) / KS;
     KS = (ga.KT + sp.per - 1) / sp.per;
     hipLaunchKernelGGL(k_svm_gemm_splitk, dim3((unsigned)tiles, (unsigned)KS), dim3(256), 0, st, sp);
-    SmallArgs sa{};
-    sa.N = (int)ga.N; sa.Mpad = ga.Mpad; sa.tile_exact = ga.tile_exact; sa.G = G; sa.g_sm = ldg; sa.g_sn = 1;
-    sa.x_isum = ga.x_isum; sa.x_isq = ga.x_isq; sa.sv_term = ga.sv_term; sa.W = ga.W; sa.gs = ga.gs; sa.kernel = ga.kernel;
-    sa.partial = ga.partial; sa.Npart = ga.Npart;
-    return launch_epi(m, sa, ga.ST, ga.N, st);
+    return launch_epi(m, small_args_from(ga, G, ldg, 1), ga.ST, ga.N, st);
 }
 
-int run_chunk(const rml_ctx* ctx, const rml_svm* m, int policy, int64_t n, const uint8_t* q, int64_t ld_q, const int32_t* isum, const int64_t* isq,
-              const int32_t* flags, const float* f32, const double* nsq, const ChunkWs& w, const DecisionOut& out, hipStream_t st,
-              bool tiles_done = false, double* kmat = nullptr, int64_t ld_k = 0, bool all_exact_known = false, bool allow_big = true,
-              bool dig_ready = false, bool defer_finish = false) {
-    const int FT = (int)((n + kTile - 1) / kTile);
-    const int ST = (int)(m->Mpad / kTile);
-    // policy: RML_PATH_AUTO (i8 on exact tiles, f64 elsewhere) / _F32 / _I8 / _F64 (forced)
-    const bool run_i8 = m->exact && q && (policy == RML_PATH_AUTO || policy == RML_PATH_I8);
-    const bool run_gen = f32 && policy != RML_PATH_I8;
-    const bool gen_f32 = (policy == RML_PATH_F32);
-    RML_REQUIRE(run_i8 || run_gen, RML_ERR_STATE, "svm: no usable operand path (model exact=%d)", (int)m->exact);
-    // large exact batches go to the 256x256 kernel; the tile predicate is then decided per pair of 128-sample tiles
-    const int gemm_cus = ctx->num_cu;
-    const bool big = allow_big && run_i8 && !kmat && use_big_gemm(m, n, gemm_cus, ctx->opt.gemm_big);
-    // general tiles whose rows fit the model's fixed-point range go to the multi-digit int8 kernel (digit planes in w.dig)
-    const bool run_dig = dig_ready && w.dig && run_gen && !gen_f32 && !kmat && m->dig_ok;
-    if (!tiles_done) {
-        const int group = (big || run_dig) ? 2 : 1;
-        hipLaunchKernelGGL(k_tile_flags, dim3((FT + group - 1) / group), dim3(128 * group), 0, st, flags, n, FT,
-                           run_i8 ? (run_gen ? 0 : 2) : 1, (int)m->exact, w.tile_exact, (int32_t*)nullptr, group);
-        if (run_dig)
-            hipLaunchKernelGGL(k_tile_dig, dim3((FT + 1) / 2), dim3(256), 0, st, w.dflags, n, FT, w.tile_exact, (const int32_t*)nullptr);
+// the multi-digit operands of a chunk: the model's digit planes against w.dig, general tiles only (tile_exact == 2)
+RingArgs digit_args(const rml_svm* m, const ChunkOps& x, const ChunkPlan& p, const ChunkWs& w) {
+    RingArgs ra{};
+    ra.sv = reinterpret_cast<const uint8_t*>(m->sv_dig); ra.x = reinterpret_cast<const uint8_t*>(w.dig);
+    ra.ld_sv = m->Dq; ra.ld_x = m->Dq; ra.sv_plane = m->Mpad * m->Dq; ra.x_plane = w.dig_plane;
+    ra.KT = (int)(m->Kq / kStepBytes); ra.N = x.n; ra.Mpad = m->Mpad; ra.sv_rows = m->Mpad; ra.ST = p.ST; ra.FT = p.FT;
+    ra.tile_exact = w.tile_exact; ra.want = 2; ra.x_nsq = w.dnsq; ra.sv_term = m->sv_dig_nsq; ra.W = m->W;
+    ra.gs = m->gamma * m->dig_s * m->dig_s; ra.kernel = RML_KERNEL_RBF; ra.partial = w.partial; ra.Npart = x.n; ra.stash = w.stash;
+    return ra;
+}
+
+// GEMM(s) + finish for one chunk whose operands are already in place.
+int run_chunk(const rml_ctx* ctx, const rml_svm* m, const ChunkOps& x, const ChunkPlan& asked, const ChunkWs& w, const DecisionOut& out,
+              hipStream_t st) {
+    const ChunkPlan p = plan_chunk(ctx, m, asked, x, w);
+    RML_REQUIRE(p.run_i8 || p.run_gen, RML_ERR_STATE, "svm: no usable operand path (model exact=%d)", (int)m->exact);
+    if (!p.tiles_done) {
+        launch_tile_flags(m, x, p, w, nullptr, st);
+        if (p.run_dig) launch_tile_dig(x, p, w, st);
     }
     GemmArgs ga{};
-    // all_exact_known: every row is on the code grid by construction (uint8 volumes): no tile predicate at all
-    ga.N = n; ga.ST = ST; ga.FT = FT; ga.tile_exact = all_exact_known ? nullptr : w.tile_exact;
-    ga.W = m->W; ga.Mpad = m->Mpad; ga.kernel = m->kernel; ga.partial = w.partial; ga.Npart = n;
-    ga.kmat = kmat; ga.ld_k = ld_k; ga.M = m->M; ga.sv_rows = m->Mpad;
-    if (run_i8) {
-        ga.sv = m->sv_q; ga.ld_sv = m->Dq; ga.x = q; ga.ld_x = ld_q; ga.KT = (int)(m->Kq / kStepBytes);
-        ga.want = 1; ga.x_isum = isum; ga.x_isq = isq; ga.sv_term = m->sv_term_q;
-        const double sc2 = m->code_scale * m->code_scale;
-        ga.gs = (m->kernel == RML_KERNEL_RBF ? m->gamma : 1.0) / sc2;
-        // a handful of rows: the matrix-vector kernels (the SV codes read once by the whole chip instead of by Mpad / 128 workgroups)
-        const bool small = !kmat && n <= RML_SMALL_FRAMES && w.gsmall && (m->Mpad % kSmallSv) == 0;
-        // ... and batches whose 128 x 128 tiles are fewer than the CUs: the same tiles cut along K (exact: any order)
-        const bool split = !kmat && !small && !big && w.gsplit && n <= kSplitRows && (int64_t)FT * ST < gemm_cus && ga.KT >= 8;
-        int rc = kmat ? launch_gemm<PATH_I8, true>(m, ga, st)
-                      : (small ? launch_small(m, ga, w.gsmall, st)
-                               : (split ? launch_split(m, ga, w.gsplit, gemm_cus, st)
-                                        : (big ? launch_gemm_big(m, ga, st) : launch_gemm<PATH_I8>(m, ga, st))));
+    ga.N = x.n; ga.ST = p.ST; ga.FT = p.FT; ga.tile_exact = p.all_exact_known ? nullptr : w.tile_exact;
+    ga.W = m->W; ga.Mpad = m->Mpad; ga.kernel = m->kernel; ga.partial = w.partial; ga.Npart = x.n;
+    ga.kmat = p.kmat; ga.ld_k = p.ld_k; ga.M = m->M; ga.sv_rows = m->Mpad;
+    int rc = RML_OK;
+    if (p.run_i8) {
+        ga.sv = m->sv_q; ga.ld_sv = m->Dq; ga.x = x.q; ga.ld_x = x.ld_q; ga.KT = (int)(m->Kq / kStepBytes);
+        ga.want = 1; ga.x_isum = x.isum; ga.x_isq = x.isq; ga.sv_term = m->sv_term_q;
+        ga.gs = (m->kernel == RML_KERNEL_RBF ? m->gamma : 1.0) / (m->code_scale * m->code_scale);
+        if (p.kmat) rc = launch_gemm<PATH_I8, true>(m, ga, st);
+        else if (p.small) rc = launch_small(m, ga, w.gsmall, st);
+        else if (p.split) rc = launch_split(m, ga, w.gsplit, ctx->num_cu, st);
+        else if (p.big) rc = launch_gemm_big(m, ga, st);
+        else rc = launch_gemm<PATH_I8>(m, ga, st);
         if (rc) return rc;
     }
-    if (run_dig) {
-        RingArgs ra{};
-        ra.sv = reinterpret_cast<const uint8_t*>(m->sv_dig); ra.x = reinterpret_cast<const uint8_t*>(w.dig);
-        ra.ld_sv = m->Dq; ra.ld_x = m->Dq; ra.sv_plane = m->Mpad * m->Dq; ra.x_plane = w.dig_plane;
-        ra.KT = (int)(m->Kq / kStepBytes); ra.N = n; ra.Mpad = m->Mpad; ra.sv_rows = m->Mpad; ra.ST = ST; ra.FT = FT;
-        ra.tile_exact = w.tile_exact; ra.want = 2; ra.x_nsq = w.dnsq; ra.sv_term = m->sv_dig_nsq; ra.W = m->W;
-        ra.gs = m->gamma * m->dig_s * m->dig_s; ra.kernel = RML_KERNEL_RBF; ra.partial = w.partial; ra.Npart = n; ra.stash = w.stash;
-        int rc = launch_gemm_ring<1>(m, ra, st);
-        if (rc) return rc;
-    }
-    if (run_gen) {
+    if (p.run_dig && (rc = launch_gemm_ring<1>(m, digit_args(m, x, p, w), st))) return rc;
+    if (p.run_gen) {
         ga.sv = reinterpret_cast<const uint8_t*>(m->sv_f32); ga.ld_sv = m->Df * 4;
-        ga.x = reinterpret_cast<const uint8_t*>(f32); ga.ld_x = m->Df * 4; ga.KT = (int)(m->Kf * 4 / kStepBytes);
-        ga.want = 0; ga.x_nsq = nsq; ga.sv_term = m->sv_nsq; ga.gs = m->gamma;
-        int rc = gen_f32 ? launch_gemm<PATH_F32>(m, ga, st)
-                         : (kmat ? launch_gemm<PATH_F64, true>(m, ga, st) : launch_gemm<PATH_F64>(m, ga, st));
+        ga.x = reinterpret_cast<const uint8_t*>(x.f32); ga.ld_x = m->Df * 4; ga.KT = (int)(m->Kf * 4 / kStepBytes);
+        ga.want = 0; ga.x_nsq = x.nsq; ga.sv_term = m->sv_nsq; ga.gs = m->gamma;
+        rc = p.gen_f32 ? launch_gemm<PATH_F32>(m, ga, st)
+                       : (p.kmat ? launch_gemm<PATH_F64, true>(m, ga, st) : launch_gemm<PATH_F64>(m, ga, st));
         if (rc) return rc;
     }
-    if (kmat || defer_finish) { RML_HIP(hipGetLastError()); return RML_OK; }      // kernel values only, or the caller launches run_finish itself
-    return run_finish(m, n, flags, w, out, st, all_exact_known, run_i8 && !run_gen);
+    if (p.kmat) { RML_HIP(hipGetLastError()); return RML_OK; }      // kernel values only
+    return run_finish(m, x, p, w, out, st);
 }
-
 }  // namespace
 
 // ---- model load ---------------------------------------------------------------------------
@@ -1936,7 +1965,30 @@ extern "C" int rml_svm_is_exact(const rml_svm* m) { return m && m->exact ? 1 : 0
 extern "C" int64_t rml_svm_num_sv(const rml_svm* m) { return m ? m->M : 0; }
 extern "C" int64_t rml_svm_dim(const rml_svm* m) { return m ? m->D : 0; }
 
+// the size of one chunk workspace (tools/sanitize pins the layout with it).  needs: bit 0 code rows, 1 float rows, 2 digit planes, 3 ijk
+size_t rml_svm_ws_bytes(const rml_svm* m, int64_t CH, unsigned needs) {
+    return carve(m, CH, nullptr, ChunkNeeds{(needs & 1u) != 0, (needs & 2u) != 0, (needs & 4u) != 0, (needs & 8u) != 0}).bytes;
+}
+
 // ---- decision on caller-provided rows -----------------------------------------------------
+namespace {
+// float rows of a caller, chunk by chunk: k_prepare_rows (and the digit planes, where the workspace has room for them) into w, then
+// run_chunk; with plan.kmat the kernel values of the rows instead of decisions
+int run_float_rows(const rml_ctx* ctx, const rml_svm* m, const float* feat, int64_t ld_feat, int64_t N, int64_t CH, const ChunkWs& w,
+                   const ChunkPlan& plan, const DecisionOut& out, hipStream_t st) {
+    for (int64_t r0 = 0; r0 < N; r0 += CH) {
+        const int64_t n = std::min(CH, N - r0);
+        hipLaunchKernelGGL(k_prepare_rows, dim3((unsigned)n), dim3(256), 0, st, feat + r0 * ld_feat, ld_feat, m->D,
+                           (float)m->code_scale, w.f32, m->Df, w.nsq, w.q, m->Dq, w.isum, w.isq, w.flags);
+        if (w.dig) launch_digit_rows(m, w, n, st);
+        RML_HIP(hipGetLastError());
+        ChunkPlan p = plan; if (p.kmat) p.kmat += r0 * p.ld_k;
+        if (int rc = run_chunk(ctx, m, ws_rows(m, w, n), p, w, out.at(r0, m->C, m->P), st)) return rc;
+    }
+    return RML_OK;
+}
+}  // namespace
+
 extern "C" int rml_svm_decision(rml_ctx* ctx, const rml_svm* m, int path,
                                 const float* feat, int64_t ld_feat,
                                 const uint8_t* feat_q, int64_t ld_q, const int32_t* row_isum, const int64_t* row_isq,
@@ -1960,43 +2012,29 @@ extern "C" int rml_svm_decision(rml_ctx* ctx, const rml_svm* m, int path,
                     "rml_svm_decision: code rows need ld_q >= %lld, ld_q %% 16 == 0 and 16-byte alignment", (long long)m->Kq);
     }
     RML_HIP(hipSetDevice(ctx->device));
-    if (N == 0) return RML_OK;
     hipStream_t st = static_cast<hipStream_t>(stream);
     rml_ctx_guard guard(ctx, st);           // shared workspace
-    // float rows of a model that is not on the code grid: the multi-digit kernel when the batch fills enough 256 x 256 tiles
-    // (chunks sized for whole rounds of one workgroup per CU, like the exact 256 x 256 kernel's)
-    const bool dig = feat != nullptr && !m->exact && use_dig_gemm(m, path, N, ctx->num_cu);
-    const int64_t CH = feat ? ((dig || m->exact) ? pick_chunk(ctx, m, N, 8192, ctx->num_cu, dig) : std::min<int64_t>(round_up(N, kTile), 8192))
-                            : pick_chunk(ctx, m, N, 8192, ctx->num_cu);
-    const bool need_q = feat != nullptr && m->exact && (path == RML_PATH_AUTO || path == RML_PATH_I8);
-    const bool need_f32 = feat != nullptr;
-    // a model on the code grid can meet general rows as well (mixed batches): digit planes then ride along with the codes
-    const bool need_dig = feat != nullptr && (dig || (m->exact && use_dig_gemm(m, path, N, ctx->num_cu)));
-    ChunkWs probe = carve(m, CH, nullptr, need_q, need_f32, need_dig);
-    void* ws = nullptr;
-    int rc = rml_ws_reserve(ctx, probe.bytes, &ws, st);
+    const DecisionOut out{dec_ovo, dec_ovr, proba, label_vote, label_calib};
+    // float rows: the multi-digit kernel takes the rows off the code grid when the batch fills enough 256 x 256 tiles (a model on
+    // the grid can meet such rows as well -- mixed batches: digit planes then ride along with the codes); a model that is not on
+    // the grid then has chunks sized for whole rounds of one workgroup per CU, like the exact 256 x 256 kernel's.
+    // The caller's code rows are taken as they are: the workspace holds the tile predicate and the partial sums only
+    ChunkNeeds need{};
+    need.q = feat && m->exact && (path == RML_PATH_AUTO || path == RML_PATH_I8); need.f32 = feat != nullptr;
+    need.dig = feat && use_dig_gemm(m, path, N, ctx->num_cu);
+    const bool dig_rounds = need.dig && !m->exact;
+    const int64_t CH = (dig_rounds || m->exact) ? pick_chunk(ctx, m, N, 8192, dig_rounds) : std::min<int64_t>(round_up(N, kTile), 8192);
+    ChunkWs w; int rc = reserve_chunks(ctx, m, CH, need, st, &w, 1);
     if (rc) return rc;
-    ChunkWs w = carve(m, CH, static_cast<unsigned char*>(ws), need_q, need_f32, need_dig);
-    DecisionOut out{dec_ovo, dec_ovr, proba, label_vote, label_calib};
-    const int policy = path;
-    for (int64_t r0 = 0; r0 < N; r0 += CH) {
-        const int64_t n = std::min(CH, N - r0);
-        if (feat) {
-            hipLaunchKernelGGL(k_prepare_rows, dim3((unsigned)n), dim3(256), 0, st, feat + r0 * ld_feat, ld_feat, m->D,
-                               (float)m->code_scale, w.f32, m->Df, w.nsq, need_q ? w.q : nullptr, m->Dq, w.isum, w.isq, w.flags);
-            if (need_dig)
-                hipLaunchKernelGGL(k_digit_rows, dim3((unsigned)n), dim3(256), 0, st, w.f32, m->Df, m->D, m->Dq, w.dig_plane, w.dig, w.dnsq,
-                                   w.dflags, m->dig_c0, 2147483648.0 / m->dig_s, (const int32_t*)nullptr);
-            RML_HIP(hipGetLastError());
-            rc = run_chunk(ctx, m, policy, n, need_q ? w.q : nullptr, m->Dq, w.isum, w.isq, w.flags, w.f32, w.nsq, w, out.at(r0, m->C, m->P), st,
-                           false, nullptr, 0, false, true, need_dig);
-        } else {
-            rc = run_chunk(ctx, m, RML_PATH_I8, n, feat_q + r0 * ld_q, ld_q, row_isum + r0, row_isq + r0, row_flags ? row_flags + r0 : nullptr,
-                           nullptr, nullptr, w, out.at(r0, m->C, m->P), st);
-        }
-        if (rc) return rc;
+    ChunkPlan plan{};
+    plan.policy = feat ? path : RML_PATH_I8; plan.allow_big = true; plan.dig_ready = need.dig;
+    if (feat) return run_float_rows(ctx, m, feat, ld_feat, N, CH, w, plan, out, st);
+    for (int64_t r0 = 0; r0 < N && !rc; r0 += CH) {
+        const ChunkOps x{std::min(CH, N - r0), feat_q + r0 * ld_q, ld_q, row_isum + r0, row_isq + r0, row_flags ? row_flags + r0 : nullptr,
+                         nullptr, nullptr};
+        rc = run_chunk(ctx, m, x, plan, w, out.at(r0, m->C, m->P), st);
     }
-    return RML_OK;
+    return rc;
 }
 
 // ---- kernel matrix K(X, SV): the Gram-matrix service for SVC training with kernel='precomputed' -------------
@@ -2013,39 +2051,250 @@ extern "C" int rml_svm_kernel_matrix(rml_ctx* ctx, const rml_svm* m, int path, c
     hipStream_t st = static_cast<hipStream_t>(stream);
     rml_ctx_guard guard(ctx, st);           // shared workspace
     const int64_t CH = std::min<int64_t>(round_up(N, kTile), 8192);
-    const bool need_q = m->exact && (path == RML_PATH_AUTO || path == RML_PATH_I8);
-    ChunkWs probe = carve(m, CH, nullptr, need_q, true);
-    void* ws = nullptr;
-    int rc = rml_ws_reserve(ctx, probe.bytes, &ws, st);
-    if (rc) return rc;
-    ChunkWs w = carve(m, CH, static_cast<unsigned char*>(ws), need_q, true);
-    DecisionOut none{nullptr, nullptr, nullptr, nullptr, nullptr};
-    for (int64_t r0 = 0; r0 < N; r0 += CH) {
-        const int64_t n = std::min(CH, N - r0);
-        hipLaunchKernelGGL(k_prepare_rows, dim3((unsigned)n), dim3(256), 0, st, feat + r0 * ld_feat, ld_feat, m->D,
-                           (float)m->code_scale, w.f32, m->Df, w.nsq, need_q ? w.q : nullptr, m->Dq, w.isum, w.isq, w.flags);
-        RML_HIP(hipGetLastError());
-        rc = run_chunk(ctx, m, path, n, need_q ? w.q : nullptr, m->Dq, w.isum, w.isq, w.flags, w.f32, w.nsq, w, none, st,
-                       /*tiles_done=*/false, kmat + r0 * ld_k, ld_k);
-        if (rc) return rc;
-    }
-    return RML_OK;
+    ChunkNeeds need{};
+    need.q = m->exact && (path == RML_PATH_AUTO || path == RML_PATH_I8); need.f32 = true;
+    ChunkWs w; ChunkPlan plan{};
+    if (int rc = reserve_chunks(ctx, m, CH, need, st, &w, 1)) return rc;
+    plan.policy = path; plan.kmat = kmat; plan.ld_k = ld_k;
+    return run_float_rows(ctx, m, feat, ld_feat, N, CH, w, plan, DecisionOut{}, st);
 }
 
 // ---- fused front door: volumes -> projection -> SVM ---------------------------------------
 namespace {
-int project_svm_impl(rml_ctx* ctx, const rml_svm* m, const void* V, int vdtype, int64_t B, int X, int Y, int Z,
-                     int mode, const int32_t* ijk, bool derive, int32_t* ijk_out, float scale_div, uint32_t mask,
-                     double* dec_ovo, double* dec_ovr, double* proba,
-                     int32_t* label_vote, int32_t* label_calib, void* stream);
+// one validated call of the front door (front_chunked fills the last group: what is fixed for its chunks)
+struct FrontCall {
+    rml_ctx* ctx; const rml_svm* m; hipStream_t caller;
+    const void* V; int vdtype; int64_t B; int X, Y, Z; int mode; const int32_t* ijk; bool derive; int32_t* ijk_out;
+    float scale_div; uint32_t mask; DecisionOut out;
+    bool grid_ok;           // the code grid of the features is the model's: codes are the unscaled values
+    int share_cu, q_rmw;    // ProjOut's: a GEMM runs beside the projections; read-compare-write of the code rows
+    bool use_dig; ChunkPlan plan;   // rows off the code grid go to the multi-digit int8 kernel; the plan of every chunk
+    bool u8() const { return vdtype == RML_VOL_U8; }
+    int64_t frame_bytes() const { return (int64_t)X * Y * Z * (u8() ? 1 : 4); }
+    int64_t plane_len(int pl) const { return pl == 0 ? (int64_t)X * Z : (pl == 1 ? (int64_t)Y * Z : (int64_t)X * Y); }
+};
+
+// projection pass 1 of a chunk: code rows + row statistics (uint8 volumes are on the code grid by construction: no row flags)
+ProjOut code_rows_out(const FrontCall& f, const ChunkWs& w) {
+    ProjOut o{}; int64_t off = 0;
+    for (int pl = 0; pl < 3; ++pl)
+        if (f.mask & (1u << pl)) { o.q[pl] = w.q + off; off += f.plane_len(pl); }
+    o.sel = f.mask & RML_MASK_ALL;
+    o.qstride = f.m->Dq; o.qrow = w.q; o.qD = f.m->D;
+    o.row_isum = w.isum; o.row_isq = w.isq; o.row_flags = f.u8() ? nullptr : w.flags; o.scale_div = f.scale_div;
+    o.share_cu = f.share_cu; o.q_rmw = f.q_rmw;
+    return o;
 }
+// projection pass 2: float rows + norms, for the rows that left the code grid (or for a model that is not on it)
+ProjOut float_rows_out(const FrontCall& f, const ChunkWs& w) {
+    ProjOut o{}; int64_t off = 0;
+    for (int pl = 0; pl < 3; ++pl)
+        if (f.mask & (1u << pl)) { o.p[pl] = w.f32 + off; o.stride[pl] = f.m->Df; off += f.plane_len(pl); }
+    o.sel = f.mask & RML_MASK_ALL;
+    o.scale_div = f.scale_div; o.prow = w.f32; o.pD = f.m->D; o.pstride = f.m->Df; o.row_nsq = w.nsq;
+    o.share_cu = f.share_cu;
+    return o;
+}
+
+// Single observations -- how the reference calls the surface (predict.py:98-119: one target per call) -- and other batches of
+// at most one sample tile (128 frames) on a code-grid model: everything on the caller's stream (no second stream, no events), the
+// frame split over the chip (rml_launch_project_split) and the matrix-vector SVM kernels (plan_chunk picks them by the row
+// count): 64x64x128 float32 314 -> ~100 us per call on the host clock, GPU work 275 -> ~60 us.
+// (slices at given voxels -- the SDK target of predict.py:98-107 -- are one wave per row as they are: k_slice_rows)
+int front_single_tile(const FrontCall& f) {
+    rml_ctx* ctx = f.ctx; const rml_svm* m = f.m; hipStream_t st = f.caller;
+    // (the frames are split while their pieces are fewer than ~4 per CU; byte volumes: k_project_u8_max takes 24 us as it is)
+    const int S = (f.vdtype == RML_VOL_F32 && f.mode == RML_MODE_MAX && f.B <= 64) ? rml_project_split_pieces(f.X, f.Y, f.Z) : 0;
+    const size_t sbytes = S ? ((rml_project_split_scratch_bytes(f.B, f.X, f.Y, f.Z, S) + 255) & ~(size_t)255) : 0;
+    ChunkNeeds need{};
+    need.q = true; need.f32 = !f.u8();
+    ChunkWs w; void* scratch = nullptr;
+    int rc = reserve_chunks(ctx, m, kTile, need, st, &w, 1, sbytes, &scratch);
+    if (rc) return rc;
+    const ProjOut o = code_rows_out(f, w);
+    rc = S ? rml_launch_project_split(ctx, f.V, f.vdtype, f.B, f.X, f.Y, f.Z, o, static_cast<float*>(scratch), S, st)
+           : rml_launch_project(ctx, f.V, f.vdtype, f.B, f.X, f.Y, f.Z, f.mode, f.ijk, o, st);
+    if (rc) return rc;
+    const ChunkOps x = ws_rows(m, w, f.B);
+    ChunkPlan plan{};           // allow_big stays off: one sample tile
+    plan.policy = f.u8() ? RML_PATH_I8 : RML_PATH_AUTO; plan.tiles_done = true; plan.all_exact_known = f.u8();
+    if (f.u8()) return run_chunk(ctx, m, x, plan, w, f.out, st);
+    launch_tile_flags(m, x, plan_chunk(ctx, m, plan, x, w), w, w.all_exact, st);
+    // float rows + norms for frames that left the code grid (float64 path): a no-op when every frame is on it
+    ProjOut of = float_rows_out(f, w);
+    of.skip_if_set = w.all_exact;
+    rc = rml_launch_project(ctx, f.V, f.vdtype, f.B, f.X, f.Y, f.Z, f.mode, f.ijk, of, st);
+    return rc ? rc : run_chunk(ctx, m, x, plan, w, f.out, st);
+}
+
+// ---- the chunked pipelines: projection(c + 1) on the caller's stream beside GEMM(c) on ctx->aux_stream, two workspaces in rotation
+struct FrontChunk {         // rows [r0, r0 + n) in w; "the rows are in w"; the frames, the given targets, where derived (i,j,k) go
+    int64_t r0, n; const ChunkWs& w; hipEvent_t ev_proj; const void* V; const int32_t* ijk; int32_t* ijkd;
+};
+
+// the caller's stream: a chunk's projection pass between the marks of the in-situ timing (and the digit planes of its float rows:
+// run_chunk decides the general tiles from their flags), then the GEMM stream takes the chunk over
+int caller_stage(const FrontCall& f, const FrontChunk& ck, const ProjOut& po) {
+    rml_prof_mark(f.ctx, f.caller);
+    const int rc = f.derive ? rml_launch_derive_slice(f.ctx, ck.V, f.vdtype, ck.n, f.X, f.Y, f.Z, 1, ck.ijkd, nullptr, po, f.caller)
+                            : rml_launch_project(f.ctx, ck.V, f.vdtype, ck.n, f.X, f.Y, f.Z, f.mode, ck.ijk, po, f.caller);
+    rml_prof_mark(f.ctx, f.caller);
+    if (f.ctx->profiling) f.ctx->prof_frames += ck.n;
+    if (rc) return rc;
+    if (f.use_dig) { launch_digit_rows(f.m, ck.w, ck.n, f.caller); RML_HIP(hipGetLastError()); }
+    RML_HIP(hipEventRecord(ck.ev_proj, f.caller));
+    RML_HIP(hipStreamWaitEvent(f.ctx->aux_stream, ck.ev_proj, 0));
+    return RML_OK;
+}
+int gemm_stage(const FrontCall& f, const FrontChunk& ck) {
+    hipStream_t aux = f.ctx->aux_stream;
+    rml_prof_mark_gemm(f.ctx, aux);
+    const int rc = run_chunk(f.ctx, f.m, ws_rows(f.m, ck.w, ck.n), f.plan, ck.w, f.out.at(ck.r0, f.m->C, f.m->P), aux);
+    rml_prof_mark_gemm(f.ctx, aux);
+    if (f.ctx->profiling) f.ctx->prof_ops_g += 2.0 * (double)ck.n * (double)f.m->M * (double)f.m->D;
+    return rc;
+}
+
+// uint8 volumes are on the code grid by construction: one projection pass (codes + statistics), the exact GEMM on
+// every tile, no flag kernels, no predicated second pass and no predicated float64 GEMM launch
+int chunk_u8(const FrontCall& f, const FrontChunk& ck) {
+    const int rc = caller_stage(f, ck, code_rows_out(f, ck.w));
+    return rc ? rc : gemm_stage(f, ck);
+}
+
+// float32 volumes, model on the code grid: two passes.
+// The caller's stream carries NOTHING but the first projection pass of every chunk (codes + statistics: the exact path needs
+// nothing else): the tile decision and the predicated second pass (float rows for tiles that left the grid: a no-op otherwise)
+// follow on the second stream, in front of the chunk's GEMMs.  (Round 2 had them between the projection launches: three launches
+// and their gaps per chunk on the stream the step waits for.)
+// (Round 5, session r5j: the exact GEMM deciding its tiles from the row flags itself and starting the moment the projection is
+// done, with the tile decision and the predicated general path -- second pass, float64 GEMM -- on a third stream beside it and
+// the finish waiting for both: the chain WAS shorter, and the step slower -- 64x64x128 0.716-0.733 end to end against
+// 0.752-0.759 on boxes of the same class, Walabot 0.593-0.598 against 0.633; k_project_lin in situ 0.66-0.68 against 0.745.
+// A GEMM that starts WITH the next projection puts its workgroups on the CUs first, two per CU where the projection's
+// persistent workgroup should go, and the projection pays for the imbalance.  The ~30 us of small kernels in front of the GEMM
+// are what lets the projection settle first.)
+int chunk_on_grid(const FrontCall& f, const FrontChunk& ck) {
+    int rc = caller_stage(f, ck, code_rows_out(f, ck.w));
+    if (rc) return rc;
+    const ChunkOps x = ws_rows(f.m, ck.w, ck.n); hipStream_t aux = f.ctx->aux_stream;
+    launch_tile_flags(f.m, x, plan_chunk(f.ctx, f.m, f.plan, x, ck.w), ck.w, ck.w.all_exact, aux);      // at the group run_chunk's GEMMs read
+    ProjOut of = float_rows_out(f, ck.w);
+    of.no_pad = 1; of.skip_if_set = ck.w.all_exact;
+    // (fused derive -> slice: the first pass derived (i,j,k) per frame and sliced there in one launch; this one is a plain slice at
+    // the indices the first one wrote)
+    rc = rml_launch_project(f.ctx, ck.V, f.vdtype, ck.n, f.X, f.Y, f.Z, f.derive ? RML_MODE_SLICE : f.mode, f.derive ? ck.ijkd : ck.ijk, of, aux);
+    return rc ? rc : gemm_stage(f, ck);
+}
+
+// a model that is not on the code grid has no code rows: ONE pass (float rows, norms, flags; it derives as well) and the digit
+// planes on the caller's stream, the float64 or the multi-digit GEMM on the second
+int chunk_off_grid(const FrontCall& f, const FrontChunk& ck) {
+    ProjOut of = float_rows_out(f, ck.w);
+    of.row_flags = ck.w.flags;
+    const int rc = caller_stage(f, ck, of);
+    return rc ? rc : gemm_stage(f, ck);
+}
+
+int front_chunked(FrontCall f) {
+    rml_ctx* ctx = f.ctx; const rml_svm* m = f.m;
+    // Persistent wave-per-frame projection (Walabot-like grids): one projection workgroup per CU plus 128x128 GEMM workgroups
+    // beside it overlap for real (GEMM hidden under the projection: 26.7 vs 28.0 ms per 262 144 frames), which the
+    // 256x256 GEMM (205 VGPRs x 8 waves) cannot do -- it does not fit on a CU next to anything.
+    // derive -> slice: the persistent k_derive_slice takes the same pairing (one 8-wave workgroup per CU beside 128x128 GEMM
+    // workgroups; the ring GEMM in whole-round chunks, the two kernels taking turns, measured 1-2 % slower: DESIGN.md 3.3)
+    // Byte volumes (k_project_u8_max): the GEMM is a third of the step there, and since the projection's cross-lane steps left the
+    // LDS pipe (round 3: 0.59 -> 0.71 of 8 TB/s alone) each kernel is worth more alone than beside the other: the 256x256 ring
+    // kernel in whole-round chunks, the projection between its rounds (64x64x128 uint8, same box: 6.5-6.9 -> 7.4-7.5 M frames/s;
+    // Walabot grid 17.9-18.0 -> 18.4).
+    // (A CU partition -- the GEMM on g CUs of every XCD, the projection on the other 32 - g, six splits -- was measured in rounds
+    // 2-3 and never won: DESIGN.md 3.3; the knob and its masked streams are gone since round 5.)
+    const bool wave_proj = f.derive || rml_project_uses_wave_kernel(ctx, f.vdtype, f.mode, f.X, f.Y, f.Z, /*share_cu=*/true, std::min<int64_t>(f.B, 8192));
+    // rows off the code grid: the multi-digit int8 kernel (256 x 256 tiles: chunks sized for whole rounds) where the model has a
+    // digit frame and the batch is large enough, the float64 MFMA kernel otherwise
+    // Only for models off the code grid: with a grid model the rows off the grid are the exception, and the digit kernel's
+    // predicated launch -- a whole CU's LDS per workgroup even when it exits at once -- cannot start beside the resident projection
+    // and GEMM workgroups: on the GEMM stream it waited for the end of the running projection launch, chunk after chunk
+    // (profiles/r03_stats_walabot_f32.txt of session r3o: 224 launches of k_svm_gemm_ring<3,1>, up to 325 us each)
+    f.use_dig = !f.grid_ok && !f.u8() && use_dig_gemm(m, RML_PATH_AUTO, f.B, ctx->num_cu);
+    f.share_cu = 1;         // a GEMM runs beside every projection
+    f.q_rmw = ctx->opt.code_rmw >= 0 ? ctx->opt.code_rmw : rml_code_rmw(m->D, f.frame_bytes(), f.derive, f.u8());
+    const bool u8_exact = f.grid_ok && f.u8();
+    f.plan.policy = u8_exact ? RML_PATH_I8 : (f.grid_ok ? RML_PATH_AUTO : RML_PATH_F64);
+    f.plan.tiles_done = f.grid_ok;              // chunk_on_grid decides the tiles itself; chunk_u8 has none to decide
+    f.plan.all_exact_known = u8_exact; f.plan.allow_big = !wave_proj; f.plan.dig_ready = f.use_dig;
+    // 8192 frames per chunk; 16384 for small byte frames (same-box A/B: 22x31x176 float32 10.3 vs 9.6 M frames/s at 8192 vs 16384,
+    // uint8 17.4 vs 17.7)
+    // derive -> slice beside the 128x128 GEMM, frames of at most 1 MiB: 12 288 (six interleaved runs, session r4bk, Walabot grid:
+    // 8.05 M frames/s at 8192, 8.21 at 12 288, 8.21 at 16 384; 64x64x128: 2.28 / 2.24 / 2.20 -- stays at 8192)
+    const int64_t small_chunk = (f.u8() && (int64_t)f.X * f.Y * f.Z <= 200000) ? 16384
+                                : (f.derive && !f.u8() && f.frame_bytes() <= (1 << 20)) ? 12288 : 8192;
+    // (the 256 x 256 kernels -- ring GEMM, multi-digit GEMM -- get chunks of whole rounds; RML_OPT_CHUNK overrides)
+    const int64_t CH = (f.grid_ok && !wave_proj) ? pick_chunk(ctx, m, f.B, small_chunk, /*dig=*/false)
+                       : f.use_dig               ? pick_chunk(ctx, m, f.B, 8192, f.use_dig)
+                                                 : std::min<int64_t>(round_up(f.B, kTile), f.grid_ok ? pick_chunk_opt(ctx, small_chunk) : 8192);
+    ChunkNeeds need{};
+    need.q = f.grid_ok; need.f32 = true; need.dig = f.use_dig; need.ijk = f.derive && !f.ijk_out;     // the derived (i,j,k) stay in the chunk's workspace when the caller does not want them
+    // workspaces in rotation: 2 (projection of chunk c+1 beside the GEMM of chunk c; a third one -- the projection two chunks
+    // ahead -- changed nothing at 64x64x128 and cost 2 % at the Walabot grid: DESIGN.md 3.3)
+    // (Three streams -- the small kernels either side of a chunk's GEMM on a third one, RML_PIPE_SPLIT in rounds 3-4 -- were
+    // bimodal at the Walabot grid and -5 % at 64x64x128: DESIGN.md 3.3; removed in round 5.)
+    constexpr int NBUF = 2;
+    ChunkWs w2[NBUF];
+    int rc = reserve_chunks(ctx, m, CH, need, f.caller, w2, NBUF);
+    if (rc) return rc;
+    // aux must start after everything already queued by the caller
+    RML_HIP(hipEventRecord(ctx->ev_fork, f.caller));
+    RML_HIP(hipStreamWaitEvent(ctx->aux_stream, ctx->ev_fork, 0));
+    // (Round 5, session r5i: tapering the last chunk -- 8 192 -> 4 096, 2 048, 2 048, so that the GEMM left exposed behind the last
+    // projection is a quarter of a chunk's -- LOST: end to end / in-situ kernel 0.953 against 0.957-0.958 at 64x64x128 and
+    // 0.607 against 0.633 of 8 TB/s at the Walabot grid; a persistent launch over 2 048 frames is two frames per wave.)
+    int64_t c = 0;
+    for (int64_t r0 = 0; r0 < f.B; r0 += CH, ++c) {
+        const int b = (int)(c % NBUF);
+        if (c >= NBUF) RML_HIP(hipStreamWaitEvent(f.caller, ctx->ev_done[b], 0));    // workspace reuse
+        const FrontChunk ck{r0, std::min(CH, f.B - r0), w2[b], ctx->ev_proj[b], static_cast<const unsigned char*>(f.V) + r0 * f.frame_bytes(),
+                            f.ijk ? f.ijk + r0 * 3 : nullptr, f.derive ? (f.ijk_out ? f.ijk_out + r0 * 3 : w2[b].ijk) : nullptr};
+        rc = !f.grid_ok ? chunk_off_grid(f, ck) : (f.u8() ? chunk_u8(f, ck) : chunk_on_grid(f, ck));
+        if (rc) return rc;
+        RML_HIP(hipEventRecord(ctx->ev_done[b], ctx->aux_stream));
+    }
+    RML_HIP(hipEventRecord(ctx->ev_join, ctx->aux_stream));
+    // join: the caller's stream continues after the last GEMMs and their finish
+    RML_HIP(hipStreamWaitEvent(f.caller, ctx->ev_join, 0));
+    return RML_OK;
+}
+
+// the validating front of rml_project_svm / rml_derive_project_svm
+int project_svm_front(rml_ctx* ctx, const rml_svm* m, const void* V, int vdtype, int64_t B, int X, int Y, int Z,
+                      int mode, const int32_t* ijk, bool derive, int32_t* ijk_out, float scale_div, uint32_t mask,
+                      const DecisionOut& out, void* stream) {
+    RML_REQUIRE(ctx && m && B >= 0, RML_ERR_INVALID, "rml_project_svm: bad arguments");
+    if (B == 0) return RML_OK;
+    RML_REQUIRE(V != nullptr, RML_ERR_INVALID, "rml_project_svm: V is NULL");
+    RML_REQUIRE(vdtype == RML_VOL_F32 || vdtype == RML_VOL_U8, RML_ERR_INVALID, "rml_project_svm: unknown volume dtype %d", vdtype);
+    RML_REQUIRE(rml_feature_len(X, Y, Z, mask) == m->D, RML_ERR_INVALID, "rml_project_svm: grid/mask give D=%lld, model has D=%lld",
+                (long long)rml_feature_len(X, Y, Z, mask), (long long)m->D);
+    RML_REQUIRE(!(out.proba || out.label_calib) || m->has_calib, RML_ERR_STATE, "rml_project_svm: model has no calibrators");
+    RML_REQUIRE(mode != RML_MODE_SLICE || ijk || derive, RML_ERR_INVALID, "rml_project_svm: mode SLICE needs ijk");
+    if (mode == RML_MODE_MAX_NAN) mode = RML_MODE_MAX;         // round 6: mode MAX itself has NumPy's NaN policy
+    const bool scaled = scale_div > 1.0f;
+    const bool grid_ok = m->exact && ((scaled && (double)scale_div == m->code_scale) || (!scaled && m->code_scale == 1.0));
+    RML_HIP(hipSetDevice(ctx->device));
+    hipStream_t caller = static_cast<hipStream_t>(stream);
+    rml_ctx_guard guard(ctx, caller);       // shared workspaces, aux stream and chunk events (the caller's stream joins at the end)
+    const FrontCall f{ctx, m, caller, V, vdtype, B, X, Y, Z, mode, ijk, derive, ijk_out, scale_div, mask, out, grid_ok};
+    if (B <= kTile && grid_ok && !derive && (mode == RML_MODE_MAX || (mode == RML_MODE_SLICE && ijk))) return front_single_tile(f);
+    return front_chunked(f);
+}
+}  // namespace
 
 extern "C" int rml_project_svm(rml_ctx* ctx, const rml_svm* m, const void* V, int vdtype, int64_t B, int X, int Y, int Z,
                                int mode, const int32_t* ijk, float scale_div, uint32_t mask,
                                double* dec_ovo, double* dec_ovr, double* proba,
                                int32_t* label_vote, int32_t* label_calib, void* stream) {
-    return project_svm_impl(ctx, m, V, vdtype, B, X, Y, Z, mode, ijk, false, nullptr, scale_div, mask, dec_ovo, dec_ovr, proba, label_vote,
-                            label_calib, stream);
+    return project_svm_front(ctx, m, V, vdtype, B, X, Y, Z, mode, ijk, /*derive=*/false, nullptr, scale_div, mask,
+                             DecisionOut{dec_ovo, dec_ovr, proba, label_vote, label_calib}, stream);
 }
 
 extern "C" int rml_derive_project_svm(rml_ctx* ctx, const rml_svm* m, const void* V, int vdtype, int64_t B, int X, int Y, int Z,
@@ -2055,260 +2304,9 @@ extern "C" int rml_derive_project_svm(rml_ctx* ctx, const rml_svm* m, const void
     RML_REQUIRE(rml_derive_slice_supported(ctx, V, vdtype, X, Y, Z, 1) == 1, RML_ERR_UNSUPPORTED,
                 "rml_derive_project_svm: no fused derive kernel for %dx%dx%d (rows of whole quads, Z <= 256, odd part of Z/4 <= 15): "
                 "use rml_derive_targets + rml_project_svm(mode SLICE)", X, Y, Z);
-    return project_svm_impl(ctx, m, V, vdtype, B, X, Y, Z, RML_MODE_SLICE, nullptr, true, ijk_out, scale_div, mask, dec_ovo, dec_ovr, proba,
-                            label_vote, label_calib, stream);
+    return project_svm_front(ctx, m, V, vdtype, B, X, Y, Z, RML_MODE_SLICE, nullptr, /*derive=*/true, ijk_out, scale_div, mask,
+                             DecisionOut{dec_ovo, dec_ovr, proba, label_vote, label_calib}, stream);
 }
-
-namespace {
-int project_svm_impl(rml_ctx* ctx, const rml_svm* m, const void* V, int vdtype, int64_t B, int X, int Y, int Z,
-                     int mode, const int32_t* ijk, bool derive, int32_t* ijk_out, float scale_div, uint32_t mask,
-                     double* dec_ovo, double* dec_ovr, double* proba,
-                     int32_t* label_vote, int32_t* label_calib, void* stream) {
-    RML_REQUIRE(ctx && m && B >= 0, RML_ERR_INVALID, "rml_project_svm: bad arguments");
-    if (B == 0) return RML_OK;
-    RML_REQUIRE(V != nullptr, RML_ERR_INVALID, "rml_project_svm: V is NULL");
-    RML_REQUIRE(vdtype == RML_VOL_F32 || vdtype == RML_VOL_U8, RML_ERR_INVALID, "rml_project_svm: unknown volume dtype %d", vdtype);
-    RML_REQUIRE(rml_feature_len(X, Y, Z, mask) == m->D, RML_ERR_INVALID, "rml_project_svm: grid/mask give D=%lld, model has D=%lld",
-                (long long)rml_feature_len(X, Y, Z, mask), (long long)m->D);
-    RML_REQUIRE(!(proba || label_calib) || m->has_calib, RML_ERR_STATE, "rml_project_svm: model has no calibrators");
-    RML_REQUIRE(mode != RML_MODE_SLICE || ijk || derive, RML_ERR_INVALID, "rml_project_svm: mode SLICE needs ijk");
-    if (mode == RML_MODE_MAX_NAN) mode = RML_MODE_MAX;         // round 6: mode MAX itself has NumPy's NaN policy
-    // the code grid of the features must be the model's: codes are the unscaled values
-    const bool scaled = scale_div > 1.0f;
-    const bool grid_ok = m->exact && ((scaled && (double)scale_div == m->code_scale) || (!scaled && m->code_scale == 1.0));
-    RML_HIP(hipSetDevice(ctx->device));
-    if (B == 0) return RML_OK;
-    hipStream_t caller = static_cast<hipStream_t>(stream);
-    rml_ctx_guard guard(ctx, caller);       // shared workspaces, aux stream and chunk events (the caller's stream joins at the end)
-    hipStream_t st = caller;                // the projections' stream
-    // Single observations -- how the reference calls the surface (predict.py:98-119: one target per call) -- and other batches of
-    // at most one sample tile (128 frames) on a code-grid model: everything on the caller's stream (no second stream, no events), the
-    // frame split over the chip (rml_launch_project_split) and the matrix-vector SVM kernels (run_chunk picks them by the row
-    // count): 64x64x128 float32 314 -> ~100 us per call on the host clock, GPU work 275 -> ~60 us.
-    if (B <= kTile && grid_ok && !derive && (mode == RML_MODE_MAX || (mode == RML_MODE_SLICE && ijk))) {
-        // (slices at given voxels -- the SDK target of predict.py:98-107 -- are one wave per row as they are: k_slice_rows)
-        // (up to one sample tile of frames on this path; the frames are split while their pieces are fewer than ~4 per CU)
-        const int S = (vdtype == RML_VOL_F32 && mode == RML_MODE_MAX && B <= 64) ? rml_project_split_pieces(X, Y, Z) : 0;      // byte volumes: k_project_u8_max takes 24 us as it is
-        const int64_t CHs = kTile;
-        ChunkWs probe = carve(m, CHs, nullptr, true, vdtype != RML_VOL_U8, false, false);
-        const size_t sbytes = S ? ((rml_project_split_scratch_bytes(B, X, Y, Z, S) + 255) & ~(size_t)255) : 0;
-        void* ws = nullptr;
-        int rc = rml_ws_reserve(ctx, probe.bytes + sbytes, &ws, st);
-        if (rc) return rc;
-        const ChunkWs w = carve(m, CHs, static_cast<unsigned char*>(ws), true, vdtype != RML_VOL_U8, false, false);
-        float* scratch = reinterpret_cast<float*>(static_cast<unsigned char*>(ws) + probe.bytes);
-        const bool u8_exact = vdtype == RML_VOL_U8;
-        ProjOut o{};
-        int64_t off = 0;
-        for (int pl = 0; pl < 3; ++pl)
-            if (mask & (1u << pl)) {
-                o.q[pl] = w.q + off;
-                off += pl == 0 ? (int64_t)X * Z : (pl == 1 ? (int64_t)Y * Z : (int64_t)X * Y);
-            }
-        o.sel = mask & RML_MASK_ALL;
-        o.qstride = m->Dq; o.qrow = w.q; o.qD = m->D;
-        o.row_isum = w.isum; o.row_isq = w.isq; o.row_flags = u8_exact ? nullptr : w.flags; o.scale_div = scale_div;
-        rc = S ? rml_launch_project_split(ctx, V, vdtype, B, X, Y, Z, o, scratch, S, st) : rml_launch_project(ctx, V, vdtype, B, X, Y, Z, mode, ijk, o, st);
-        if (rc) return rc;
-        DecisionOut out{dec_ovo, dec_ovr, proba, label_vote, label_calib};
-        if (u8_exact)
-            return run_chunk(ctx, m, RML_PATH_I8, B, w.q, m->Dq, w.isum, w.isq, nullptr, nullptr, nullptr, w, out, st, /*tiles_done=*/true, nullptr, 0,
-                             /*all_exact_known=*/true, /*allow_big=*/false);
-        hipLaunchKernelGGL(k_tile_flags, dim3(2), dim3(128), 0, st, w.flags, B, 1, 0, 1, w.tile_exact, w.all_exact, 1);
-        // float rows + norms for frames that left the code grid (float64 path): a no-op when every frame is on it
-        ProjOut of{};
-        off = 0;
-        for (int pl = 0; pl < 3; ++pl)
-            if (mask & (1u << pl)) {
-                of.p[pl] = w.f32 + off; of.stride[pl] = m->Df;
-                off += pl == 0 ? (int64_t)X * Z : (pl == 1 ? (int64_t)Y * Z : (int64_t)X * Y);
-            }
-        of.sel = mask & RML_MASK_ALL;
-        of.scale_div = scale_div; of.prow = w.f32; of.pD = m->D; of.pstride = m->Df; of.row_nsq = w.nsq;
-        of.skip_if_set = w.all_exact;
-        rc = rml_launch_project(ctx, V, vdtype, B, X, Y, Z, mode, ijk, of, st);
-        if (rc) return rc;
-        return run_chunk(ctx, m, RML_PATH_AUTO, B, w.q, m->Dq, w.isum, w.isq, w.flags, w.f32, w.nsq, w, out, st, /*tiles_done=*/true, nullptr, 0, false,
-                         /*allow_big=*/false);
-    }
-    // chunk so that GEMM(c) overlaps projection(c+1): two workspaces, aux stream for the GEMMs
-    // frames per chunk: see small_chunk below; RML_CHUNK overrides
-    // Persistent wave-per-frame projection (Walabot-like grids): one projection workgroup per CU plus 128x128 GEMM workgroups
-    // beside it overlap for real (GEMM hidden under the projection: 26.7 vs 28.0 ms per 262 144 frames), which the
-    // 256x256 GEMM (205 VGPRs x 8 waves) cannot do -- it does not fit on a CU next to anything.
-    // derive -> slice: the persistent k_derive_slice takes the same pairing (one 8-wave workgroup per CU beside 128x128 GEMM
-    // workgroups; the ring GEMM in whole-round chunks, the two kernels taking turns, measured 1-2 % slower: DESIGN.md 3.3)
-    const bool wave_proj = derive ? true
-                                  : rml_project_uses_wave_kernel(ctx, vdtype, mode, X, Y, Z, /*share_cu=*/true, std::min<int64_t>(B, 8192));
-    // Byte volumes (k_project_u8_max): the GEMM is a third of the step there, and since the projection's cross-lane steps left the
-    // LDS pipe (round 3: 0.59 -> 0.71 of 8 TB/s alone) each kernel is worth more alone than beside the other: the 256x256 ring
-    // kernel in whole-round chunks, the projection between its rounds (64x64x128 uint8, same box: 6.5-6.9 -> 7.4-7.5 M frames/s;
-    // Walabot grid 17.9-18.0 -> 18.4).
-    // (A CU partition -- the GEMM on g CUs of every XCD, the projection on the other 32 - g, six splits -- was measured in rounds
-    // 2-3 and never won: DESIGN.md 3.3; the knob and its masked streams are gone since round 5.)
-    const int gemm_cus = ctx->num_cu;
-    const bool small_gemm = wave_proj;
-    // 8192 frames per chunk; 16384 for small byte frames (same-box A/B: 22x31x176 float32 10.3 vs 9.6 M frames/s at 8192 vs 16384,
-    // uint8 17.4 vs 17.7)
-    // derive -> slice beside the 128x128 GEMM, frames of at most 1 MiB: 12 288 (six interleaved runs, session r4bk, Walabot grid:
-    // 8.05 M frames/s at 8192, 8.21 at 12 288, 8.21 at 16 384; 64x64x128: 2.28 / 2.24 / 2.20 -- stays at 8192)
-    const int64_t small_chunk = (vdtype == RML_VOL_U8 && (int64_t)X * Y * Z <= 200000) ? 16384
-                                : (derive && vdtype != RML_VOL_U8 && (int64_t)X * Y * Z * 4 <= (1 << 20)) ? 12288 : 8192;
-    // rows off the code grid: the multi-digit int8 kernel (256 x 256 tiles: chunks sized for whole rounds) where the model has a
-    // digit frame and the batch is large enough, the float64 MFMA kernel otherwise
-    // Only for models off the code grid: with a grid model the rows off the grid are the exception, and the digit kernel's
-    // predicated launch -- a whole CU's LDS per workgroup even when it exits at once -- cannot start beside the resident projection
-    // and GEMM workgroups: on the GEMM stream it waited for the end of the running projection launch, chunk after chunk
-    // (profiles/r03_stats_walabot_f32.txt of session r3o: 224 launches of k_svm_gemm_ring<3,1>, up to 325 us each)
-    const bool use_dig = !grid_ok && vdtype != RML_VOL_U8 && use_dig_gemm(m, RML_PATH_AUTO, B, ctx->num_cu);
-    const int64_t CH = (grid_ok && !small_gemm) ? pick_chunk(ctx, m, B, small_chunk, gemm_cus)
-                       : (!grid_ok && use_dig)  ? pick_chunk(ctx, m, B, 8192, ctx->num_cu, true)
-                                                : std::min<int64_t>(round_up(B, kTile), grid_ok ? pick_chunk_opt(ctx, small_chunk) : 8192);
-    const bool ws_ijk = derive && !ijk_out;             // the derived (i,j,k) stay in the chunk's workspace when the caller does not want them
-    ChunkWs probe = carve(m, CH, nullptr, grid_ok, true, use_dig, ws_ijk);
-    // workspaces in rotation: 2 (projection of chunk c+1 beside the GEMM of chunk c; a third one -- the projection two chunks
-    // ahead -- changed nothing at 64x64x128 and cost 2 % at the Walabot grid: DESIGN.md 3.3)
-    constexpr int NBUF = 2;
-    void* ws = nullptr;
-    int rc = rml_ws_reserve(ctx, (size_t)NBUF * probe.bytes, &ws, st);
-    if (rc) return rc;
-    ChunkWs w2[NBUF];
-    for (int i = 0; i < NBUF; ++i) w2[i] = carve(m, CH, static_cast<unsigned char*>(ws) + (size_t)i * probe.bytes, grid_ok, true, use_dig, ws_ijk);
-    DecisionOut out{dec_ovo, dec_ovr, proba, label_vote, label_calib};
-    const int64_t frame_elems = (int64_t)X * Y * Z;
-    hipStream_t aux = ctx->aux_stream;
-    hipEvent_t* ev_proj = ctx->ev_proj;
-    hipEvent_t* ev_done = ctx->ev_done;
-    // (Three streams -- the small kernels either side of a chunk's GEMM on a third one, RML_PIPE_SPLIT in rounds 3-4 -- were
-    // bimodal at the Walabot grid and -5 % at 64x64x128: DESIGN.md 3.3; removed in round 5.)
-    // (Round 5, session r5j: the exact GEMM deciding its tiles from the row flags itself and starting the moment the projection is
-    // done, with the tile decision and the predicated general path -- second pass, float64 GEMM -- on a third stream beside it and
-    // the finish waiting for both: the chain WAS shorter, and the step slower -- 64x64x128 0.716-0.733 end to end against
-    // 0.752-0.759 on boxes of the same class, Walabot 0.593-0.598 against 0.633; k_project_lin in situ 0.66-0.68 against 0.745.
-    // A GEMM that starts WITH the next projection puts its workgroups on the CUs first, two per CU where the projection's
-    // persistent workgroup should go, and the projection pays for the imbalance.  The ~30 us of small kernels in front of the GEMM
-    // are what lets the projection settle first.)
-    hipStream_t side = aux;
-    // aux must start after everything already queued by the caller
-    RML_HIP(hipEventRecord(ctx->ev_fork, caller));
-    RML_HIP(hipStreamWaitEvent(aux, ctx->ev_fork, 0));
-    // (Round 5, session r5i: tapering the last chunk -- 8 192 -> 4 096, 2 048, 2 048, so that the GEMM left exposed behind the last
-    // projection is a quarter of a chunk's -- LOST: end to end / in-situ kernel 0.953 against 0.957-0.958 at 64x64x128 and
-    // 0.607 against 0.633 of 8 TB/s at the Walabot grid; a persistent launch over 2 048 frames is two frames per wave.)
-    int64_t c = 0;
-    for (int64_t r0 = 0; r0 < B; r0 += CH, ++c) {
-        const int64_t n = std::min(CH, B - r0);
-        const ChunkWs& w = w2[c % NBUF];
-        hipStream_t sp = st;                            // the stream of this chunk's first projection pass
-        if (c >= NBUF) RML_HIP(hipStreamWaitEvent(sp, ev_done[c % NBUF], 0));    // workspace reuse
-        const int FT = (int)((n + kTile - 1) / kTile);
-        ProjOut o{};
-        int64_t off = 0;
-        for (int pl = 0; pl < 3; ++pl)
-            if (mask & (1u << pl)) {
-                o.q[pl] = grid_ok ? w.q + off : nullptr;
-                off += pl == 0 ? (int64_t)X * Z : (pl == 1 ? (int64_t)Y * Z : (int64_t)X * Y);
-            }
-        o.sel = mask & RML_MASK_ALL;
-        o.qstride = m->Dq; o.qrow = grid_ok ? w.q : nullptr; o.qD = m->D;
-        o.row_isum = w.isum; o.row_isq = w.isq; o.row_flags = w.flags; o.scale_div = scale_div;
-        o.share_cu = 1;
-        o.q_rmw = ctx->opt.code_rmw >= 0 ? ctx->opt.code_rmw : rml_code_rmw(m->D, frame_elems * (vdtype == RML_VOL_U8 ? 1 : 4), derive, vdtype == RML_VOL_U8);
-        const void* Vc = static_cast<const unsigned char*>(V) + r0 * frame_elems * (vdtype == RML_VOL_U8 ? 1 : 4);
-        const int32_t* ijkc = ijk ? ijk + r0 * 3 : nullptr;
-        // fused derive -> slice: the first pass derives (i,j,k) per frame and slices there in one launch; a second pass (float rows
-        // for tiles that left the code grid) is a plain slice at the indices the first one wrote
-        int32_t* ijkd = derive ? (ijk_out ? ijk_out + r0 * 3 : w.ijk) : nullptr;
-        auto first_pass = [&](const ProjOut& po, hipStream_t ps) -> int {
-            if (derive) return rml_launch_derive_slice(ctx, Vc, vdtype, n, X, Y, Z, 1, ijkd, nullptr, po, ps);
-            return rml_launch_project(ctx, Vc, vdtype, n, X, Y, Z, mode, ijkc, po, ps);
-        };
-        // uint8 volumes are on the code grid by construction: one projection pass (codes + statistics), the exact GEMM on
-        // every tile, no flag kernels, no predicated second pass and no predicated float64 GEMM launch
-        const bool u8_exact = grid_ok && vdtype == RML_VOL_U8;
-        if (u8_exact) {
-            o.row_flags = nullptr;
-            rml_prof_mark(ctx, st);
-            rc = first_pass(o, st);
-            rml_prof_mark(ctx, st);
-            if (ctx->profiling) ctx->prof_frames += n;
-            if (rc) return rc;
-            RML_HIP(hipEventRecord(ev_proj[c % NBUF], st));
-            RML_HIP(hipStreamWaitEvent(aux, ev_proj[c % NBUF], 0));
-            rml_prof_mark_gemm(ctx, aux);
-            rc = run_chunk(ctx, m, RML_PATH_I8, n, w.q, m->Dq, w.isum, w.isq, nullptr, nullptr, nullptr, w, out.at(r0, m->C, m->P), aux,
-                           /*tiles_done=*/true, nullptr, 0, /*all_exact_known=*/true, /*allow_big=*/!small_gemm);
-            rml_prof_mark_gemm(ctx, aux);
-            if (ctx->profiling) ctx->prof_ops_g += 2.0 * (double)n * (double)m->M * (double)m->D;
-            if (rc) return rc;
-            RML_HIP(hipEventRecord(ev_done[c % NBUF], aux));
-            continue;
-        }
-        // With a model on the code grid the caller's stream carries NOTHING but the first projection pass of every chunk (codes
-        // + statistics): the tile decision, the predicated second pass (float rows for tiles that left the grid: a no-op
-        // otherwise) and the digit planes follow on the second stream, in front of the chunk's GEMMs.  (Round 2 had them between
-        // the projection launches: three launches and their gaps per chunk on the stream the step waits for.)
-        hipStream_t s2 = grid_ok ? side : st;           // the stream of pass 2 and its followers
-        if (grid_ok) {
-            // pass 1: codes + statistics only (the exact path needs nothing else)
-            rml_prof_mark(ctx, sp);
-            rc = first_pass(o, sp);
-            rml_prof_mark(ctx, sp);
-            if (ctx->profiling) ctx->prof_frames += n;
-            if (rc) return rc;
-            RML_HIP(hipEventRecord(ev_proj[c % NBUF], sp));
-            RML_HIP(hipStreamWaitEvent(side, ev_proj[c % NBUF], 0));
-            const int group = (use_dig || (!small_gemm && use_big_gemm(m, n, gemm_cus, ctx->opt.gemm_big))) ? 2 : 1;      // the same decision run_chunk takes for this chunk
-            hipLaunchKernelGGL(k_tile_flags, dim3((FT + group - 1) / group + 1), dim3(128 * group), 0, side, w.flags, n, FT, 0, 1, w.tile_exact,
-                               w.all_exact, group);
-        }
-        // pass 2: float rows + norms for the f32 path; a no-op when every tile is exact
-        ProjOut of{};
-        off = 0;
-        for (int pl = 0; pl < 3; ++pl)
-            if (mask & (1u << pl)) {
-                of.p[pl] = w.f32 + off; of.stride[pl] = m->Df;
-                off += pl == 0 ? (int64_t)X * Z : (pl == 1 ? (int64_t)Y * Z : (int64_t)X * Y);
-            }
-        of.sel = mask & RML_MASK_ALL;
-        of.scale_div = scale_div; of.prow = w.f32; of.pD = m->D; of.pstride = m->Df; of.row_nsq = w.nsq;
-        of.share_cu = o.share_cu;
-        of.no_pad = grid_ok ? 1 : 0;
-        of.skip_if_set = grid_ok ? w.all_exact : nullptr;
-        if (!grid_ok) of.row_flags = w.flags;
-        if (!grid_ok) rml_prof_mark(ctx, st);
-        // (a model off the code grid has no first pass: this one derives as well)
-        rc = (derive && grid_ok) ? rml_launch_project(ctx, Vc, vdtype, n, X, Y, Z, RML_MODE_SLICE, ijkd, of, s2) : first_pass(of, s2);
-        if (!grid_ok) { rml_prof_mark(ctx, st); if (ctx->profiling) ctx->prof_frames += n; }
-        if (rc) return rc;
-        if (use_dig) {
-            // digit planes of the float rows (skipped with the float rows when every tile is exact); with an exact model the
-            // general tiles are re-decided here, otherwise run_chunk decides
-            hipLaunchKernelGGL(k_digit_rows, dim3((unsigned)n), dim3(256), 0, s2, w.f32, m->Df, m->D, m->Dq, w.dig_plane, w.dig, w.dnsq,
-                               w.dflags, m->dig_c0, 2147483648.0 / m->dig_s, of.skip_if_set);
-            if (grid_ok)
-                hipLaunchKernelGGL(k_tile_dig, dim3((FT + 1) / 2), dim3(256), 0, s2, w.dflags, n, FT, w.tile_exact, of.skip_if_set);
-            RML_HIP(hipGetLastError());
-        }
-        if (!grid_ok) {
-            RML_HIP(hipEventRecord(ev_proj[c % NBUF], st));
-            RML_HIP(hipStreamWaitEvent(aux, ev_proj[c % NBUF], 0));
-        }
-        rml_prof_mark_gemm(ctx, aux);
-        rc = run_chunk(ctx, m, grid_ok ? RML_PATH_AUTO : RML_PATH_F64, n, grid_ok ? w.q : nullptr, m->Dq, w.isum, w.isq, w.flags, w.f32, w.nsq, w,
-                       out.at(r0, m->C, m->P), aux, /*tiles_done=*/grid_ok, nullptr, 0, false, /*allow_big=*/!small_gemm, /*dig_ready=*/use_dig,
-                       /*defer_finish=*/false);
-        rml_prof_mark_gemm(ctx, aux);
-        if (ctx->profiling) ctx->prof_ops_g += 2.0 * (double)n * (double)m->M * (double)m->D;
-        if (rc) return rc;
-        RML_HIP(hipEventRecord(ev_done[c % NBUF], aux));
-    }
-    RML_HIP(hipEventRecord(ctx->ev_join, aux));
-    // join: the caller's stream continues after the last GEMMs and their finish
-    RML_HIP(hipStreamWaitEvent(caller, ctx->ev_join, 0));
-    return RML_OK;
-}
-}  // namespace
 
 // libsvm's own Platt coefficients (SVC(probability=True): sk:svm/_base.py _probA / _probB, one pair per class pair):
 // uploaded once, at load time, so that rml_svm_pairwise_proba is an ordinary asynchronous launch

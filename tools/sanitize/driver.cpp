@@ -132,6 +132,52 @@ static void phase_a_model_packing() {
     }
 }
 
+// The byte size of a chunk workspace (rml_svm_ws_bytes: svm.hip's carve) for seven model geometries x two chunk sizes x the 16
+// combinations of ChunkNeeds {code rows, float rows, digit planes, derived ijk} against kWsBytes: the sizes the layout had when
+// the table was printed (`driver --print-ws-table` on a commit whose layout is trusted).  The fused front doors carve two such
+// workspaces back to back from one block, so a part that grows or moves unnoticed is an overrun, not an error.
+struct WsCase { int64_t M, D; int C; };
+static const WsCase kWsCases[] = {{5, 7, 2}, {300, 1234, 3}, {17, 130, 6}, {64, 129, 3}, {128, 128, 4}, {129, 127, 5}, {2562, 20480, 3}};
+static const int64_t kWsChunks[] = {2048, 8192};        // with and without the split-K scratch
+static const size_t kWsBytes[7][2][16] = {
+    {{66048, 1380864, 328192, 1643008, 5333504, 6648320, 5595648, 6910464, 90624, 1405440, 352768, 1667584, 5358080, 6672896, 5620224, 6935040},
+     {262912, 1315584, 1311488, 2364160, 21332736, 22385408, 22381312, 23433984, 361216, 1413888, 1409792, 2462464, 21431040, 22483712, 22479616, 23532288}},
+    {{197120, 6238720, 10420736, 16462336, 20144640, 26186240, 30368256, 36409856, 221696, 6263296, 10445312, 16486912, 20169216, 26210816, 30392832, 36434432},
+     {787200, 12333824, 41681664, 53228288, 80577280, 92123904, 121471744, 133018368, 885504, 12432128, 41779968, 53326592, 80675584, 92222208, 121570048, 133116672}},
+    {{295424, 2134528, 1606144, 3445248, 7660032, 9499136, 8970752, 10809856, 320000, 2159104, 1630720, 3469824, 7684608, 9523712, 8995328, 10834432},
+     {1180416, 4330240, 6423296, 9573120, 30638848, 33788672, 35881728, 39031552, 1278720, 4428544, 6521600, 9671424, 30737152, 33886976, 35980032, 39129856}},
+    {{98816, 1937920, 1409536, 3248640, 7463424, 9302528, 8774144, 10613248, 123392, 1962496, 1434112, 3273216, 7488000, 9327104, 8798720, 10637824},
+     {393984, 3543808, 5636864, 8786688, 29852416, 33002240, 35095296, 38245120, 492288, 3642112, 5735168, 8884992, 29950720, 33100544, 35193600, 38343424}},
+    {{147968, 1462784, 1458688, 2773504, 5415424, 6730240, 6726144, 8040960, 172544, 1487360, 1483264, 2798080, 5440000, 6754816, 6750720, 8065536},
+     {590592, 1643264, 5833472, 6886144, 21660416, 22713088, 26903296, 27955968, 688896, 1741568, 5931776, 6984448, 21758720, 22811392, 27001600, 28054272}},
+    {{377344, 2744832, 1688064, 4055552, 5644800, 8012288, 6955520, 9323008, 401920, 2769408, 1712640, 4080128, 5669376, 8036864, 6980096, 9347584},
+     {1508096, 2564864, 6750976, 7807744, 22577920, 23634688, 27820800, 28877568, 1606400, 2663168, 6849280, 7906048, 22676224, 23732992, 27919104, 28975872}},
+    {{1081856, 65393152, 169116160, 233427456, 216064512, 280375808, 384098816, 448410112, 1106432, 65417728, 169140736, 233452032, 216089088, 280400384, 384123392, 448434688},
+     {4326144, 173232896, 676463360, 845370112, 864256768, 1033163520, 1536393984, 1705300736, 4424448, 173331200, 676561664, 845468416, 864355072, 1033261824, 1536492288, 1705399040}},
+};
+
+static void phase_a_workspace_layout(bool print) {
+    for (int ci = 0; ci < 7; ++ci) {
+        const WsCase& c = kWsCases[ci];
+        std::vector<double> sv((size_t)c.M * c.D, 0.0), dc((size_t)(c.C - 1) * c.M, 0.0);
+        std::vector<int32_t> ns(c.C, 0);
+        ns[0] = (int32_t)c.M;
+        rml_svm m;
+        rml_svm_pack pk;
+        CHECK(rml_svm_pack_host(sv.data(), c.M, c.D, dc.data(), ns.data(), c.C, RML_KERNEL_RBF, 0.01, 255.0, false, &m, &pk) == RML_OK);
+        if (print) printf("    {");
+        for (int hi = 0; hi < 2; ++hi) {
+            if (print) printf("%s{", hi ? ",\n     " : "");
+            for (unsigned needs = 0; needs < 16; ++needs) {
+                const size_t b = rml_svm_ws_bytes(&m, kWsChunks[hi], needs);
+                if (print) printf("%zu%s", b, needs < 15 ? ", " : "}");
+                else CHECK(b == kWsBytes[ci][hi][needs]);
+            }
+        }
+        if (print) printf("},\n");
+    }
+}
+
 static void phase_a_thread_local_errors() {
     // rml_last_error is thread-local: four threads fail differently at the same time and each reads its own message
     std::vector<std::thread> ts;
@@ -237,9 +283,11 @@ static void phase_b(rml_ctx* ctx) {
 
 int main(int argc, char** argv) {
     const bool need_device = argc > 1 && strcmp(argv[1], "--need-device") == 0;
+    if (argc > 1 && strcmp(argv[1], "--print-ws-table") == 0) { phase_a_workspace_layout(true); return 0; }
     phase_a_arguments();
     phase_a_pillow_tables();
     phase_a_model_packing();
+    phase_a_workspace_layout(false);
     phase_a_thread_local_errors();
     printf("phase A: %s\n", g_fail ? "FAILED" : "ok");
     rml_ctx* ctx = nullptr;
