@@ -13,24 +13,19 @@
 // kernel; the recomputation is ~10 % of the K loop at D = 10 010.
 //
 // Tiles: 128 x 128 per workgroup, 4 waves as 2 x 2, each wave 4 x 4 MFMA tiles of 16 x 16; K-step = 32 floats = 128 bytes per
-// row, staged by LDS-DMA into swizzled [128 rows][128 B] images, double-buffered (the K loop of k_svm_gemm<PATH_F64>, svm.hip).
+// row, staged by LDS-DMA into swizzled [128 rows][128 B] images, double-buffered (mfma_tile.h: the K loop of k_svm_gemm<PATH_F64>).
 // Only the upper triangle of tile pairs (bi <= bj) is launched.  An off-diagonal tile writes K[i][j] and its mirror K[j][i] from
 // the same inner product; a diagonal tile writes its upper half and mirrors it -- every matrix is symmetric by construction.
 // Both stores go through one LDS image of the accumulator half so that each wave stores 512 contiguous bytes of one row.
 // The rows are first copied into a zero-padded workspace (k_gram_prep: N_pad x D_pad float32 + float64 row norms), so the
 // K loop needs no clamping and no tail.  Every reduction has a fixed order: results are deterministic run to run.
 #include "rml_internal.h"
+#include "mfma_tile.h"
 #include <math.h>
 
 namespace {
 
-typedef float v4f __attribute__((ext_vector_type(4)));
-typedef double v4d __attribute__((ext_vector_type(4)));
-
-constexpr int kTile = 128;                          // rows per tile
-constexpr int kStepBytes = 128;                     // K-step bytes per row (32 floats)
 constexpr int kStepFloats = kStepBytes / 4;
-constexpr int kTileBytes = kTile * kStepBytes;      // 16 KiB
 constexpr int kHalfRows = 64;                       // epilogue: one row half of the tile at a time
 constexpr int kLdG = kTile + 1;                     // doubles per LDS row of the G image (odd: the column reads are conflict free)
 constexpr int kGBytes = kHalfRows * kLdG * 8;       // 66 048 B
@@ -48,11 +43,6 @@ struct GramArgs {
     double gamma[kMaxKinds];
     double* out; int64_t ld_out, stride_k;
 };
-
-__device__ __forceinline__ void glds16(const void* g, void* l) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
-                                     (__attribute__((address_space(3))) void*)l, 16, 0, 0);
-}
 
 // rows -> zero-padded float32 copy and float64 norms (a fixed-order tree: deterministic).  One workgroup per padded row.
 __global__ __launch_bounds__(256) void k_gram_prep(const float* __restrict__ feat, int64_t ld_feat, int64_t N, int64_t D,
@@ -95,74 +85,15 @@ __global__ __launch_bounds__(256, 2) void k_gram(GramArgs a) {
     tn[tid] = a.nsq[(tid < kTile ? r0 : c0 - kTile) + tid];
     if (tid < a.nk) kg[tid] = a.kind[tid] == RML_GRAM_LINEAR ? -1.0 : a.gamma[tid];
 
-    // staging addresses: 16 wave-instructions of 1 KiB per operand tile, 4 per wave
-    const unsigned char* ga[4];
-    const unsigned char* gb[4];
-    const int64_t ldb = a.lda * 4;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const int s = (wave * 4 + q) * 64 + lane;     // 16-byte slot in the LDS image
-        const int r = s >> 3;
-        const int c = (s & 7) ^ ((r >> 1) & 7);       // inverse swizzle on the source
-        ga[q] = reinterpret_cast<const unsigned char*>(a.a) + (r0 + r) * ldb + c * 16;
-        gb[q] = reinterpret_cast<const unsigned char*>(a.a) + (c0 + r) * ldb + c * 16;
-    }
-    auto stage = [&](int kt, int buf) {
-        unsigned char* base = smem + buf * 2 * kTileBytes;
-        const int64_t ko = (int64_t)kt * kStepBytes;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            glds16(ga[q] + ko, base + (wave * 4 + q) * 1024);
-            glds16(gb[q] + ko, base + kTileBytes + (wave * 4 + q) * 1024);
-        }
-    };
-
-    // fragment addressing: lane = (row l&15, k-group l>>4) of a 16-row tile
-    int doff_a[4], dsw_a[4], doff_b[4], dsw_b[4];
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-        const int ra = wr * 64 + t * 16 + (lane & 15);
-        const int rb = wc * 64 + t * 16 + (lane & 15);
-        doff_a[t] = ra * kStepBytes; dsw_a[t] = (ra >> 1) & 7;
-        doff_b[t] = rb * kStepBytes; dsw_b[t] = (rb >> 1) & 7;
-    }
+    TileStager sg;
+    const uint8_t* rows = reinterpret_cast<const uint8_t*>(a.a);
+    sg.init<false>(rows, a.lda * 4, r0, rows, a.lda * 4, c0, 0, wave, lane);
+    Frag64 fa, fb;
+    fa.init(wr * 64, lane); fb.init(wc * 64, lane);
     const int kgrp = lane >> 4;
     v4d acc[4][4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = v4d{0.0, 0.0, 0.0, 0.0};
-
-    stage(0, 0);
-    for (int kt = 0; kt < a.KT; ++kt) {
-        __syncthreads();                               // DMA of step kt landed and visible; step kt-1's buffer is free
-        if (kt + 1 < a.KT) stage(kt + 1, (kt + 1) & 1);
-        const unsigned char* sA = smem + (kt & 1) * 2 * kTileBytes;
-        const unsigned char* sB = sA + kTileBytes;
-        // 32 floats per row per K-step = 8 chunks of 4; pass h covers chunks 4h..4h+3, one per k-group;
-        // MFMA c of a pass multiplies element c of every lane's chunk (k = 4*chunk + c)
-#pragma unroll
-        for (int hh = 0; hh < 2; ++hh) {
-            const int ch = 4 * hh + kgrp;
-            v4f af[4], bf[4];
-#pragma unroll
-            for (int t = 0; t < 4; ++t) {
-                af[t] = *reinterpret_cast<const v4f*>(sA + doff_a[t] + ((ch ^ dsw_a[t]) << 4));
-                bf[t] = *reinterpret_cast<const v4f*>(sB + doff_b[t] + ((ch ^ dsw_b[t]) << 4));
-            }
-#pragma unroll
-            for (int c = 0; c < 4; ++c) {
-                double ad[4], bd[4];
-#pragma unroll
-                for (int t = 0; t < 4; ++t) { ad[t] = (double)af[t][c]; bd[t] = (double)bf[t][c]; }
-#pragma unroll
-                for (int i = 0; i < 4; ++i)
-#pragma unroll
-                    for (int j = 0; j < 4; ++j)
-                        acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(ad[i], bd[j], acc[i][j], 0, 0, 0);
-            }
-        }
-    }
+    zero_acc(acc);
+    tile_k_loop(sg, smem, 0, a.KT, [&](const unsigned char* sA, const unsigned char* sB) { kstep_f64(acc, sA, sB, fa, fb, kgrp); });
 
     // ---- epilogue: one row half (64 rows x 128 columns of G) at a time through LDS ----
     double* gd = reinterpret_cast<double*>(smem);      // [64][kLdG]
@@ -176,8 +107,8 @@ __global__ __launch_bounds__(256, 2) void k_gram(GramArgs a) {
                 for (int j = 0; j < 4; ++j)
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
-                        const int ml = i * 16 + kgrp + 4 * r;               // f64 C/D map: row = (lane>>4) + 4 reg
-                        const int nl = wc * 64 + j * 16 + (lane & 15);      //              col = lane & 15
+                        const int ml = cd64_row(i * 16, r, lane);
+                        const int nl = cd64_col(wc * 64 + j * 16, lane);
                         gd[ml * kLdG + nl] = acc[i][j][r];
                     }
         }

@@ -68,13 +68,13 @@ class _Base:
         return Xd
 
 
-MAX_CLASSES = 6         # kMaxC of csrc/svm.hip (15 one-vs-one pairs)
+MAX_CLASSES = 6         # kMaxC of csrc/svm_finish.h (15 one-vs-one pairs)
 
 
 def _check_classes(n):
     if not 2 <= n <= MAX_CLASSES:
         raise NotImplementedError("%d classes: the HIP SVM / linear kernels are built for 2..%d classes "
-                                  "(csrc/svm.hip kMaxC)" % (n, MAX_CLASSES))
+                                  "(csrc/svm_finish.h kMaxC)" % (n, MAX_CLASSES))
 
 
 class GpuSVC(_Base):
