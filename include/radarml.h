@@ -115,7 +115,9 @@ int rml_ctx_device(const rml_ctx* ctx);
  *   RML_OPT_CODE_RMW (default -1 = the measured rule, rml_code_rmw_default; 0 / 1 forced): read-compare-write code-row stores.
  *   RML_OPT_GEMM_BIG (default -1 = the whole-round rule; 0 never, 1 for every chunk of >= 256 rows): 256 x 256 ring GEMM.
  *   RML_OPT_CHUNK (default 0 = chosen per batch): rows per chunk of the chunked front doors (>= 128; rounded up to 128).
- *   RML_OPT_C1_PK (default 1): packed first-layer kernels of the SGAN branches. */
+ *   RML_OPT_C1_PK (default 1): packed first-layer kernels of the SGAN branches.
+ *   RML_OPT_SMO_LDS_ROWS (default RML_SMO_LDS_ROWS_MAX = 2 768, the 160 KB of a CU at 59 bytes per row): rml_smo_solve keeps the state
+ *     of a dual of at most this many rows in LDS; larger duals run the same code on the workspace.  0: every dual on the workspace. */
 #define RML_OPT_PROJECT_SHARE_CU 1
 #define RML_OPT_WAVEFRAME 2
 #define RML_OPT_LINPLANE 3
@@ -126,6 +128,8 @@ int rml_ctx_device(const rml_ctx* ctx);
 #define RML_OPT_GEMM_BIG 8
 #define RML_OPT_CHUNK 9
 #define RML_OPT_C1_PK 10
+#define RML_OPT_SMO_LDS_ROWS 11
+#define RML_SMO_LDS_ROWS_MAX 2768
 int rml_ctx_set_option(rml_ctx* ctx, int option, int value);
 int rml_ctx_get_option(const rml_ctx* ctx, int option, int* value);
 
@@ -337,6 +341,58 @@ int rml_svm_kernel_matrix(rml_ctx* ctx, const rml_svm* m, int path, const float*
 int rml_gram(rml_ctx* ctx, const float* feat, int64_t ld_feat, int64_t N, int64_t D,
              int nk, const int* kinds, const double* gammas,
              double* out, int64_t ld_out, int64_t stride_k, void* stream);
+
+/* ---- SVC duals of a grid search on the device ---------------------------------------------------------------------
+ * rml_smo_solve: a batch of independent binary C-SVC duals (one per grid point x fold x class pair), each solved by one
+ * workgroup running libsvm's Solver::Solve as scikit-learn ships it (sklearn/svm/src/libsvm/svm.cpp: Solver, lines
+ * ~560-1160 -- select_working_set 833-932, do_shrinking 969-1031, reconstruct_gradient 662-709, calculate_rho 1033-1075 --
+ * and SVC_Q, ~1423-1470) on Gram matrices in the layout rml_gram writes.  It replaces the host libsvm fits of
+ * GridSearchCV(SVC) at train.py:462-491.  Working-set ties, the Qfloat rounding of kernel rows, shrinking with its position
+ * permutation, the gradient reconstruction order and the un-fused double arithmetic are libsvm's: on the same matrix n_iter,
+ * alpha and rho are the bits of SVC(kernel='precomputed').fit (n_iter_, |dual_coef_|, -intercept_ up to scikit-learn's
+ * sign flip of binary models).  The matrices must be bit-exactly symmetric.
+ *   gram: DEVICE; matrix k at gram + k * stride_k, row i at + i * ld (ld >= N, stride_k >= N * ld), k < n_mats.
+ *   probs: HOST, n_probs descriptors.  rows: DEVICE int32, n_rows_total entries in [0, N): problem p reads its l Gram rows at
+ *   rows + rows_off in libsvm's order -- the rows of class i (y = +1, the first n_pos) in original order, then those of class
+ *   j (y = -1); problems may share a row list.  Per-row C is Cp for y = +1 and Cn for y = -1 (libsvm's weighted C); eps is
+ *   SVC's tol; max_iter -1 = no limit.
+ *   Outputs, DEVICE: alpha (n_alpha_total doubles; problem p writes l of them at alpha_off, in the order of its row list),
+ *   rho, n_iter, stopped (n_probs each; stopped: 1 = max_iter reached, 0 = converged, -1 = a row index outside [0, N): that
+ *   problem is not solved and its alpha is 0).
+ * rml_smo_score: libsvm's svm_predict_values + vote (svm.cpp ~2842-2900, SVC.predict on K[test, train]) for n_fits models
+ * of n_classes (2..8) classes.  Fit f is made of the n_classes (n_classes - 1) / 2 consecutive problems prob0 .. in libsvm's
+ * pair order (0,1), (0,2), .., (1,2), .., all on one matrix; its held-out Gram rows are test_rows + test_off (DEVICE int32,
+ * n_test entries), their true class indices test_y + test_off.  Per (row, pair) the decision value is the sequential sum of
+ * coef * K[row][sv] over the pair's rows with alpha > 0 (class i then class j, coef = +alpha / -alpha) minus rho -- libsvm's
+ * order, so the values are its bits.  Outputs, DEVICE: dec (n_test_total x pairs doubles, row-major per fit at
+ * test_off * pairs), labels (n_test_total int32 class indices: dec > 0 votes i, first maximum wins), correct (n_fits int32:
+ * labels equal to test_y).  Row indices are checked on the device as in rml_smo_solve: a held-out row, or a row with
+ * alpha > 0, outside [0, N) is not read -- its decision values are NaN and the row's label is -1 (never counted correct).
+ * Both calls use the context's workspace, are asynchronous on `stream` and read no environment variable. */
+typedef struct rml_smo_problem {
+    int32_t matrix;             /* which Gram matrix */
+    int32_t l;                  /* rows of the dual */
+    int32_t n_pos;              /* the first n_pos rows have y = +1 */
+    int32_t shrinking;          /* SVC(shrinking=...) */
+    int32_t max_iter;           /* SVC(max_iter=...), -1: no limit */
+    int32_t reserved;
+    int64_t rows_off;           /* into `rows` */
+    int64_t alpha_off;          /* into `alpha` */
+    double Cp, Cn, eps;
+} rml_smo_problem;
+typedef struct rml_smo_fit {
+    int32_t prob0;              /* first of the fit's pair problems */
+    int32_t n_test;             /* held-out rows */
+    int64_t test_off;           /* into test_rows / test_y / labels; dec at test_off * pairs */
+} rml_smo_fit;
+int rml_smo_solve(rml_ctx* ctx, const double* gram, int64_t N, int64_t ld, int64_t stride_k, int n_mats,
+                  const rml_smo_problem* probs, int64_t n_probs, const int32_t* rows, int64_t n_rows_total,
+                  double* alpha, int64_t n_alpha_total, double* rho, int32_t* n_iter, int32_t* stopped, void* stream);
+int rml_smo_score(rml_ctx* ctx, const double* gram, int64_t N, int64_t ld, int64_t stride_k, int n_mats,
+                  const rml_smo_problem* probs, int64_t n_probs, const int32_t* rows, int64_t n_rows_total,
+                  const double* alpha, int64_t n_alpha_total, const double* rho, int n_classes,
+                  const rml_smo_fit* fits, int64_t n_fits, const int32_t* test_rows, const int32_t* test_y,
+                  int64_t n_test_total, double* dec, int32_t* labels, int32_t* correct, void* stream);
 
 /* Fused front door: volumes -> projection (mode, mask fixed at load: D must match) ->
  * SVM outputs, features never returned to the caller.  Workspace is owned by the ctx and

@@ -68,6 +68,10 @@ SIGNATURES = {
     "rml_svm_kernel_matrix": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p]),
     "rml_gram": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_int64, c_int64,
                          c_void_p]),
+    "rml_smo_solve": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64,
+                              c_void_p, c_void_p, c_void_p, c_void_p]),
+    "rml_smo_score": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64,
+                              c_void_p, c_int, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
     "rml_project_svm": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_int, c_int, c_void_p, c_float,
                                 c_uint32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "rml_derive_project_svm": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_int, c_float, c_uint32, c_void_p,
@@ -125,15 +129,19 @@ SIGNATURES = {
 
 MODE_MAX, MODE_SLICE, MODE_SUM, MODE_MAX_NAN = 0, 1, 2, 3
 # rml_ctx_set_option ids (include/radarml.h RML_OPT_*)
-OPT_PROJECT_SHARE_CU, OPT_WAVEFRAME, OPT_LINPLANE, OPT_STAGE_CODES, OPT_SLICE_WAVE, OPT_DERIVE_FUSED, OPT_CODE_RMW, OPT_GEMM_BIG, OPT_CHUNK, OPT_C1_PK = range(1, 11)
+OPT_PROJECT_SHARE_CU, OPT_WAVEFRAME, OPT_LINPLANE, OPT_STAGE_CODES, OPT_SLICE_WAVE, OPT_DERIVE_FUSED, OPT_CODE_RMW, OPT_GEMM_BIG, OPT_CHUNK, OPT_C1_PK, OPT_SMO_LDS_ROWS = range(1, 12)
 OPTIONS = {"project_share_cu": OPT_PROJECT_SHARE_CU, "waveframe": OPT_WAVEFRAME, "linplane": OPT_LINPLANE, "stage_codes": OPT_STAGE_CODES,
            "slice_wave": OPT_SLICE_WAVE, "derive_fused": OPT_DERIVE_FUSED, "code_rmw": OPT_CODE_RMW, "gemm_big": OPT_GEMM_BIG,
            "chunk": OPT_CHUNK, "c1_pk": OPT_C1_PK}
+# options of the training-side solver (rml_smo_solve); set_option, get_option and the `options` context manager below take these
+# names too (kept apart from OPTIONS, whose keys are the inference paths' knobs)
+SOLVER_OPTIONS = {"smo_lds_rows": OPT_SMO_LDS_ROWS}
+SMO_LDS_ROWS_MAX = 2768
 # A/B runs from a shell (tools/profile_round.sh, tools/kbench.py under rocprofv3): these environment variables are read ONCE, here in
 # Python, when a context is created, and applied as options -- the library itself never reads the environment
 ENV_OPTIONS = {"RML_WAVE_SHARE": "project_share_cu", "RML_WAVEFRAME": "waveframe", "RML_LINPLANE": "linplane", "RML_STAGE_CODES": "stage_codes",
                "RML_SLICE_WAVE": "slice_wave", "RML_DERIVE_FUSED": "derive_fused", "RML_CODE_RMW": "code_rmw", "RML_GEMM_BIG": "gemm_big",
-               "RML_CHUNK": "chunk", "RML_C1_PK": "c1_pk"}
+               "RML_CHUNK": "chunk", "RML_C1_PK": "c1_pk", "RML_SMO_LDS_ROWS": "smo_lds_rows"}
 AUG_ROTATE, AUG_ZOOM, AUG_NOISE = 0, 1, 2
 VOL_F32, VOL_U8 = 0, 1
 MODES = {"max": MODE_MAX, "slice": MODE_SLICE, "sum": MODE_SUM, "max_nan": MODE_MAX_NAN}
@@ -141,6 +149,11 @@ KERNEL_RBF, KERNEL_LINEAR = 0, 1
 PATH_AUTO, PATH_F32, PATH_I8, PATH_F64, PATH_DIGITS = 0, 1, 2, 3, 4
 GRAM_LINEAR, GRAM_RBF = 0, 1
 PATHS = {"auto": PATH_AUTO, "f32": PATH_F32, "i8": PATH_I8, "f64": PATH_F64, "digits": PATH_DIGITS}
+
+
+def option_id(name):
+    """RML_OPT_* id of an option name (a key of OPTIONS or SOLVER_OPTIONS)."""
+    return OPTIONS[name] if name in OPTIONS else SOLVER_OPTIONS[name]
 
 
 def load():
@@ -201,7 +214,7 @@ def context(device=None):
         for var, name in ENV_OPTIONS.items():
             val = os.environ.get(var)
             if val not in (None, ""):
-                check(lib.rml_ctx_set_option(new, OPTIONS[name], int(val)), "rml_ctx_set_option(%s from $%s)" % (name, var))
+                check(lib.rml_ctx_set_option(new, option_id(name), int(val)), "rml_ctx_set_option(%s from $%s)" % (name, var))
         with _lock:
             h = _ctx.setdefault(device, new)
         if h is not new:                    # another thread won the race
@@ -210,17 +223,17 @@ def context(device=None):
 
 
 def set_option(name, value, device=None):
-    """rml_ctx_set_option on the device's context; returns the previous value.  ``name``: a key of OPTIONS."""
+    """rml_ctx_set_option on the device's context; returns the previous value.  ``name``: a key of OPTIONS or SOLVER_OPTIONS."""
     lib, ctx = load(), context(device)
     old = C.c_int()
-    check(lib.rml_ctx_get_option(ctx, OPTIONS[name], C.byref(old)), "rml_ctx_get_option")
-    check(lib.rml_ctx_set_option(ctx, OPTIONS[name], int(value)), "rml_ctx_set_option")
+    check(lib.rml_ctx_get_option(ctx, option_id(name), C.byref(old)), "rml_ctx_get_option")
+    check(lib.rml_ctx_set_option(ctx, option_id(name), int(value)), "rml_ctx_set_option")
     return old.value
 
 
 def get_option(name, device=None):
     v = C.c_int()
-    check(load().rml_ctx_get_option(context(device), OPTIONS[name], C.byref(v)), "rml_ctx_get_option")
+    check(load().rml_ctx_get_option(context(device), option_id(name), C.byref(v)), "rml_ctx_get_option")
     return v.value
 
 

@@ -87,6 +87,35 @@ int rml_ws_reserve(rml_ctx* ctx, size_t bytes, void** out, hipStream_t st) {
     return RML_OK;
 }
 
+int rml_stage_reserve(rml_ctx* ctx, size_t bytes, void** host) {
+    if (ctx->ev_stage_valid) {
+        RML_HIP(hipEventSynchronize(ctx->ev_stage));
+        ctx->ev_stage_valid = false;
+    }
+    if (bytes > ctx->stage_bytes) {
+        if (ctx->stage) { (void)hipHostFree(ctx->stage); ctx->stage = nullptr; ctx->stage_bytes = 0; }
+        const size_t want = bytes + (bytes >> 2);
+        const hipError_t e = hipHostMalloc(&ctx->stage, want, hipHostMallocDefault);
+        if (e != hipSuccess) {
+            ctx->stage = nullptr;
+            rml_set_error("pinned staging allocation of %zu bytes failed: %s", want, hipGetErrorString(e));
+            (void)hipGetLastError();
+            return RML_ERR_NOMEM;
+        }
+        ctx->stage_bytes = want;
+    }
+    *host = ctx->stage;
+    return RML_OK;
+}
+
+int rml_stage_upload(rml_ctx* ctx, void* dst, size_t bytes, hipStream_t st) {
+    if (!ctx->ev_stage) RML_HIP(hipEventCreateWithFlags(&ctx->ev_stage, hipEventDisableTiming));
+    RML_HIP(hipMemcpyAsync(dst, ctx->stage, bytes, hipMemcpyHostToDevice, st));
+    RML_HIP(hipEventRecord(ctx->ev_stage, st));
+    ctx->ev_stage_valid = true;
+    return RML_OK;
+}
+
 extern "C" int rml_ctx_reserve_workspace(rml_ctx* ctx, int64_t bytes) {
     RML_REQUIRE(ctx != nullptr && bytes >= 0, RML_ERR_INVALID, "rml_ctx_reserve_workspace: bad arguments");
     std::lock_guard<std::recursive_mutex> lk(ctx->mu);
@@ -157,6 +186,8 @@ extern "C" int rml_ctx_destroy(rml_ctx* ctx) {
     if (ctx->ev_fork) (void)hipEventDestroy(ctx->ev_fork);
     if (ctx->ev_join) (void)hipEventDestroy(ctx->ev_join);
     if (ctx->ev_last) (void)hipEventDestroy(ctx->ev_last);
+    if (ctx->ev_stage) (void)hipEventDestroy(ctx->ev_stage);
+    if (ctx->stage) (void)hipHostFree(ctx->stage);
     for (int i = 0; i < 2; ++i) {
         if (ctx->ev_proj[i]) (void)hipEventDestroy(ctx->ev_proj[i]);
         if (ctx->ev_done[i]) (void)hipEventDestroy(ctx->ev_done[i]);
@@ -271,6 +302,12 @@ static int* opt_slot(rml_opts& o, int option) {
 extern "C" int rml_ctx_set_option(rml_ctx* ctx, int option, int value) {
     RML_REQUIRE(ctx != nullptr, RML_ERR_INVALID, "rml_ctx_set_option: ctx is NULL");
     std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+    if (option == RML_OPT_SMO_LDS_ROWS) {
+        RML_REQUIRE(value >= 0 && value <= RML_SMO_LDS_ROWS_MAX, RML_ERR_INVALID, "rml_ctx_set_option: RML_OPT_SMO_LDS_ROWS is 0..%d rows",
+                    RML_SMO_LDS_ROWS_MAX);
+        ctx->opt.smo_lds_rows = value;
+        return RML_OK;
+    }
     if (option == RML_OPT_CHUNK) {
         RML_REQUIRE(value == 0 || value >= 128, RML_ERR_INVALID, "rml_ctx_set_option: RML_OPT_CHUNK is 0 (automatic) or >= 128 rows");
         ctx->opt.chunk = value;
@@ -291,6 +328,7 @@ extern "C" int rml_ctx_get_option(const rml_ctx* ctx, int option, int* value) {
     rml_ctx* c = const_cast<rml_ctx*>(ctx);
     std::lock_guard<std::recursive_mutex> lk(c->mu);
     if (option == RML_OPT_CHUNK) { *value = (int)c->opt.chunk; return RML_OK; }
+    if (option == RML_OPT_SMO_LDS_ROWS) { *value = c->opt.smo_lds_rows; return RML_OK; }
     const int* slot = opt_slot(c->opt, option);
     RML_REQUIRE(slot != nullptr, RML_ERR_INVALID, "rml_ctx_get_option: unknown option %d", option);
     *value = *slot;

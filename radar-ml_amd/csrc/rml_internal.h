@@ -37,6 +37,7 @@ struct rml_opts {
     int gemm_big = -1;          // RML_OPT_GEMM_BIG: -1 = whole-round rule (use_big_gemm), 0 never, 1 for every n >= 256
     int c1_pk = 1;              // RML_OPT_C1_PK: packed first-layer kernels of the SGAN branches
     int64_t chunk = 0;          // RML_OPT_CHUNK: rows per chunk of the chunked front doors, 0 = chosen per batch
+    int smo_lds_rows = RML_SMO_LDS_ROWS_MAX;   // RML_OPT_SMO_LDS_ROWS: duals of more rows run on the workspace variant of k_smo
 };
 
 struct rml_ws_retired {         // a workspace block that was outgrown: freed once the work queued before its retirement is done
@@ -71,6 +72,11 @@ struct rml_ctx {
     std::recursive_mutex mu;
     hipEvent_t ev_last = nullptr;
     bool ev_last_valid = false;
+    // pinned host buffer for per-call descriptor tables (rml_stage_reserve / rml_stage_upload), and the event behind its last copy
+    void* stage = nullptr;
+    size_t stage_bytes = 0;
+    hipEvent_t ev_stage = nullptr;
+    bool ev_stage_valid = false;
 };
 
 // RAII serialisation of one entry point on a context: locks ctx->mu, makes `stream` wait for the work the previous
@@ -136,6 +142,12 @@ int rml_hip_fail(hipError_t e, const char* what, const char* file, int line);
 
 // workspace of at least `bytes` (inside an rml_ctx_guard on `st`); growing allocates -- not inside a stream capture: context.hip
 int rml_ws_reserve(rml_ctx* ctx, size_t bytes, void** out, hipStream_t st);
+
+// Per-call descriptor tables (inside an rml_ctx_guard): rml_stage_reserve hands out the context's pinned host buffer, grown to
+// `bytes`, after the copy of the previous user has completed (a wait for a few KB queued a whole call ago); rml_stage_upload
+// copies its first `bytes` to `dst` asynchronously on `st`.
+int rml_stage_reserve(rml_ctx* ctx, size_t bytes, void** host);
+int rml_stage_upload(rml_ctx* ctx, void* dst, size_t bytes, hipStream_t st);
 
 // ---- projection (project.hip) -------------------------------------------------------------
 struct ProjOut {

@@ -24,27 +24,106 @@ _CARRY = ("C", "probability", "class_weight", "random_state", "cache_size", "tol
 _NONFINITE = "Input contains NaN, infinity or a value too large for dtype('float64')."      # scikit-learn's message
 
 
-def _gram(X, kernels, device=None):
-    """Every kernel matrix of ``kernels`` (a list of ('linear', None) / ('rbf', gamma), at most 8) of the float32 rows ``X`` against
-    themselves: one upload, one ``rml_gram`` call, one copy back.  Returns a list of host (N, N) float64 matrices.
-
-    All device work of the search goes through this function (tests replace it to run the search logic without a GPU)."""
+def _gram_device(X, kernels, dev):
+    """``rml_gram`` of the float32 host rows ``X`` for ``kernels``: a DEVICE (len(kernels), N, N) float64 tensor."""
     import torch
     lib = _lib.load()
     if not 1 <= len(kernels) <= 8:
         raise ValueError("_gram: 1..8 kernels per call, got %d" % len(kernels))
     N, D = X.shape
-    dev = _lib.device_of(device)
     ctx = _lib.context(dev)
     kinds = np.array([_lib.GRAM_LINEAR if k == "linear" else _lib.GRAM_RBF for k, _ in kernels], dtype=np.int32)
     gammas = np.array([0.0 if g is None else float(g) for _, g in kernels], dtype=np.float64)
+    Xd = torch.from_numpy(np.ascontiguousarray(X, dtype=np.float32)).to(dev)
+    out = torch.empty((len(kernels), N, N), dtype=torch.float64, device=dev)
+    _lib.check(lib.rml_gram(ctx, _lib.ptr(Xd), D, N, D, len(kernels), kinds.ctypes.data, gammas.ctypes.data, _lib.ptr(out),
+                            N, N * N, _lib.stream_ptr(dev)), "rml_gram")
+    return out
+
+
+def _gram(X, kernels, device=None):
+    """Every kernel matrix of ``kernels`` (a list of ('linear', None) / ('rbf', gamma), at most 8) of the float32 rows ``X`` against
+    themselves: one upload, one ``rml_gram`` call, one copy back.  Returns a list of host (N, N) float64 matrices.
+
+    All device work of the host search goes through this function (tests replace it to run the search logic without a GPU)."""
+    import torch
+    dev = _lib.device_of(device)
     with torch.cuda.device(dev):
-        Xd = torch.from_numpy(np.ascontiguousarray(X, dtype=np.float32)).to(dev)
-        out = torch.empty((len(kernels), N, N), dtype=torch.float64, device=dev)
-        _lib.check(lib.rml_gram(ctx, _lib.ptr(Xd), D, N, D, len(kernels), kinds.ctypes.data, gammas.ctypes.data, _lib.ptr(out),
-                                N, N * N, _lib.stream_ptr(dev)), "rml_gram")
-        host = out.cpu().numpy()
+        host = _gram_device(X, kernels, dev).cpu().numpy()
     return [host[k] for k in range(len(kernels))]
+
+
+# rml_smo_problem / rml_smo_fit of include/radarml.h
+SMO_PROBLEM = np.dtype([("matrix", "<i4"), ("l", "<i4"), ("n_pos", "<i4"), ("shrinking", "<i4"), ("max_iter", "<i4"), ("reserved", "<i4"),
+                        ("rows_off", "<i8"), ("alpha_off", "<i8"), ("Cp", "<f8"), ("Cn", "<f8"), ("eps", "<f8")])
+SMO_FIT = np.dtype([("prob0", "<i4"), ("n_test", "<i4"), ("test_off", "<i8")])
+
+
+def smo_device(Kd, plan, device=None):
+    """``rml_smo_solve`` + ``rml_smo_score`` on the DEVICE matrices ``Kd`` (a (nk, N, N) float64 tensor, each matrix bit-exactly
+    symmetric) for ``plan``: a dict of ``problems`` (SMO_PROBLEM records), ``rows`` (int32, the problems' Gram rows), ``fits``
+    (SMO_FIT records), ``test_rows`` / ``test_y`` (int32: held-out Gram rows and their class indices) and ``n_classes``.
+    Returns host arrays ``alpha``, ``rho``, ``n_iter``, ``stopped`` per problem, ``dec``, ``labels`` per held-out row, ``correct`` per
+    fit, and ``solve_s`` / ``score_s``, the wall time of the two batched calls."""
+    import torch
+    lib = _lib.load()
+    dev = _lib.device_of(device if device is not None else Kd.device)
+    ctx = _lib.context(dev)
+    probs = np.ascontiguousarray(plan["problems"], dtype=SMO_PROBLEM)
+    fits = np.ascontiguousarray(plan["fits"], dtype=SMO_FIT)
+    nk, N = int(Kd.shape[0]), int(Kd.shape[1])
+    if Kd.dtype != torch.float64 or Kd.dim() != 3 or Kd.shape[2] != N or not Kd.is_contiguous():
+        raise ValueError("smo_device: the matrices are a contiguous (nk, N, N) float64 tensor")
+    C = int(plan["n_classes"])
+    P = C * (C - 1) // 2
+    n_alpha = int((probs["alpha_off"] + probs["l"]).max()) if len(probs) else 0
+    with torch.cuda.device(dev):
+        i32 = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(dev)
+        rows, te_rows, te_y = i32(plan["rows"]), i32(plan["test_rows"]), i32(plan["test_y"])
+        n_test = int(te_rows.numel())
+        alpha = torch.zeros(max(n_alpha, 1), dtype=torch.float64, device=dev)
+        rho = torch.zeros(max(len(probs), 1), dtype=torch.float64, device=dev)
+        n_iter = torch.zeros(max(len(probs), 1), dtype=torch.int32, device=dev)
+        stopped = torch.zeros(max(len(probs), 1), dtype=torch.int32, device=dev)
+        dec = torch.zeros(max(n_test * P, 1), dtype=torch.float64, device=dev)
+        labels = torch.zeros(max(n_test, 1), dtype=torch.int32, device=dev)
+        correct = torch.zeros(max(len(fits), 1), dtype=torch.int32, device=dev)
+        st = _lib.stream_ptr(dev)
+        torch.cuda.synchronize(dev)
+        t0 = time.perf_counter()
+        _lib.check(lib.rml_smo_solve(ctx, _lib.ptr(Kd), N, N, N * N, nk, probs.ctypes.data, len(probs), _lib.ptr(rows), int(rows.numel()),
+                                     _lib.ptr(alpha), n_alpha, _lib.ptr(rho), _lib.ptr(n_iter), _lib.ptr(stopped), st), "rml_smo_solve")
+        torch.cuda.synchronize(dev)
+        t1 = time.perf_counter()
+        _lib.check(lib.rml_smo_score(ctx, _lib.ptr(Kd), N, N, N * N, nk, probs.ctypes.data, len(probs), _lib.ptr(rows), int(rows.numel()),
+                                     _lib.ptr(alpha), n_alpha, _lib.ptr(rho), C, fits.ctypes.data, len(fits), _lib.ptr(te_rows),
+                                     _lib.ptr(te_y), n_test, _lib.ptr(dec), _lib.ptr(labels), _lib.ptr(correct), st), "rml_smo_score")
+        torch.cuda.synchronize(dev)
+        t2 = time.perf_counter()
+        out = {"alpha": alpha.cpu().numpy()[:n_alpha], "rho": rho.cpu().numpy()[:len(probs)], "n_iter": n_iter.cpu().numpy()[:len(probs)],
+               "stopped": stopped.cpu().numpy()[:len(probs)], "dec": dec.cpu().numpy()[:n_test * P].reshape(n_test, P),
+               "labels": labels.cpu().numpy()[:n_test], "correct": correct.cpu().numpy()[:len(fits)],
+               "solve_s": t1 - t0, "score_s": t2 - t1}
+    if (out["stopped"] < 0).any():
+        raise _lib.RadarMLError("rml_smo_solve: a problem names a row outside the matrix")
+    if (out["labels"] < 0).any():
+        raise _lib.RadarMLError("rml_smo_score: a held-out row outside the matrix")
+    return out
+
+
+def _smo(X, kernels, plan, device=None):
+    """The kernel matrices of ``kernels`` of the float32 rows ``X`` (``rml_gram``, as ``_gram``) kept ON THE DEVICE, every dual of
+    ``plan`` solved on them in one ``rml_smo_solve`` call and every held-out row scored in one ``rml_smo_score`` call (``smo_device``).
+    Returns ``smo_device``'s dict plus ``matrix``: a function k -> host copy of matrix k (the search fetches the winner's only).
+
+    All device work of the device search goes through this function (tests replace it to run the search logic without a GPU)."""
+    import torch
+    dev = _lib.device_of(device)
+    with torch.cuda.device(dev):
+        Kd = _gram_device(X, kernels, dev)
+        out = smo_device(Kd, plan, dev)
+    out["matrix"] = lambda k: Kd[k].cpu().numpy()
+    return out
 
 
 def _rows(X):
@@ -106,10 +185,19 @@ class GridSearchSVC:
     ``best_index_``, ``cv_results_``, ``n_splits_``, ``refit_time_``, ``scorer_`` (accuracy).  Fit order: rows validated; every distinct
     kernel of the grid computed by ``rml_gram`` (grouped so that the host copies stay under ``max_gram_bytes``); the candidates in
     ``ParameterGrid`` order x the splits fitted by libsvm on ``K[train, train]`` and scored on ``K[test, train]`` on a pool of
-    ``n_jobs`` threads (libsvm releases the GIL); the best point refitted on all rows."""
+    ``n_jobs`` threads (libsvm releases the GIL); the best point refitted on all rows.
+
+    ``solver="device"`` keeps the kernel matrices on the GPU and replaces the host fits and scores of the search: per group of
+    kernels, every candidate x split x class-pair dual is solved by ONE ``rml_smo_solve`` call (libsvm's SMO, one workgroup per
+    dual, the same iterates bit for bit) and every held-out row is scored by ONE ``rml_smo_score`` call; only the winner's matrix
+    is copied back, for the same host refit (``probability`` and libsvm's Platt step included).  ``tol``, ``shrinking``,
+    ``max_iter`` and ``class_weight`` of the base estimator are honoured (weighted C as scikit-learn forms it: ``compute_class_weight``
+    on the fold's labels, times C).  A split whose training rows miss a class is fitted on the host as before.  The batch has no
+    per-fit times: ``fit_time`` / ``score_time`` of a device fit are the batch's solve / score time divided evenly among its fits.
+    ``solver="host"`` (the default) is the search described above."""
 
     def __init__(self, estimator, param_grid, cv=5, n_jobs=4, refit=True, device=None, max_gram_bytes=8 << 30, scoring=None,
-                 verbose=0):
+                 verbose=0, solver="host"):
         self.estimator = estimator
         self.param_grid = param_grid
         self.cv = cv
@@ -119,11 +207,14 @@ class GridSearchSVC:
         self.max_gram_bytes = max_gram_bytes
         self.scoring = scoring
         self.verbose = verbose
+        self.solver = solver
 
     # ---- argument checks (before any work) ----
     def _check(self):
         from sklearn.model_selection import ParameterGrid
         from sklearn.svm import SVC
+        if self.solver not in ("host", "device"):
+            raise ValueError("GridSearchSVC: solver must be 'host' or 'device', got %r" % (self.solver,))
         if type(self.estimator) is not SVC:
             raise NotImplementedError("GridSearchSVC searches sklearn.svm.SVC, not %s" % type(self.estimator).__name__)
         if self.scoring not in (None, "accuracy"):
@@ -162,6 +253,55 @@ class GridSearchSVC:
         if probability is not None:
             kw["probability"] = probability
         return SVC(kernel=kernel, **kw)
+
+    def _smo_plan(self, candidates, base, grp, splits, y):
+        """The batch of one group of kernels for ``_smo``: per candidate of the group (ParameterGrid order) and split, one fit made of
+        one dual per class pair in libsvm's order.  Returns (plan, [(ci, si) of fit f], [(ci, si) left to the host])."""
+        from sklearn.utils.class_weight import compute_class_weight
+        classes = np.unique(y)
+        nc = len(classes)
+        yi = np.searchsorted(classes, y).astype(np.int32)
+        pairs = [(a, b) for a in range(nc) for b in range(a + 1, nc)]
+        rows, test_rows, test_y = [], [], []
+        per_split = {}                      # si -> ([(rows_off, l, n_pos) per pair], class weights)
+        n_rows = 0
+        for si, (tr, te) in enumerate(splits):
+            if not 2 <= nc <= 8 or len(np.unique(yi[tr])) < nc or len(te) == 0:
+                continue                    # a class without rows in this fold: libsvm fits another model -- the host path's job
+            cw = base["class_weight"]
+            w = np.ones(nc) if cw is None else compute_class_weight(cw, classes=classes, y=y[tr])
+            subs = []
+            for a, b in pairs:
+                ra, rb = tr[yi[tr] == a], tr[yi[tr] == b]
+                rows += [ra, rb]
+                subs.append((n_rows, len(ra) + len(rb), len(ra)))
+                n_rows += len(ra) + len(rb)
+            per_split[si] = (subs, w)
+        problems, fits, on_device, host = [], [], [], []
+        n_alpha = n_test = 0
+        for ci, p in enumerate(candidates):
+            key = self._key(p, base)
+            if key not in grp:
+                continue
+            C = float(p.get("C", base["C"]))
+            for si, (tr, te) in enumerate(splits):
+                if si not in per_split:
+                    host.append((ci, si))
+                    continue
+                subs, w = per_split[si]
+                fits.append((len(problems), len(te), n_test))
+                on_device.append((ci, si))
+                test_rows.append(te)
+                test_y.append(yi[te])
+                n_test += len(te)
+                for (off, l, n_pos), (a, b) in zip(subs, pairs):
+                    problems.append((grp.index(key), l, n_pos, int(bool(base["shrinking"])), int(base["max_iter"]), 0, off, n_alpha,
+                                     C * w[a], C * w[b], float(base["tol"])))
+                    n_alpha += l
+        cat = lambda parts: np.concatenate(parts).astype(np.int32) if parts else np.zeros(0, np.int32)
+        plan = {"problems": np.array(problems, dtype=SMO_PROBLEM), "rows": cat(rows), "fits": np.array(fits, dtype=SMO_FIT),
+                "test_rows": cat(test_rows), "test_y": cat(test_y), "n_classes": nc}
+        return plan, on_device, host
 
     def fit(self, X, y):
         from sklearn.base import clone
@@ -224,11 +364,28 @@ class GridSearchSVC:
                                                              t2 - t0), flush=True)
 
         mats = {}
+        fetch = {}                              # device search: kernel key -> function returning its host matrix (last group only)
         with ThreadPoolExecutor(max_workers=nj) as pool:
             for grp in groups:
-                mats = dict(zip(grp, _gram(X32, grp, self.device)))
-                jobs = [pool.submit(one, mats[self._key(p, base)], ci, si)
-                        for ci, p in enumerate(candidates) if self._key(p, base) in mats for si in range(n_splits)]
+                todo = [(ci, si) for ci, p in enumerate(candidates) if self._key(p, base) in grp for si in range(n_splits)]
+                if self.solver == "device":
+                    plan, on_device, todo = self._smo_plan(candidates, base, grp, splits, y)
+                    out = _smo(X32, grp, plan, self.device)
+                    fetch = {k: (lambda i=i, m=out["matrix"]: m(i)) for i, k in enumerate(grp)}
+                    mats = {}
+                    for f, (ci, si) in enumerate(on_device):
+                        scores[ci, si] = float(out["correct"][f]) / len(splits[si][1])
+                        fit_t[ci, si] = out["solve_s"] / len(on_device)
+                        score_t[ci, si] = out["score_s"] / len(on_device)
+                        if self.verbose > 1:
+                            p = candidates[ci]
+                            print("[CV %d/%d] END %s; total time=%5.1fs" % (si + 1, n_splits, ", ".join("%s=%s" % (k, p[k]) for k in sorted(p)),
+                                                                         fit_t[ci, si] + score_t[ci, si]), flush=True)
+                    for k in sorted({self._key(candidates[ci], base) for ci, _ in todo}, key=grp.index):
+                        mats[k] = fetch[k]()
+                else:
+                    mats = dict(zip(grp, _gram(X32, grp, self.device)))
+                jobs = [pool.submit(one, mats[self._key(candidates[ci], base)], ci, si) for ci, si in todo]
                 for j in jobs:
                     j.result()
 
@@ -261,7 +418,7 @@ class GridSearchSVC:
         if self.refit:
             best = self.best_params_
             key = self._key(best, base)
-            K = mats[key] if key in mats else _gram(X32, [key], self.device)[0]
+            K = mats[key] if key in mats else fetch[key]() if key in fetch else _gram(X32, [key], self.device)[0]
             t0 = time.perf_counter()
             pre = self._svc(best, base, "precomputed").fit(K, y)
             self.refit_time_ = time.perf_counter() - t0
@@ -292,8 +449,9 @@ class GridSearchSVC:
         return self.best_estimator_.score(X, y)
 
 
-def find_best_svm_estimator(X, y, cv, random_seed):
+def find_best_svm_estimator(X, y, cv, random_seed, solver="host"):
     """Exhaustive search over specified parameter values for svm (train.py:462-491, the same grid, base estimator and log lines).
+    ``solver="device"`` runs the search's fits on the GPU (GridSearchSVC); the result is the same.
 
     Returns:
         optimized svm estimator.
@@ -311,7 +469,7 @@ def find_best_svm_estimator(X, y, cv, random_seed):
     ]
     init_est = svm.SVC(probability=True, class_weight='balanced',
                        random_state=random_seed, cache_size=1000, verbose=False)
-    grid_search = GridSearchSVC(estimator=init_est, param_grid=param_grid, verbose=2, n_jobs=4, cv=cv)
+    grid_search = GridSearchSVC(estimator=init_est, param_grid=param_grid, verbose=2, n_jobs=4, cv=cv, solver=solver)
     grid_search.fit(X, y)
     logger.info('\n Best estimator:')
     logger.info(grid_search.best_estimator_)

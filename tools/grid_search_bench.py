@@ -1,6 +1,6 @@
 """SVC grid search on GPU kernel matrices (GridSearchSVC, rml_gram): one JSON line.
 
-    python tools/grid_search_bench.py [--sets 1458,7290] [--jobs 4,16] [--sklearn]
+    python tools/grid_search_bench.py [--sets 1458,7290] [--jobs 4,16] [--solver host|device] [--sklearn]
 
 Two seeded synthetic training sets at the reference's feature length D = 10 010 (three planes of the Walabot grid):
   1458 x 10010  rows on the code grid, float32(c/255) (the reference's balanced training set, train.py:534)
@@ -10,6 +10,11 @@ and the reference's grid (5 linear + 25 RBF points, 5 stratified folds).  Per se
   d2h_ms         the six N x N float64 matrices to the host
   host_s_jJ      the search on the host (libsvm fits on the precomputed matrices) with n_jobs = J
   total_s        one end-to-end GridSearchSVC.fit (upload, Gram, copy, search, refit) at the largest n_jobs
+--solver device times GridSearchSVC(solver="device") instead (the duals solved by rml_smo_solve on the resident matrices): per n_jobs
+(used only by the refit-free host fall-backs, so the figures should agree) device_search_s_jJ end to end, plus of the last run
+  smo_solve_ms / smo_score_ms   wall time of the batched rml_smo_solve / rml_smo_score calls, host-synchronised
+  smo_problems, smo_iters, smo_iters_max   duals in the batch, their libsvm iterations in total and of the longest dual
+  refit_s        the host refit of the winner (libsvm with probability=True), part of every search
 --sklearn also runs scikit-learn's GridSearchCV on the raw rows of the 1458 set, on the sub-grid stated in the output (the full grid
 runs for about an hour), and reports its time and whether best_params_ agree with GridSearchSVC on the same sub-grid.
 """
@@ -87,6 +92,39 @@ def gram_timing(rml, X, kernels, reps=3):
     return min(ms), d2h, [host[k] for k in range(len(kernels))]
 
 
+def run_set_device(rml, N, on_grid, jobs, seed):
+    """GridSearchSVC(solver="device") end to end per n_jobs, with the batch's own figures (train._smo wrapped, not replaced)"""
+    from sklearn.model_selection import StratifiedKFold
+    import radar_ml_amd.train as T
+    X, y = synth(N, on_grid, seed)
+    res = {"rows": N, "D": D, "on_code_grid": on_grid, "solver": "device"}
+    real = T._smo
+    seen = []
+
+    def watched(Xh, ks, plan, device=None):
+        out = real(Xh, ks, plan, device)
+        seen.append((len(plan["problems"]), out["solve_s"], out["score_s"], int(out["n_iter"].sum()), int(out["n_iter"].max()),
+                     int(plan["problems"]["l"].max())))
+        return out
+    T._smo = watched
+    try:
+        T.GridSearchSVC(base_svc(), GRID, cv=StratifiedKFold(5).split(X, y), n_jobs=min(jobs), solver="device").fit(X, y)   # warm-up
+        for j in sorted(jobs):
+            del seen[:]
+            t0 = time.perf_counter()
+            gs = T.GridSearchSVC(base_svc(), GRID, cv=StratifiedKFold(5).split(X, y), n_jobs=j, solver="device").fit(X, y)
+            res["device_search_s_j%d" % j] = round(time.perf_counter() - t0, 3)
+            progress("%d rows: device search at n_jobs=%d: %.3f s (solve %.1f ms, score %.1f ms, refit %.3f s)"
+                     % (N, j, res["device_search_s_j%d" % j], 1e3 * sum(s[1] for s in seen), 1e3 * sum(s[2] for s in seen), gs.refit_time_))
+    finally:
+        T._smo = real
+    res.update({"smo_solve_ms": round(1e3 * sum(s[1] for s in seen), 2), "smo_score_ms": round(1e3 * sum(s[2] for s in seen), 2),
+                "smo_problems": sum(s[0] for s in seen), "smo_iters": sum(s[3] for s in seen), "smo_iters_max": max(s[4] for s in seen),
+                "smo_rows_max": max(s[5] for s in seen), "refit_s": round(gs.refit_time_, 3),
+                "best_params": gs.best_params_, "best_score": round(gs.best_score_, 4)})
+    return res, X, y
+
+
 def run_set(rml, N, on_grid, jobs, seed):
     from sklearn.model_selection import StratifiedKFold
     import radar_ml_amd.train as T
@@ -143,6 +181,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sets", default="1458,7290", help="training set sizes to run (1458: code grid, 7290: off-grid)")
     ap.add_argument("--jobs", default="4,16", help="n_jobs values of the host search")
+    ap.add_argument("--solver", default="host", choices=["host", "device"], help="where the search's SVC duals are solved")
     ap.add_argument("--sklearn", action="store_true", help="also time scikit-learn's GridSearchCV on the 1458 set (sub-grid)")
     args = ap.parse_args()
     import torch
@@ -153,7 +192,7 @@ def main():
     out = {"metric": "svc_grid_search", "grid": "5 linear + 25 rbf, 5 folds", "f64_peak_tflops": F64_PEAK / 1e12, "sets": []}
     keep = None
     for n in [int(s) for s in args.sets.split(",")]:
-        r, X, y = run_set(rml, n, n == 1458, jobs, seed=n)
+        r, X, y = (run_set_device if args.solver == "device" else run_set)(rml, n, n == 1458, jobs, seed=n)
         out["sets"].append(r)
         if n == 1458:
             keep = (X, y)

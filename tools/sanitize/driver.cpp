@@ -45,6 +45,13 @@ static void phase_a_arguments() {
         const double gm[2] = {0.0, 0.5};
         CHECK(rml_gram(nullptr, &f, 1, 1, 1, 2, kd, gm, &d, 1, 1, nullptr) == RML_ERR_INVALID && strlen(rml_last_error()) > 0);
     }
+    {
+        rml_smo_problem sp{};
+        rml_smo_fit sf{};
+        int32_t i32 = 0;
+        CHECK(rml_smo_solve(nullptr, &d, 1, 1, 1, 1, &sp, 1, &i32, 1, &d, 1, &d, &i32, &i32, nullptr) == RML_ERR_INVALID && strlen(rml_last_error()) > 0);
+        CHECK(rml_smo_score(nullptr, &d, 1, 1, 1, 1, &sp, 1, &i32, 1, &d, 1, &d, 2, &sf, 1, &i32, &i32, 1, &d, &i32, &i32, nullptr) == RML_ERR_INVALID);
+    }
     CHECK(rml_profile_read(nullptr, &n, &d, &n) < 0);
     CHECK(rml_probe_stream(nullptr, &f, 1 << 20, 1, &d, nullptr) < 0);
     CHECK(rml_ctx_set_option(nullptr, RML_OPT_PROJECT_SHARE_CU, 1) < 0);
@@ -226,6 +233,45 @@ static void phase_b_gram_arguments(rml_ctx* ctx) {
     CHECK(rml_gram(ctx, nullptr, D, 0, D, 2, kd, gm, nullptr, 0, 0, nullptr) == RML_OK);       // N == 0: a no-op
 }
 
+// rml_smo_solve / rml_smo_score: every bad descriptor is a status and a message, before any device work
+static void phase_b_smo_arguments(rml_ctx* ctx) {
+    double d = 0;
+    int32_t i32 = 0;
+    const int64_t N = 4;
+    rml_smo_problem ok{};
+    ok.matrix = 0; ok.l = 4; ok.n_pos = 2; ok.shrinking = 1; ok.max_iter = -1; ok.rows_off = 0; ok.alpha_off = 0; ok.Cp = 1.0; ok.Cn = 1.0; ok.eps = 1e-3;
+    auto solve = [&](const rml_smo_problem& p, int64_t n_rows = 4, int64_t n_alpha = 4, int n_mats = 1) {
+        return rml_smo_solve(ctx, &d, N, N, N * N, n_mats, &p, 1, &i32, n_rows, &d, n_alpha, &d, &i32, &i32, nullptr);
+    };
+    rml_smo_problem p = ok;
+    p.matrix = 1; CHECK(solve(p) == RML_ERR_INVALID); p = ok;
+    p.l = 0; CHECK(solve(p) == RML_ERR_INVALID); p = ok;
+    p.n_pos = 5; CHECK(solve(p) == RML_ERR_INVALID); p = ok;
+    p.rows_off = 1; CHECK(solve(p) == RML_ERR_INVALID); p = ok;
+    p.alpha_off = -1; CHECK(solve(p) == RML_ERR_INVALID); p = ok;
+    p.Cp = 0.0; CHECK(solve(p) == RML_ERR_INVALID); p = ok;
+    p.Cn = NAN; CHECK(solve(p) == RML_ERR_INVALID); p = ok;
+    p.eps = -1e-3; CHECK(solve(p) == RML_ERR_INVALID); p = ok;
+    p.max_iter = -2; CHECK(solve(p) == RML_ERR_INVALID); p = ok;
+    CHECK(solve(ok, 3) == RML_ERR_INVALID && solve(ok, 4, 3) == RML_ERR_INVALID && solve(ok, 4, 4, 0) == RML_ERR_INVALID);
+    CHECK(strlen(rml_last_error()) > 0);
+    CHECK(rml_smo_solve(ctx, &d, N, N - 1, N * N, 1, &ok, 1, &i32, 4, &d, 4, &d, &i32, &i32, nullptr) == RML_ERR_INVALID);
+    CHECK(rml_smo_solve(ctx, nullptr, N, N, N * N, 1, &ok, 1, &i32, 4, &d, 4, &d, &i32, &i32, nullptr) == RML_ERR_INVALID);
+    CHECK(rml_smo_solve(ctx, nullptr, N, N, N * N, 1, nullptr, 0, nullptr, 0, nullptr, 0, nullptr, nullptr, nullptr, nullptr) == RML_OK);   // no problems: a no-op
+    rml_smo_fit f{};
+    f.prob0 = 0; f.n_test = 2; f.test_off = 0;
+    auto score = [&](const rml_smo_fit& ff, int n_classes, int64_t n_test_total) {
+        return rml_smo_score(ctx, &d, N, N, N * N, 1, &ok, 1, &i32, 4, &d, 4, &d, n_classes, &ff, 1, &i32, &i32, n_test_total, &d, &i32, &i32, nullptr);
+    };
+    CHECK(score(f, 1, 2) == RML_ERR_INVALID && score(f, 9, 2) == RML_ERR_INVALID);
+    CHECK(score(f, 3, 2) == RML_ERR_INVALID);          // three classes need three pair problems, one given
+    CHECK(score(f, 2, 1) == RML_ERR_INVALID);          // held-out rows past the list
+    rml_smo_fit g = f;
+    g.prob0 = 1; CHECK(score(g, 2, 2) == RML_ERR_INVALID);
+    int32_t cnt[1];
+    CHECK(rml_smo_score(ctx, &d, N, N, N * N, 1, &ok, 1, &i32, 4, &d, 4, &d, 2, nullptr, 0, nullptr, nullptr, 0, nullptr, nullptr, cnt, nullptr) == RML_OK);
+}
+
 static void phase_b(rml_ctx* ctx) {
     const int X = 22, Y = 31, Z = 176, C = 3;
     const int64_t B = 9000, M = 300;                   // two pipeline chunks (8192 + 808)
@@ -299,6 +345,7 @@ int main(int argc, char** argv) {
         if (need_device) { fprintf(stderr, "a device was required\n"); ++g_fail; }
     } else {
         phase_b_gram_arguments(ctx);
+        phase_b_smo_arguments(ctx);
         phase_b(ctx);
         CHECK(rml_ctx_destroy(ctx) == RML_OK);
     }
