@@ -466,7 +466,10 @@ int rml_dnn_trunk(rml_ctx* ctx, const void* xz, const void* yz, const void* xy, 
  * pixel, channel) -- element (branch, pixel, channel) of sample b at block kb = (branch * P + pixel) / 2, offset (pixel & 1) * 32 +
  * channel, P = (H/4) * (W/4) even.  A 128-sample tile of one K-step is then 16 KB of contiguous memory (row-major rows put those
  * 128 pieces of 128 B 76.8 KB apart: every piece its own DRAM page, 3.3-3.6 TB/s for every GEMM that was tried on it).
- * RML_ERR_UNSUPPORTED for planes the register-resident trunk kernel does not take. */
+ * RML_ERR_UNSUPPORTED for planes the register-resident trunk kernel does not take.
+ * rml_dnn_trunk_kblock_supported (host only, no device needed): H % 4 == 0, W % 8 == 0, P even and that kernel's LDS layout -- eight
+ * wave-private bf16 planes with a 4-pixel border + 36 KB of weights -- within the 160 KB; the 80 x 80 of dnn.py:33 does. */
+int rml_dnn_trunk_kblock_supported(int H, int W);
 int rml_dnn_trunk_kblock(rml_ctx* ctx, const void* xz, const void* yz, const void* xy, int in_bf16, int64_t B, int H, int W,
                          const float* w1, const float* b1, const uint16_t* w2t, const float* b2,
                          uint16_t* feat, void* stream);

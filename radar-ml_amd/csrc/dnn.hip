@@ -619,6 +619,12 @@ int launch_trunk_rf(const TrunkArgs& a, int num_cu, hipStream_t stream) {
 
 }  // namespace
 
+// host only: the planes launch_trunk_rf takes in the K-block layout (trunk_entry's checks for bf16 planes + RfLayout within the LDS)
+extern "C" int rml_dnn_trunk_kblock_supported(int H, int W) {
+    if (H <= 0 || W <= 0 || H % 4 || W % 8 || ((H / 4) * (W / 4)) % 2) return 0;
+    return RfLayout(H, W).total <= 160 * 1024;
+}
+
 namespace {
 template <bool INBF>
 int dispatch_trunk(const TrunkArgs& a, int num_cu, hipStream_t st) {

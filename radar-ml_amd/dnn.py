@@ -10,21 +10,22 @@ through PyTorch, which the north star allows for these layers.
 """
 import numpy as np
 
+from . import dnn_guard
+from .dnn_guard import LABEL_GUARD, LABEL_GUARD_X3, LABEL_GUARD_X6, LABEL_GUARD_F32      # noqa: F401  (the margin guard's levels)
 from .nn_common import make_same_conv, to_nchw, flatten_nhwc, tf_same_pad
 
 RESCALE = (80, 80)          # dnn.py:33
-# Margin guard of predict_volumes / predict: rows whose top-2 probability gap is below this are re-scored in float64.  The bf16
-# chain moves a probability by <= 3.4e-3 on trained weights (larger logits) and <= 4.8e-4 on random-init ones (measured against
-# the float64 restatement, tests/test_nn_gpu.py DNN_BF16_PROBA_TOL / _RANDOM_INIT_TOL), i.e. a gap by <= 6.8e-3: 3 x that.
-LABEL_GUARD = 2e-2
-# Second level: the float32-class trunk (csrc/dnn_x3.hip, bf16 operand pairs) + float32 dense layers on exact inputs; rows whose gap
-# there is below this go on.  Measured |x3 - float64|: 7.0e-6 on the trained bench model's candidate rows, 5e-7 at random init
-# (tools/guard_profile.py; tests/test_nn_gpu.py::test_x3_trunk_is_float32_class asserts 4 x its own worst under this): 7 x that.
-LABEL_GUARD_X3 = 5e-5
-# Third level: the same kernel with three bf16 parts per operand ("x6": float32-class in the strict sense; measured 9.6e-7 / 1.1e-7
-# on the same rows) on the rows whose x3 gap is below LABEL_GUARD_X3; rows whose gap there is below this go to float64.
-LABEL_GUARD_X6 = 1e-5
-LABEL_GUARD_F32 = LABEL_GUARD_X3        # (the name of rounds 1-5, when this stage ran PyTorch's float32 layers)
+
+
+def rescore_route(n_rows, N, fused, host):
+    """Which pass of ``Classifier.rescore_exact`` scores ``n_rows`` (None: all) of ``N`` frames.  ``fused``: precision, mode, planes
+    and volumes fit rml_dnn_exact_features; ``host``: host volumes.  Sparse: fewer than half of the frames are wanted."""
+    sparse = n_rows is not None and 2 * n_rows < N
+    if sparse and fused and not host:
+        return "fused_gather"       # one library call per pass: gather, projection, resize, trunk
+    if n_rows is None:
+        return "all"
+    return "gather" if sparse else "dense_blocks"
 
 
 def define_classifier(xz_shape=(80, 80, 1), yz_shape=(80, 80, 1), xy_shape=(80, 80, 1), n_classes=3,
@@ -60,6 +61,8 @@ class Classifier(_module_base()):
         self.fc2 = nn.Linear(64, 64)
         self.fc3 = nn.Linear(64, n_classes)
         self.drop = nn.Dropout(0.5)
+        self._packs = {}                            # name -> (key of the parameters it was made from, value): _cached
+        self._margin = dnn_guard.MarginGuard()
         # Keras defaults: glorot_uniform kernels, zero biases
         for mod in self.modules():
             if isinstance(mod, (nn.Conv2d, nn.Linear)):
@@ -162,24 +165,69 @@ class Classifier(_module_base()):
         pt = np.clip(p[np.arange(len(yi)), yi], 1e-7, 1.0 - 1e-7)
         return float(-np.log(pt).mean()), float((p.argmax(axis=1) == yi).mean())
 
-    # ---- fused HIP trunk -------------------------------------------------------------------------------
-    def _packed_trunk_weights(self):
-        """conv weights in the layout of rml_dnn_trunk, cached and re-packed whenever a convolution parameter was written
-        (optimizer step, load_state_dict, .to(): the tensors' version counters / storage change)."""
+    # ---- weight packs: values derived from parameters, rebuilt when one of them was written ------------------
+    def _cached(self, name, params, make):
+        """``make()``, kept under ``name`` until one of ``params`` is written (optimizer step, load_state_dict, .to(): the tensors'
+        version counters / storage change -- dnn_guard.weights_key)."""
+        key = dnn_guard.weights_key(params)
+        hit = self._packs.get(name)
+        if hit is None or hit[0] != key:
+            hit = self._packs[name] = (key, make())
+        return hit[1]
+
+    def _conv_packs(self):
+        """The convolution weights in the layout of the trunk kernels: w1 [3][64][9], b1 [3][64], w2 [3][32][576] with k = (ky*3+kx)*64
+        + cin, b2 [3][32], float32 -- ``["x3"]`` for rml_dnn_trunk_x3 as they are, ``["bf16"]`` for rml_dnn_trunk with w2 in bf16."""
         import torch
-        key = tuple((p._version, p.data_ptr()) for br in self.branches for cv in (br[0].conv, br[1].conv) for p in (cv.weight, cv.bias))
-        pk = getattr(self, "_trunk_pack", None)
-        if pk is None or getattr(self, "_trunk_pack_key", None) != key:
-            self._trunk_pack_key = key
+
+        def make():
             w1 = torch.stack([br[0].conv.weight.detach().float().reshape(64, 9) for br in self.branches]).contiguous()
             b1 = torch.stack([br[0].conv.bias.detach().float() for br in self.branches]).contiguous()
-            # (32, 64, 3, 3) -> (32, ky, kx, cin) -> (32, 576): k = (ky*3+kx)*64 + cin
-            w2t = torch.stack([br[1].conv.weight.detach().float().permute(0, 2, 3, 1).reshape(32, 576)
-                               for br in self.branches]).to(torch.bfloat16).contiguous()
+            # (32, 64, 3, 3) -> (32, ky, kx, cin) -> (32, 576)
+            w2 = torch.stack([br[1].conv.weight.detach().float().permute(0, 2, 3, 1).reshape(32, 576) for br in self.branches]).contiguous()
             b2 = torch.stack([br[1].conv.bias.detach().float() for br in self.branches]).contiguous()
-            pk = self._trunk_pack = (w1, b1, w2t, b2)
-        return pk
+            return {"x3": (w1, b1, w2, b2), "bf16": (w1, b1, w2.to(torch.bfloat16).contiguous(), b2)}
+        return self._cached("conv", [p for br in self.branches for cv in (br[0].conv, br[1].conv) for p in (cv.weight, cv.bias)], make)
 
+    def _dense_packs(self):
+        """The dense kernels in the layouts the tails use.  ``["bf16"]``: (kernel, bias) copies per layer for the matrix cores (autocast
+        re-casts the three weight matrices on every call: six element-wise launches of ~6 us per batch in the round-3 profile);
+        ``["f32"]``: the float32 operands of csrc/dense.hip's small layers (b1, second kernel transposed to (in, out), b2, w3, b3);
+        ``["w1_kblock"]``: the first bf16 kernel with its K axis in the K-block order (branch, pixel, channel) instead of Keras'
+        (pixel, branch, channel), blocked like the features: [K/64][out][64] (None unless K % 192 == 0)."""
+        import torch
+        fcs = (self.fc1, self.fc2, self.fc3)
+
+        def make():
+            bf16 = [(fc.weight.detach().to(torch.bfloat16).contiguous(), fc.bias.detach().to(torch.bfloat16).contiguous()) for fc in fcs]
+            f32 = (self.fc1.bias.detach().float().contiguous(), self.fc2.weight.detach().float().t().contiguous(),
+                   self.fc2.bias.detach().float().contiguous(), self.fc3.weight.detach().float().contiguous(),
+                   self.fc3.bias.detach().float().contiguous())
+            w1 = bf16[0][0]
+            K = int(w1.shape[1])
+            kblock = (w1.view(w1.shape[0], K // 96, 3, 32).permute(0, 2, 1, 3).reshape(w1.shape[0], K // 64, 64)
+                      .permute(1, 0, 2).contiguous() if K % 192 == 0 else None)
+            return {"bf16": bf16, "f32": f32, "w1_kblock": kblock}
+        return self._cached("dense", [p for fc in fcs for p in (fc.weight, fc.bias)], make)
+
+    def _tail_weights(self):
+        return self._dense_packs()["bf16"]
+
+    @property
+    def _tail_f32(self):
+        return self._dense_packs()["f32"]
+
+    def _exact_weights(self, dtype):
+        """float32 / float64 copies of every parameter in the layout of forward_exact, cached until one is written."""
+        made = self._cached("exact", self.parameters(), dict)
+        if dtype not in made:
+            made[dtype] = {
+                "conv": [[(cv.conv.weight.detach().to(dtype).reshape(cv.conv.weight.shape[0], -1).contiguous(), cv.conv.bias.detach().to(dtype),
+                           int(cv.conv.weight.shape[2]), int(cv.conv.weight.shape[3])) for cv in br] for br in self.branches],
+                "fc": [(fc.weight.detach().to(dtype), fc.bias.detach().to(dtype)) for fc in (self.fc1, self.fc2, self.fc3)]}
+        return made[dtype]
+
+    # ---- fused HIP trunk + dense tail: the bf16 chain ----------------------------------------------------
     def features_fused(self, xz, yz, xy, layout="nhwc"):
         """The conv features (bf16) of the three branches from the fused HIP kernel (csrc/dnn.hip); inputs (N,H,W) or
         (N,1,H,W) CUDA tensors, float32 or bfloat16 (same results).  ``layout="nhwc"``: (N, 38 400) rows in Keras' Flatten
@@ -193,7 +241,7 @@ class Classifier(_module_base()):
         xs = [(x if bf else x.float()).contiguous() for x in xs]
         n, H, W = xs[0].shape
         dev = xs[0].device
-        w1, b1, w2t, b2 = self._packed_trunk_weights()
+        w1, b1, w2t, b2 = self._conv_packs()["bf16"]
         K = (H // 4) * (W // 4) * 96
         kb = layout == "kblock"
         if not kb and layout != "nhwc":
@@ -206,15 +254,17 @@ class Classifier(_module_base()):
                           _lib.stream_ptr(dev)), "rml_dnn_trunk")
         return feat
 
+    def _small_tail_shape(self):
+        """the reference's 64 / 64 / n dense layers, as csrc/dense.hip's finishing kernels take them"""
+        return tuple(self.fc2.weight.shape) == (64, 64) and self.fc1.weight.shape[0] == 64 and self.n_classes <= 16
+
     def kblock_supported(self, H, W):
         """True when trunk and dense tail can hand the features over in the K-block layout: planes the register-resident trunk
-        kernel takes (the 80 x 80 of dnn.py does), an even number of output pixels, the reference's 64 / 64 / n dense layers."""
-        P = (H // 4) * (W // 4)
-        # k_dnn_trunk_rf's LDS layout (csrc/dnn.hip RfLayout): eight wave-private bf16 planes with a 4-pixel border + 36 KB of weights
-        rf_lds = 8 * (((H + 4) * (W + 4) * 2 + 15) // 16 * 16) + 36 * 1024 + 160
-        return (H % 4 == 0 and W % 8 == 0 and P % 2 == 0 and rf_lds <= 160 * 1024 and len(self.branches) == 3
-                and tuple(self.fc2.weight.shape) == (64, 64) and self.fc1.weight.shape[0] == 64 and self.n_classes <= 16
-                and self.fc1.weight.shape[1] == P * 96)
+        kernel takes (rml_dnn_trunk_kblock_supported answers from the kernel's own LDS layout; the 80 x 80 of dnn.py does), the
+        reference's three branches and 64 / 64 / n dense layers on those planes."""
+        from . import _lib
+        return (len(self.branches) == 3 and self._small_tail_shape() and self.fc1.weight.shape[1] == (H // 4) * (W // 4) * 96
+                and bool(_lib.load().rml_dnn_trunk_kblock_supported(int(H), int(W))))
 
     def forward_fused(self, xz, yz, xy):
         """Class probabilities with the fused HIP trunk + the fused dense tail (csrc/dense.hip)."""
@@ -223,26 +273,36 @@ class Classifier(_module_base()):
             return self.dense_tail(self.features_fused(xz, yz, xy, layout="kblock"), kblock=True)
         return self.dense_tail(self.features_fused(xz, yz, xy))
 
-    def _tail_weights(self):
-        """The dense kernels in the layouts the tail uses, cached until a parameter is written: bf16 copies for the matrix cores
-        (autocast re-casts the three weight matrices on every call: six element-wise launches of ~6 us per batch in the round-3
-        profile) and the float32 operands of rml_dnn_dense_tail (second kernel transposed to (in, out), biases)."""
+    def _hip_tail(self, name, fv, lead, n, K, w1, small, ws_bytes):
+        """csrc/dense.hip's tail ``name`` (rml_dnn_dense_tail / _f32) on the features ``fv``: ``lead`` are its arguments between
+        the features and n, ``w1`` the first kernel as it takes it, ``small`` = _dense_packs()["f32"], ``ws_bytes(ctx)`` its
+        workspace size."""
         import torch
-        key = tuple((p._version, p.data_ptr()) for fc in (self.fc1, self.fc2, self.fc3) for p in (fc.weight, fc.bias))
-        if getattr(self, "_tail_pack_key", None) != key:
-            self._tail_pack_key = key
-            self._tail_pack = [(fc.weight.detach().to(torch.bfloat16).contiguous(), fc.bias.detach().to(torch.bfloat16).contiguous())
-                               for fc in (self.fc1, self.fc2, self.fc3)]
-            self._tail_f32 = (self.fc1.bias.detach().float().contiguous(), self.fc2.weight.detach().float().t().contiguous(),
-                              self.fc2.bias.detach().float().contiguous(), self.fc3.weight.detach().float().contiguous(),
-                              self.fc3.bias.detach().float().contiguous())
-            # the first kernel with its K axis in the K-block order (branch, pixel, channel) instead of Keras' (pixel, branch, channel)
-            w1 = self._tail_pack[0][0]
-            K = int(w1.shape[1])
-            # ... and blocked like the features: [K/64][out][64]
-            self._w1_kblock = (w1.view(w1.shape[0], K // 96, 3, 32).permute(0, 2, 1, 3).reshape(w1.shape[0], K // 64, 64)
-                               .permute(1, 0, 2).contiguous() if K % 192 == 0 else None)
-        return self._tail_pack
+        from . import _lib
+        dev = fv.device
+        out = torch.empty((n, self.n_classes), dtype=torch.float32, device=dev)
+        if n == 0:
+            return out
+        bb1, w2t, bb2, w3f, bb3 = small
+        ctx = _lib.context(dev)
+        nbytes = int(ws_bytes(ctx))
+        ws = torch.empty((nbytes // 4,), dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(getattr(_lib.load(), name)(ctx, _lib.ptr(fv), *lead, n, K, _lib.ptr(w1), _lib.ptr(bb1), _lib.ptr(w2t), _lib.ptr(bb2),
+                                                  _lib.ptr(w3f), _lib.ptr(bb3), self.n_classes, _lib.ptr(ws), nbytes, _lib.ptr(out),
+                                                  _lib.stream_ptr(dev)), name)
+        return out
+
+    @staticmethod
+    def _torch_tail(fv, layers):
+        """Dense relu, Dense relu, Dense softmax through PyTorch (hipBLASLt), float32 accumulation and softmax: the tails' form for
+        the shapes and devices csrc/dense.hip does not take."""
+        import torch
+        import torch.nn.functional as F
+        (w1, b1), (w2, b2), (w3, b3) = layers
+        h = F.relu(F.linear(fv, w1, b1))
+        h = F.relu(F.linear(h, w2, b2))
+        return torch.softmax(F.linear(h, w3, b3).float(), dim=-1)
 
     def dense_tail(self, fv, fused=True, kblock=False):
         """Dense 64 relu, Dense 64 relu, Dense n softmax (dnn.py:78-88) on bf16 feature rows.  ``fused`` (default, CUDA bf16 rows
@@ -252,40 +312,56 @@ class Classifier(_module_base()):
         without its per-call casts.  ``kblock=True``: ``fv`` is the (K/64, N, 64) tensor of ``features_fused(layout="kblock")`` --
         a 128-sample tile of a K-step is then 16 KB of contiguous memory instead of 128 pieces 76.8 KB apart."""
         import torch
-        import torch.nn.functional as F
-        (w1, b1), (w2, b2), (w3, b3) = self._tail_weights()
+        from . import _lib
+        pk = self._dense_packs()
+        w1 = pk["bf16"][0][0]
         if kblock:
-            # (K/64, N, 64) features of features_fused(layout="kblock")
+            w1 = pk["w1_kblock"]
             if not (fused and fv.is_cuda and fv.dtype == torch.bfloat16 and fv.ndim == 3 and fv.shape[2] == 64 and fv.is_contiguous()
-                    and self._w1_kblock is not None and int(fv.shape[0]) == int(self._w1_kblock.shape[0])):
+                    and w1 is not None and int(fv.shape[0]) == int(w1.shape[0])):
                 raise ValueError("dense_tail(kblock=True): contiguous CUDA bfloat16 (K/64, N, 64) features expected")
             K, n, ld = int(fv.shape[0]) * 64, int(fv.shape[1]), 0
-            w1 = self._w1_kblock
         else:
             K, n, ld = (int(fv.shape[1]), int(fv.shape[0]), int(fv.stride(0))) if fv.ndim == 2 else (0, 0, 0)
         if kblock or (fused and fv.is_cuda and fv.dtype == torch.bfloat16 and fv.ndim == 2 and K % 64 == 0 and fv.stride(1) == 1
-                      and fv.stride(0) % 8 == 0 and fv.data_ptr() % 16 == 0
-                      and tuple(self.fc2.weight.shape) == (64, 64) and self.fc1.weight.shape[0] == 64 and self.n_classes <= 16):
-            from . import _lib
-            lib = _lib.load()
-            dev = fv.device
-            out = torch.empty((n, self.n_classes), dtype=torch.float32, device=dev)
-            if n == 0:
-                return out
-            bb1, w2t, bb2, w3f, bb3 = self._tail_f32
-            ctx = _lib.context(dev)
-            nbytes = int(lib.rml_dnn_dense_workspace_bytes(ctx, n, K))
-            ws = torch.empty((nbytes // 4,), dtype=torch.float32, device=dev)
-            with torch.cuda.device(dev):
-                _lib.check(lib.rml_dnn_dense_tail(ctx, _lib.ptr(fv), ld, 1 if kblock else 0, n, K, _lib.ptr(w1), _lib.ptr(bb1), _lib.ptr(w2t),
-                                                  _lib.ptr(bb2), _lib.ptr(w3f), _lib.ptr(bb3), self.n_classes, _lib.ptr(ws), nbytes,
-                                                  _lib.ptr(out), _lib.stream_ptr(dev)), "rml_dnn_dense_tail")
-            return out
-        h = F.relu(F.linear(fv, w1, b1))
-        h = F.relu(F.linear(h, w2, b2))
-        lg = F.linear(h, w3, b3)
-        return torch.softmax(lg.float(), dim=-1)
+                      and fv.stride(0) % 8 == 0 and fv.data_ptr() % 16 == 0 and self._small_tail_shape()):
+            return self._hip_tail("rml_dnn_dense_tail", fv, (ld, 1 if kblock else 0), n, K, w1, pk["f32"],
+                                  lambda ctx: _lib.load().rml_dnn_dense_workspace_bytes(ctx, n, K))
+        return self._torch_tail(fv, pk["bf16"])
 
+    def _tail_float32(self, fv):
+        """Dense 64 relu, Dense 64 relu, Dense n softmax in float32 on float32 feature rows (no dropout: inference).  CUDA rows
+        (two hidden layers of 64 units, <= 16 classes, K % 4 == 0): csrc/dense.hip rml_dnn_dense_tail_f32 -- a row's result depends
+        on that row alone (fixed K splits, one fma chain each, added in order), so a row re-scored alone, inside any candidate set
+        or twice has the same bits; hipBLASLt's float32 GEMM for these shapes splits K with atomics and does not (session r6b:
+        the same call twice 1e-7 apart).  Other shapes / CPU tensors: the plain PyTorch layers."""
+        import torch
+        from . import _lib
+        layers = self._exact_weights(torch.float32)["fc"]
+        w1, w2 = layers[0][0], layers[1][0]
+        if (fv.is_cuda and fv.dtype == torch.float32 and fv.ndim == 2 and fv.stride(1) == 1 and fv.shape[1] % 4 == 0 and fv.stride(0) % 4 == 0
+                and fv.data_ptr() % 16 == 0 and tuple(w1.shape) == (64, int(fv.shape[1])) and tuple(w2.shape) == (64, 64) and self.n_classes <= 16):
+            n, K = int(fv.shape[0]), int(fv.shape[1])
+            return self._hip_tail("rml_dnn_dense_tail_f32", fv, (int(fv.stride(0)),), n, K, w1 if w1.is_contiguous() else w1.contiguous(),
+                                  self._tail_f32, lambda ctx: _lib.load().rml_dnn_dense_tail_f32_workspace_bytes(n, K))
+        return self._torch_tail(fv, layers)
+
+    def _features_timed(self, xs, trunk_events, layout="nhwc"):
+        import torch
+        if trunk_events is None:
+            return self.features_fused(*xs, layout=layout)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        fv = self.features_fused(*xs, layout=layout)
+        e1.record()
+        trunk_events.append((e0, e1, int(xs[0].shape[0])))
+        return fv
+
+    def _forward_timed(self, xs, trunk_events):
+        kb = self.kblock_supported(int(xs[0].shape[-2]), int(xs[0].shape[-1]))
+        return self.dense_tail(self._features_timed(xs, trunk_events, "kblock" if kb else "nhwc"), kblock=kb)
+
+    # ---- volumes -> probabilities --------------------------------------------------------------------------
     def predict_volumes(self, volumes, rescale=(80, 80), mode="max", batch_size=16384, overlap=False, trunk_events=None,
                         exact_resize=False, label_guard=LABEL_GUARD):
         """The whole inference path of BASELINE configs[3] on the GPU: (N,X,Y,Z) volumes (float32 or uint8) ->
@@ -297,268 +373,129 @@ class Classifier(_module_base()):
 
         ``batch_size``: frames per pass of the chain (16 384: 5.96-6.08 M frames/s against 5.83-5.85 M at 8 192 and 6.03-6.04 M at
         32 768 on one box -- fewer launch gaps and persistent-kernel tails; 2.2 GB of intermediates at the Walabot grid).
-        ``overlap`` (off): the projection of batch b+2 on a second stream beside the resize of batch b+1, the trunk (a whole CU's
-        LDS) and the dense tail (hipBLASLt: 135 KB of LDS) alone between two projection launches.  Measured in round 4 (three
-        schedules, kernel timeline in tools/exp/README.md): no gain -- beside the projection the resize kernels take 3 x as long
-        (both live on the LDS pipe and the issue ports) and the projection 1.25 x, so the pair costs what the two cost in turn:
-        4.6-4.7 against 4.7-4.8 M frames/s.  Kept as a knob.  ``trunk_events``: a list that receives one (start, stop, frames)
-        torch.cuda.Event triple per trunk launch (bench.py's in-situ roofline of k_dnn_trunk_rf).
+        ``overlap`` (off): the two-stream chain (:meth:`_chain_two_streams`; measured: no gain, kept as a knob).  ``trunk_events``:
+        a list that receives one (start, stop, frames) torch.cuda.Event triple per trunk launch (bench.py's in-situ roofline of
+        k_dnn_trunk_rf).
 
-        ``label_guard`` (default LABEL_GUARD = 2e-2; None or 0 turns it off): the margin guard (:meth:`_guard`).  The bf16 chain moves a
-        probability by up to 3.4e-3 (measured against the float64 restatement of the Keras layers, trained weights; 4.8e-4 on random-init
-        ones), so rows whose two largest probabilities are closer than ``label_guard`` -- and only those -- are scored again from
-        their volumes from exact inputs (exact projection, Pillow-bit-identical resize: :meth:`rescore_exact`): all of them at once
-        through the float32-class trunk (csrc/dnn_x3.hip, bf16 operand pairs: ~1e-5 from float64, 0.2-0.3 us per row) and, where that
-        gap is below LABEL_GUARD_X3, in float64; their probabilities are replaced.  The gap calibrates itself: it is widened to four
-        times the bf16 error seen on the re-scored rows -- an EMPIRICAL bound: ``argmax`` is the float64 label on every row inside the
-        covered gap and on every row outside it whose bf16 error is below twice the largest error seen.  Guarded outputs are not
-        batching-invariant bit for bit (a row near the gap may be re-scored under one batching and not under another; both values
-        are within the bf16 tolerance); ``label_guard=None`` results are.  ``self.last_guard`` = {"rows", "rescored",
-        "rescored_float64", "observed_error", "gap"}.
+        ``label_guard`` (default LABEL_GUARD = 2e-2; None or 0 turns it off): the margin guard (:meth:`_guard`, dnn_guard.py).  The bf16
+        chain moves a probability by up to 3.4e-3 (measured against the float64 restatement of the Keras layers, trained weights;
+        4.8e-4 on random-init ones), so rows whose two largest probabilities are closer than ``label_guard`` -- and only those -- are
+        scored again from their volumes from exact inputs (exact projection, Pillow-bit-identical resize: :meth:`rescore_exact`) and
+        replaced; the gap widens itself to four times the bf16 error seen on them -- an EMPIRICAL bound: ``argmax`` is the float64
+        label on every row inside the covered gap and on every row outside it whose bf16 error is below twice the largest error
+        seen.  Guarded outputs are not batching-invariant bit for bit (a row near the gap may be re-scored under one batching and
+        not under another; both values are within the bf16 tolerance); ``label_guard=None`` results are.  ``self.last_guard``: what
+        the guard did (the keys: dnn_guard.py).
         """
         import torch
-        from . import common, nn_common, _lib
         if not isinstance(volumes, torch.Tensor):
             volumes = torch.as_tensor(volumes)
         n = int(volumes.shape[0])
-        X, Y, Z = (int(v) for v in volumes.shape[1:])
-        if n == 0:
-            return torch.zeros((0, self.n_classes), device=volumes.device if volumes.is_cuda else next(self.parameters()).device)
         dev = volumes.device if volumes.is_cuda else next(self.parameters()).device
+        if n == 0:
+            return torch.zeros((0, self.n_classes), device=dev)
         if dev.type != "cuda":
             raise RuntimeError("predict_volumes runs on the GPU: move the model to a CUDA device (there is no CPU path)")
-        host = not volumes.is_cuda          # host volumes stay on the host: one slice per pass crosses PCIe, not the whole data set
-
-        def vol(sel):
-            v = volumes[sel.cpu() if (host and isinstance(sel, torch.Tensor)) else sel]
-            return v.to(dev, non_blocking=False) if host else v
         bs = int(min(batch_size, n))
-        nb = (n + bs - 1) // bs
-        D = common.feature_len(X, Y, Z)
-        overlap = bool(overlap) and nb > 1 and not host
+        plan = [(s0, min(n, s0 + bs)) for s0 in range(0, n, bs)]         # the passes: frames [s0, s1) each
         out = torch.empty((n, self.n_classes), dtype=torch.float32, device=dev)
         with torch.no_grad(), torch.cuda.device(dev):
-            cur = torch.cuda.current_stream(dev)
-            if not overlap:
-                # (mode "max_nan" can put NaN into the float rows: the fused float32 preprocessing multiplies out-of-window taps by
-                # zero weights, 0 * NaN, where Pillow never reads them -- those batches take the Pillow-exact resize)
-                fused = not exact_resize and mode != "max_nan" and nn_common.preprocess_supported((X, Y, Z), rescale)
-                for b in range(nb):
-                    s0, s1 = b * bs, min(n, (b + 1) * bs)
-                    if fused:
-                        xs = nn_common.preprocess_volumes(vol(slice(s0, s1)), rescale, mode=mode)
-                    else:
-                        feat = common.process_volumes(vol(slice(s0, s1)), mode=mode, scale=False)
-                        xs = nn_common.preprocess_features(feat, (X, Y, Z), rescale, out_dtype="bfloat16")
-                    out[s0:s1] = self._forward_timed(xs, trunk_events)
-                # the margin guard once per call, behind the last pass.  (Per pass on a second stream beside the next pass, with a
-                # context of its own, was measured in session r5f: no overlap -- the chain's persistent kernels hold every CU and
-                # the guard's small launches start only at kernel boundaries -- and more padded chunks: 58 % against ~35 %.)
-                return self._guard(out, label_guard, lambda idx, prec: self.rescore_exact(volumes, rescale, mode, prec, rows=idx))
-            lib = _lib.load()
-            ctx = _lib.context(dev)
-            sp = getattr(self, "_proj_stream", None)
-            if sp is None or sp.device != dev:
-                sp = self._proj_stream = torch.cuda.Stream(device=dev)
-            feats = [torch.empty((bs, D), dtype=torch.float32, device=dev) for _ in range(2)]
-            ev_proj = [torch.cuda.Event(), torch.cuda.Event()]
-            sp.wait_stream(cur)                         # the volumes (and the fresh buffers) are the caller's stream's
-            _lib.check(lib.rml_ctx_set_option(ctx, _lib.OPT_PROJECT_SHARE_CU, 1), "rml_ctx_set_option")
-            ev_trunk = [torch.cuda.Event(), torch.cuda.Event()]
-            try:
-                def project(b):
-                    k = b & 1
-                    s0, s1 = b * bs, min(n, (b + 1) * bs)
-                    with torch.cuda.stream(sp):
-                        if b >= 2:
-                            # not before the trunk of batch b-2 is done: the trunk needs a whole CU's LDS, and a projection launch
-                            # that reaches the CUs first keeps it waiting (two persistent kernels taking turns CU by CU: measured
-                            # slower than one stream).  That trunk is also behind the resizes that read this buffer.
-                            sp.wait_event(ev_trunk[k])
-                        common.process_volumes(volumes[s0:s1], mode=mode, scale=False, out=feats[k][:s1 - s0])
-                        ev_proj[k].record(sp)
-                def resize(b):
-                    k = b & 1
-                    s0, s1 = b * bs, min(n, (b + 1) * bs)
-                    cur.wait_event(ev_proj[k])
-                    return nn_common.preprocess_features(feats[k][:s1 - s0], (X, Y, Z), rescale, out_dtype="bfloat16")
-                project(0)
-                if nb > 1:
-                    project(1)
-                xs = resize(0)
-                for b in range(nb):
-                    k = b & 1
-                    s0, s1 = b * bs, min(n, (b + 1) * bs)
-                    if b + 1 < nb:
-                        cur.wait_event(ev_proj[(b + 1) & 1])    # the trunk could not start beside the running projection anyway
-                    fv = self._features_timed(xs, trunk_events)
-                    ev_trunk[k].record(cur)
-                    if b + 2 < nb:
-                        project(b + 2)                  # second stream: behind this trunk
-                    if b + 1 < nb:
-                        xs = resize(b + 1)              # float64 VALU work beside the streaming projection of batch b+2
-                    # the dense tail last: hipBLASLt's kernel wants 135 KB of LDS and waits for the projection to leave the CUs
-                    out[s0:s1] = self.dense_tail(fv)
-            finally:
-                _lib.check(lib.rml_ctx_set_option(ctx, _lib.OPT_PROJECT_SHARE_CU, 0), "rml_ctx_set_option")
-            cur.wait_stream(sp)
-            out = self._guard(out, label_guard, lambda idx, prec: self.rescore_exact(volumes, rescale, mode, prec, rows=idx))
-        return out
+            if overlap and len(plan) > 1 and volumes.is_cuda:
+                self._chain_two_streams(volumes, plan, out, rescale, mode, trunk_events)
+            else:
+                self._chain_serial(volumes, plan, out, rescale, mode, exact_resize, trunk_events)
+            # the margin guard once per call, behind the last pass.  (Per pass on a second stream beside the next pass, with a
+            # context of its own, was measured in session r5f: no overlap -- the chain's persistent kernels hold every CU and
+            # the guard's small launches start only at kernel boundaries -- and more padded chunks: 58 % against ~35 %.)
+            return self._guard(out, label_guard, lambda idx, prec: self.rescore_exact(volumes, rescale, mode, prec, rows=idx))
 
-    # ---- margin guard: float64 labels from a bf16 chain -------------------------------------------------
+    def _chain_serial(self, volumes, plan, out, rescale, mode, exact_resize, trunk_events):
+        """One pass after the other on the caller's stream.  Host volumes stay on the host: one slice per pass crosses PCIe, not the
+        whole data set."""
+        from . import common, nn_common
+        dims = tuple(int(v) for v in volumes.shape[1:])
+        dev = out.device
+        # (mode "max_nan" can put NaN into the float rows: the fused float32 preprocessing multiplies out-of-window taps by
+        # zero weights, 0 * NaN, where Pillow never reads them -- those batches take the Pillow-exact resize)
+        fused = not exact_resize and mode != "max_nan" and nn_common.preprocess_supported(dims, rescale)
+        for s0, s1 in plan:
+            v = volumes[s0:s1] if volumes.is_cuda else volumes[s0:s1].to(dev)
+            if fused:
+                xs = nn_common.preprocess_volumes(v, rescale, mode=mode)
+            else:
+                feat = common.process_volumes(v, mode=mode, scale=False)
+                xs = nn_common.preprocess_features(feat, dims, rescale, out_dtype="bfloat16")
+            out[s0:s1] = self._forward_timed(xs, trunk_events)
+
+    def _chain_two_streams(self, volumes, plan, out, rescale, mode, trunk_events):
+        """The ``overlap`` chain: the projection of pass b+2 on a second stream beside the resize of pass b+1, the trunk (a whole CU's
+        LDS) and the dense tail (hipBLASLt: 135 KB of LDS) alone between two projection launches.  Measured in round 4 (three
+        schedules, kernel timeline in tools/exp/README.md): no gain -- beside the projection the resize kernels take 3 x as long
+        (both live on the LDS pipe and the issue ports) and the projection 1.25 x, so the pair costs what the two cost in turn:
+        4.6-4.7 against 4.7-4.8 M frames/s."""
+        import torch
+        from . import common, nn_common, _lib
+        dims = tuple(int(v) for v in volumes.shape[1:])
+        dev, nb, bs = out.device, len(plan), plan[0][1]
+        lib, ctx = _lib.load(), _lib.context(dev)
+        cur = torch.cuda.current_stream(dev)
+        sp = getattr(self, "_proj_stream", None)
+        if sp is None or sp.device != dev:
+            sp = self._proj_stream = torch.cuda.Stream(device=dev)
+        feats = [torch.empty((bs, common.feature_len(*dims)), dtype=torch.float32, device=dev) for _ in range(2)]
+        ev_proj = [torch.cuda.Event(), torch.cuda.Event()]
+        sp.wait_stream(cur)                         # the volumes (and the fresh buffers) are the caller's stream's
+        _lib.check(lib.rml_ctx_set_option(ctx, _lib.OPT_PROJECT_SHARE_CU, 1), "rml_ctx_set_option")
+        ev_trunk = [torch.cuda.Event(), torch.cuda.Event()]
+        try:
+            def project(b):
+                k, (s0, s1) = b & 1, plan[b]
+                with torch.cuda.stream(sp):
+                    if b >= 2:
+                        # not before the trunk of batch b-2 is done: the trunk needs a whole CU's LDS, and a projection launch
+                        # that reaches the CUs first keeps it waiting (two persistent kernels taking turns CU by CU: measured
+                        # slower than one stream).  That trunk is also behind the resizes that read this buffer.
+                        sp.wait_event(ev_trunk[k])
+                    common.process_volumes(volumes[s0:s1], mode=mode, scale=False, out=feats[k][:s1 - s0])
+                    ev_proj[k].record(sp)
+
+            def resize(b):
+                k, (s0, s1) = b & 1, plan[b]
+                cur.wait_event(ev_proj[k])
+                return nn_common.preprocess_features(feats[k][:s1 - s0], dims, rescale, out_dtype="bfloat16")
+            project(0)
+            project(1)
+            xs = resize(0)
+            for b, (s0, s1) in enumerate(plan):
+                if b + 1 < nb:
+                    cur.wait_event(ev_proj[(b + 1) & 1])    # the trunk could not start beside the running projection anyway
+                fv = self._features_timed(xs, trunk_events)
+                ev_trunk[b & 1].record(cur)
+                if b + 2 < nb:
+                    project(b + 2)                  # second stream: behind this trunk
+                if b + 1 < nb:
+                    xs = resize(b + 1)              # float64 VALU work beside the streaming projection of batch b+2
+                # the dense tail last: hipBLASLt's kernel wants 135 KB of LDS and waits for the projection to leave the CUs
+                out[s0:s1] = self.dense_tail(fv)
+        finally:
+            _lib.check(lib.rml_ctx_set_option(ctx, _lib.OPT_PROJECT_SHARE_CU, 0), "rml_ctx_set_option")
+        cur.wait_stream(sp)
+
+    # ---- margin guard: float64 labels from a bf16 chain (dnn_guard.py) -----------------------------------------
+    _gaps = staticmethod(dnn_guard.top2_gaps)
+
+    @property
+    def last_guard(self):
+        """What the last guarded call did (the keys: dnn_guard.py)."""
+        return self._margin.last
+
     def _guard(self, proba, eps, rescore):
-        """Replace the rows of ``proba`` (N, C) whose top-2 gap is too small for a bf16 chain by what exact-input arithmetic gives.
-        Stage 1, ``rescore(rows, "x3")``: the float32-class trunk (csrc/dnn_x3.hip: every operand as a bf16 pair, three matrix-core
-        products per product) + float32 dense layers on exact inputs, ~1e-5 from float64, ALL candidates of a round in one pass --
-        0.2-0.3 us per row, no host round trip but the candidate count and one (error, count) read-back.  The gap calibrates itself:
-        a round's candidates are the rows below ``eps``; their re-scoring measures the bf16 chain's error; if four times that error
-        (a gap moves by at most twice a probability's error, twice again for margin) reaches past the gap covered so far, the rows in
-        between are the next round.  Stage 2: rows whose x3 gap is still below LABEL_GUARD_X3 go through ``rescore(rows, "x6")``
-        (three bf16 parts per operand: float32-class in the strict sense); stage 3: rows whose x6 gap is below LABEL_GUARD_X6
-        through ``rescore(rows, "float64")``.  The bound is EMPIRICAL: a row outside the covered gap whose bf16 error exceeds twice the largest error seen
-        on the re-scored rows keeps its bf16 label (``last_guard["covered"]`` is False when the loop gave up before the gap covered
-        four times the error).  The gap a call ends with is where the next call on the same weights starts (the same
-        rows, the same bits when the call is repeated).  ``self.last_guard`` = {"rows", "rescored", "rescored_float64", "observed_error", "gap", "rounds",
-        "covered"}."""
-        import torch
-        from . import _lib
-        self.last_guard = {"rows": int(proba.shape[0]), "rescored": 0, "rescored_float64": 0, "rounds": 0, "covered": True}
-        if not eps or proba.shape[0] == 0 or proba.shape[1] < 2:
-            return proba
-        if not (proba.is_cuda and proba.dtype == torch.float32 and proba.stride(1) == 1 and proba.shape[1] <= 16):
-            raise ValueError("_guard: a CUDA float32 (N, C <= 16) probability tensor expected")
-        lib, dev = _lib.load(), proba.device
-        N, C, ld = int(proba.shape[0]), int(proba.shape[1]), int(proba.stride(0))
-        thr, err, err3, err6, n3, n6, n64, rounds = float(eps), 0.0, 0.0, 0.0, 0, 0, 0, 0
-        # the gap the last call on these weights ended with is where this one starts: one round instead of two in the steady state
-        key = tuple((p._version, p.data_ptr()) for p in self.parameters())
-        if getattr(self, "_guard_gap_key", None) == key:
-            thr = max(thr, self._guard_gap)
-        with torch.cuda.device(dev):
-            ctx, st = _lib.context(dev), _lib.stream_ptr(dev)
-            g = torch.empty((N,), dtype=torch.float32, device=dev)
-            _lib.check(lib.rml_dnn_top2_gap(ctx, _lib.ptr(proba), ld, N, C, _lib.ptr(g), st), "rml_dnn_top2_gap")
-            stats = None
-            while True:
-                if N <= 4096:
-                    # a few rows (dnn.py:373-381 predicts ONE target per call): the gaps cross to the host in one copy and the
-                    # candidates are picked there -- compare + nonzero on the device are three launches and a synchronisation
-                    idx = np.flatnonzero(g.cpu().numpy() < thr)
-                    n = int(idx.size)
-                    cand = torch.from_numpy(idx).to(dev) if n else None
-                else:
-                    cand = (g < thr).nonzero().squeeze(1)                   # device -> host: the candidate count
-                    n = int(cand.numel())
-                if n:
-                    if stats is None:
-                        stats = torch.zeros((2,), dtype=torch.int32, device=dev)
-                    rounds += 1
-                    p3 = rescore(cand, "x3").float().contiguous()
-                    close = torch.empty((n,), dtype=torch.uint8, device=dev)
-                    stats.zero_()
-                    # rows replaced, largest |bf16 - x3| on them, the rows still near a tie, g[rows] = inf: one launch
-                    _lib.check(lib.rml_dnn_guard_apply(ctx, _lib.ptr(proba), ld, C, _lib.ptr(cand), n, _lib.ptr(p3), float(LABEL_GUARD_X3),
-                                                       _lib.ptr(g), _lib.ptr(stats), _lib.ptr(close), st), "rml_dnn_guard_apply")
-                    sh = stats.cpu()                                        # device -> host: the error seen, rows for float64
-                    err = max(err, float(sh[:1].view(torch.float32)[0]))
-                    n3 += n
-                    if int(sh[1]):
-                        # second stage: the rows still near a tie through the three-part trunk ("x6"), the same bookkeeping launch
-                        rows6 = cand[close.nonzero().squeeze(1)]
-                        p6 = rescore(rows6, "x6").float().contiguous()
-                        k6 = int(rows6.numel())
-                        close6 = torch.empty((k6,), dtype=torch.uint8, device=dev)
-                        stats.zero_()
-                        _lib.check(lib.rml_dnn_guard_apply(ctx, _lib.ptr(proba), ld, C, _lib.ptr(rows6), k6, _lib.ptr(p6), float(LABEL_GUARD_X6),
-                                                           None, _lib.ptr(stats), _lib.ptr(close6), st), "rml_dnn_guard_apply")
-                        sh = stats.cpu()
-                        err3 = max(err3, float(sh[:1].view(torch.float32)[0]))
-                        n6 += k6
-                        if int(sh[1]):
-                            sel = close6.nonzero().squeeze(1)
-                            k64, e6 = self._guard_float64(proba, rows6[sel], p6[sel], rescore)
-                            n64 += k64
-                            err6 = max(err6, e6)
-                if thr >= min(4.0 * err, 1.0):
-                    break
-                if rounds >= 4:
-                    self.last_guard["covered"] = False
-                    break
-                thr = min(8.0 * err, 1.0)
-        self.last_guard.update(rescored=n3, rescored_x6=n6, rescored_float64=n64, observed_error=err, observed_error_x3=err3,
-                               observed_error_x6=err6, gap=thr, rounds=rounds)
-        if rounds:
-            self._guard_gap_key, self._guard_gap = key, thr
-        return proba
+        """Replace the rows of ``proba`` (N, C) whose top-2 gap is below ``eps`` -- too small for a bf16 chain -- by what
+        ``rescore(rows, precision)`` gives from exact inputs: dnn_guard.MarginGuard (the policy: rounds, stages "x3" -> "x6" ->
+        "float64", the self-calibrating gap, remembered per weight version) on dnn_guard.CudaOps (csrc/guard.hip)."""
+        return self._margin.run(proba, eps, rescore, dnn_guard.CudaOps(), self.parameters())
 
-    def _guard_float64(self, proba, rows, p3, rescore, chunk=32):
-        """Last stage: ``rows`` (their x6 probabilities ``p3`` have a top-2 gap below LABEL_GUARD_X6), closest ties first, ``chunk``
-        at a time through ``rescore(rows, "float64")``; the pass stops at the first chunk boundary whose gap is at least eight times
-        the largest |x6 - float64| seen (at least 1e-6).  Returns (rows re-scored, largest error of the x6 stage seen)."""
-        import torch
-        g3 = self._gaps(p3)
-        order = torch.argsort(g3)
-        gs = g3[order].cpu()                                                 # ascending, on the host
-        rows, p3 = rows[order], p3[order]
-        n, pos, e3 = int(rows.numel()), 0, 0.0
-        while pos < n:
-            idx = rows[pos:pos + chunk]
-            p64 = self._run_padded(lambda r: rescore(r, "float64"), idx, chunk)
-            e3 = max(e3, float((p3[pos:pos + chunk].double() - p64.double()).abs().max()))
-            proba[idx] = p64.to(proba.dtype)
-            pos += int(idx.numel())
-            if pos < n and float(gs[pos]) >= max(8.0 * e3, 1e-6):
-                break
-        return pos, e3
-
-    @staticmethod
-    def _gaps(p):
-        """top-2 gap per row; a row with a non-finite probability counts as a tie"""
-        import torch
-        top2 = torch.nan_to_num(p.float(), nan=0.0, posinf=0.0, neginf=0.0).topk(2, dim=1).values
-        g = top2[:, 0] - top2[:, 1]
-        return torch.where(torch.isfinite(p.float()).all(dim=1), g, torch.zeros_like(g))
-
-    @staticmethod
-    def _run_padded(fn, idx, size):
-        """fn(rows) in launches of EXACTLY ``size`` rows (a short one padded by repeating its first row): every launch of a size has
-        the same shape whatever the count"""
-        import torch
-        outs = []
-        for s in range(0, int(idx.numel()), size):
-            sel = idx[s:s + size]
-            k = int(sel.numel())
-            if k < size:
-                sel = torch.cat([sel, sel[:1].expand(size - k)])
-            outs.append(fn(sel)[:k])
-        return torch.cat(outs)
-
-    def _exact_weights(self, dtype):
-        """float32 / float64 copies of every parameter in the layout of forward_exact, cached until one is written."""
-        key = tuple((p._version, p.data_ptr()) for p in self.parameters())
-        if getattr(self, "_exact_key", None) != key:
-            self._exact_key, self._exact = key, {}
-        if dtype not in self._exact:
-            self._exact[dtype] = {
-                "conv": [[(cv.conv.weight.detach().to(dtype).reshape(cv.conv.weight.shape[0], -1).contiguous(), cv.conv.bias.detach().to(dtype),
-                           int(cv.conv.weight.shape[2]), int(cv.conv.weight.shape[3])) for cv in br] for br in self.branches],
-                "fc": [(fc.weight.detach().to(dtype), fc.bias.detach().to(dtype)) for fc in (self.fc1, self.fc2, self.fc3)]}
-        return self._exact[dtype]
-
-    def _x3_weights(self):
-        """float32 conv weights in the layout of rml_dnn_trunk_x3 (w1 [3][64][9], b1 [3][64], w2 [3][32][576] with k = (ky*3+kx)*64 +
-        cin, b2 [3][32]), cached until a convolution parameter is written."""
-        import torch
-        key = tuple((p._version, p.data_ptr()) for br in self.branches for cv in (br[0].conv, br[1].conv) for p in (cv.weight, cv.bias))
-        if getattr(self, "_x3_key", None) != key:
-            self._x3_key = key
-            self._x3_pack = (
-                torch.stack([br[0].conv.weight.detach().float().reshape(64, 9) for br in self.branches]).contiguous(),
-                torch.stack([br[0].conv.bias.detach().float() for br in self.branches]).contiguous(),
-                torch.stack([br[1].conv.weight.detach().float().permute(0, 2, 3, 1).reshape(32, 576) for br in self.branches]).contiguous(),
-                torch.stack([br[1].conv.bias.detach().float() for br in self.branches]).contiguous())
-        return self._x3_pack
-
+    # ---- exact-input arithmetic: what the guard re-scores with -------------------------------------------------
     def x3_supported(self, H, W):
         """True when csrc/dnn_x3.hip takes (H, W) planes of this model: three branches of Conv2D(1->64) -> Conv2D(64->32), 3x3."""
         from . import _lib
@@ -576,7 +513,7 @@ class Classifier(_module_base()):
         xs = [x.reshape(x.shape[0], x.shape[-2], x.shape[-1]).float().contiguous() for x in (xz, yz, xy)]
         n, H, W = xs[0].shape
         dev = xs[0].device
-        w1, b1, w2, b2 = self._x3_weights()
+        w1, b1, w2, b2 = self._conv_packs()["x3"]
         feat = torch.empty((n, (H // 4) * (W // 4) * 96), dtype=torch.float32, device=dev)
         with torch.cuda.device(dev):
             _lib.check(lib.rml_dnn_trunk_x3(_lib.context(dev), _lib.ptr(xs[0]), _lib.ptr(xs[1]), _lib.ptr(xs[2]), n, H, W, _lib.ptr(w1),
@@ -587,9 +524,10 @@ class Classifier(_module_base()):
         """The layers of dnn.py:45-91 on the inputs' device with no single-bf16 operand anywhere, dropout inactive whatever the
         module's mode: (N,H,W) or (N,1,H,W) planes -> (N, n_classes) probabilities.
         "x3" / "x6": the float32-class HIP trunk (:meth:`features_x3`, two / three bf16 parts per operand) + the dense layers in
-        float32 (hipBLASLt) -- the margin guard's first two stages; planes it does not take fall to "float32".  "float32": the plain PyTorch layers (MIOpen float32 convolutions,
-        hipBLASLt), the reference's own arithmetic.  "float64": im2col by nine strided slices + rocBLAS matrix products (MIOpen
-        has no float64 convolution and PyTorch's fallback takes 10 ms for a handful of rows; F.unfold is as slow)."""
+        float32 (:meth:`_tail_float32`) -- the margin guard's first two stages; planes it does not take fall to "float32".
+        "float32": the plain PyTorch layers (MIOpen float32 convolutions, hipBLASLt), the reference's own arithmetic.  "float64": im2col
+        by nine strided slices + rocBLAS matrix products (MIOpen has no float64 convolution and PyTorch's fallback takes 10 ms for a
+        handful of rows; F.unfold is as slow)."""
         import torch
         import torch.nn.functional as F
         if precision not in ("x3", "x6", "float32", "float64"):
@@ -627,36 +565,9 @@ class Classifier(_module_base()):
         h = F.relu(F.linear(h, w2, b2))
         return torch.softmax(F.linear(h, w3, b3), dim=-1)
 
-    def _tail_float32(self, fv):
-        """Dense 64 relu, Dense 64 relu, Dense n softmax in float32 on float32 feature rows (no dropout: inference).  CUDA rows
-        (two hidden layers of 64 units, <= 16 classes, K % 4 == 0): csrc/dense.hip rml_dnn_dense_tail_f32 -- a row's result depends
-        on that row alone (fixed K splits, one fma chain each, added in order), so a row re-scored alone, inside any candidate set
-        or twice has the same bits; hipBLASLt's float32 GEMM for these shapes splits K with atomics and does not (session r6b:
-        the same call twice 1e-7 apart).  Other shapes / CPU tensors: the plain PyTorch layers."""
-        import torch
-        import torch.nn.functional as F
-        (w1, b1), (w2, b2), (w3, b3) = self._exact_weights(torch.float32)["fc"]
-        if (fv.is_cuda and fv.dtype == torch.float32 and fv.ndim == 2 and fv.stride(1) == 1 and fv.shape[1] % 4 == 0 and fv.stride(0) % 4 == 0
-                and fv.data_ptr() % 16 == 0 and tuple(w1.shape) == (64, int(fv.shape[1])) and tuple(w2.shape) == (64, 64) and self.n_classes <= 16):
-            from . import _lib
-            lib = _lib.load()
-            dev, n, K = fv.device, int(fv.shape[0]), int(fv.shape[1])
-            out = torch.empty((n, self.n_classes), dtype=torch.float32, device=dev)
-            if n == 0:
-                return out
-            self._tail_weights()
-            bb1, w2t, bb2, w3f, bb3 = self._tail_f32
-            nbytes = int(lib.rml_dnn_dense_tail_f32_workspace_bytes(n, K))
-            ws = torch.empty((nbytes // 4,), dtype=torch.float32, device=dev)
-            w1c = w1 if w1.is_contiguous() else w1.contiguous()
-            with torch.cuda.device(dev):
-                _lib.check(lib.rml_dnn_dense_tail_f32(_lib.context(dev), _lib.ptr(fv), int(fv.stride(0)), n, K, _lib.ptr(w1c), _lib.ptr(bb1),
-                                                      _lib.ptr(w2t), _lib.ptr(bb2), _lib.ptr(w3f), _lib.ptr(bb3), self.n_classes, _lib.ptr(ws),
-                                                      nbytes, _lib.ptr(out), _lib.stream_ptr(dev)), "rml_dnn_dense_tail_f32")
-            return out
-        h = F.relu(F.linear(fv, w1, b1))
-        h = F.relu(F.linear(h, w2, b2))
-        return torch.softmax(F.linear(h, w3, b3), dim=-1)
+    def forward_float64(self, xz, yz, xy):
+        """:meth:`forward_exact` in float64: what the oracle's NumPy restatement computes, to ~1e-16."""
+        return self.forward_exact(xz, yz, xy, "float64")
 
     def exact_features(self, volumes, rows=None, rescale=(80, 80), mode="max", parts=2):
         """CUDA volumes (float32 or uint8) -> float32-class conv features of frames ``rows`` (an int64 CUDA index tensor; None:
@@ -669,7 +580,7 @@ class Classifier(_module_base()):
         X, Y, Z = (int(t) for t in v.shape[1:])
         n = int(rows.numel()) if rows is not None else int(v.shape[0])
         oh, ow = int(rescale[1]), int(rescale[0])
-        w1, b1, w2, b2 = self._x3_weights()
+        w1, b1, w2, b2 = self._conv_packs()["x3"]
         feat = torch.empty((n, (oh // 4) * (ow // 4) * 96), dtype=torch.float32, device=dev)
         if n == 0:
             return feat
@@ -683,12 +594,11 @@ class Classifier(_module_base()):
                                                   _lib.ptr(feat), _lib.stream_ptr(dev)), "rml_dnn_exact_features")
         return feat
 
-    def forward_float64(self, xz, yz, xy):
-        """:meth:`forward_exact` in float64: what the oracle's NumPy restatement computes, to ~1e-16."""
-        return self.forward_exact(xz, yz, xy, "float64")
-
     # frames per pass of rescore_exact: the gathered volumes, their float rows, three float32 planes and 150 KB of float32 features each
     RESCORE_BYTES = 2 << 30
+    # frames per block of its dense route (nothing is gathered there: a pass is bounded by its intermediates -- 270 KB per frame --
+    # not by RESCORE_BYTES of volumes)
+    RESCORE_BLOCK = 16384
 
     def rescore_exact(self, volumes, rescale=(80, 80), mode="max", precision="float64", rows=None):
         """(n,X,Y,Z) volumes -> (n, n_classes) probabilities through the reference's chain without a rounding the reference does
@@ -696,14 +606,14 @@ class Classifier(_module_base()):
         Pillow stores them (csrc/resize.hip, bit-identical), then the layers in ``precision`` (:meth:`forward_exact`: "x3",
         "float32" -- the reference's own arithmetic, dnn.py runs Keras in float32 -- or "float64", the oracle's).  ``rows``: an index
         tensor -- score ``volumes[rows]`` (in that order), a pass of at most RESCORE_BYTES of volumes at a time.  A sparse ``rows``
-        gathers its frames; when at least half of the frames are wanted the passes project whole contiguous blocks of frames
-        instead (no 480 KB-per-frame gather) and pick the 40 KB feature rows."""
+        gathers its frames (:func:`rescore_route`: in one library call per pass where that takes them); when at least half of the
+        frames are wanted the passes project whole contiguous blocks of frames instead (no 480 KB-per-frame gather) and pick the
+        40 KB feature rows."""
         import torch
         from . import common, nn_common
         N = int(volumes.shape[0])
-        X, Y, Z = (int(v) for v in volumes.shape[1:])
-        per = max(1, X * Y * Z * volumes.element_size())
-        step = max(64, min(16384, self.RESCORE_BYTES // per))
+        dims = tuple(int(v) for v in volumes.shape[1:])
+        step = max(64, min(16384, self.RESCORE_BYTES // max(1, dims[0] * dims[1] * dims[2] * volumes.element_size())))
         host = not volumes.is_cuda
         dev = next(self.parameters()).device
 
@@ -713,54 +623,45 @@ class Classifier(_module_base()):
             feat = common.process_volumes(v, mode=mode, scale=False)
             if pick is not None:
                 feat = feat[pick]
-            xs = nn_common.preprocess_features(feat, (X, Y, Z), rescale, out_dtype="float32")
+            xs = nn_common.preprocess_features(feat, dims, rescale, out_dtype="float32")
             return self.forward_exact(*xs, precision=precision)
 
         with torch.no_grad():
             fused = (precision in ("x3", "x6") and not host and mode != "slice" and self.x3_supported(int(rescale[1]), int(rescale[0]))
                      and volumes.dtype in (torch.float32, torch.uint8) and volumes.is_contiguous())
-            if fused and rows is not None and 2 * int(rows.numel()) < N:
-                # the sparse case on the device: one library call per pass (gather, projection, resize, trunk) + the float32 tail
-                n = int(rows.numel())
+            route = rescore_route(None if rows is None else int(rows.numel()), N, fused, host)
+            if route == "dense_blocks":
+                return self._rescore_dense_blocks(volumes, rows, score)
+            if route == "fused_gather":
                 outs = [self._tail_float32(self.exact_features(volumes, rows[s:s + step], rescale, mode, 3 if precision == "x6" else 2))
-                        for s in range(0, n, step)]
-            elif rows is None:
+                        for s in range(0, int(rows.numel()), step)]
+            elif route == "all":
                 outs = [score(volumes[s:s + step]) for s in range(0, N, step)]
-            elif 2 * int(rows.numel()) >= N:
-                # (nothing is gathered here: a pass is bounded by its intermediates -- 270 KB per frame -- not by RESCORE_BYTES of volumes)
-                srt, order = torch.sort(rows)
-                dstep = 16384
-                cuts = torch.searchsorted(srt, torch.arange(0, N + dstep, dstep, device=srt.device, dtype=srt.dtype)).cpu().tolist()
-                outs = []
-                for i, s in enumerate(range(0, N, dstep)):
-                    if cuts[i + 1] > cuts[i]:
-                        outs.append(score(volumes[s:s + dstep], (srt[cuts[i]:cuts[i + 1]] - s).to(dev)))
-                res = torch.empty_like(torch.cat(outs))
-                res[order.to(dev)] = torch.cat(outs)
-                return res
             else:
-                n = int(rows.numel())
-                outs = []
-                for s in range(0, n, step):
-                    sel = rows[s:s + step]
-                    outs.append(score(volumes[sel.cpu() if host else sel]))
+                outs = self._rescore_gather(volumes, rows, step, score)
         return torch.cat(outs) if len(outs) != 1 else outs[0]
 
-    def _features_timed(self, xs, trunk_events, layout="nhwc"):
+    @staticmethod
+    def _rescore_gather(volumes, rows, step, score):
+        """the sparse route for host volumes and for what the library call does not take: gather ``step`` frames, score them"""
+        host = not volumes.is_cuda
+        return [score(volumes[rows[s:s + step].cpu() if host else rows[s:s + step]]) for s in range(0, int(rows.numel()), step)]
+
+    def _rescore_dense_blocks(self, volumes, rows, score):
+        """the dense route: every block of RESCORE_BLOCK contiguous frames that holds a wanted frame is projected whole, the wanted
+        feature rows picked (in ascending order) and their probabilities put back in the order of ``rows``"""
         import torch
-        if trunk_events is None:
-            return self.features_fused(*xs, layout=layout)
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        fv = self.features_fused(*xs, layout=layout)
-        e1.record()
-        trunk_events.append((e0, e1, int(xs[0].shape[0])))
-        return fv
+        N, blk, dev = int(volumes.shape[0]), self.RESCORE_BLOCK, next(self.parameters()).device
+        srt, order = torch.sort(rows)
+        cuts = torch.searchsorted(srt, torch.arange(0, N + blk, blk, device=srt.device, dtype=srt.dtype)).cpu().tolist()
+        outs = [score(volumes[s:s + blk], (srt[cuts[i]:cuts[i + 1]] - s).to(dev))
+                for i, s in enumerate(range(0, N, blk)) if cuts[i + 1] > cuts[i]]
+        got = torch.cat(outs)
+        res = torch.empty_like(got)
+        res[order.to(dev)] = got
+        return res
 
-    def _forward_timed(self, xs, trunk_events):
-        kb = self.kblock_supported(int(xs[0].shape[-2]), int(xs[0].shape[-1]))
-        return self.dense_tail(self._features_timed(xs, trunk_events, "kblock" if kb else "nhwc"), kblock=kb)
-
+    # ---- Keras surface -----------------------------------------------------------------------------------------
     def predict(self, inputs, batch_size=8192, autocast_dtype="bfloat16", label_guard=LABEL_GUARD, fused=None):
         """Keras ``model.predict([xz, yz, xy])``: numpy (N,H,W,1) inputs -> (N, n_classes) float32 numpy.  Under autocast on the
         GPU the margin guard of :meth:`predict_volumes` applies: rows whose top-2 gap is below ``label_guard`` are scored again
@@ -779,17 +680,18 @@ class Classifier(_module_base()):
             for s in range(0, n, batch_size):
                 xs = [to_nchw(a[s:s + batch_size], dev) for a in inputs]
                 H, W = int(xs[0].shape[-2]), int(xs[0].shape[-1])
+                reduced = dt is not None and dev.type == "cuda"            # a reduced-precision chain: guarded
                 use_fused = (fused if fused is not None else True) and dt is torch.bfloat16 and dev.type == "cuda" \
                     and all(tuple(x.shape[-2:]) == (H, W) and x.shape[1] == 1 for x in xs) and self.kblock_supported(H, W) and self.x3_supported(H, W)
                 if use_fused:
                     p = self.forward_fused(*xs)
-                    p = self._guard(p.float(), label_guard, lambda idx, prec: self.forward_exact(*[x[idx] for x in xs], precision=prec))
-                elif dt is not None and dev.type == "cuda":
+                elif reduced:
                     with torch.autocast("cuda", dtype=dt):
                         p = self(*xs)
-                    p = self._guard(p.float(), label_guard, lambda idx, prec: self.forward_exact(*[x[idx] for x in xs], precision=prec))
                 else:
                     p = self(*xs)
+                if reduced:
+                    p = self._guard(p.float(), label_guard, lambda idx, prec: self.forward_exact(*[x[idx] for x in xs], precision=prec))
                 outs.append(p.float().cpu())
         self.train(was)
         return torch.cat(outs).numpy() if outs else np.zeros((0, self.n_classes), np.float32)

@@ -59,6 +59,7 @@ static void phase_a_arguments() {
         int v = 0;
         CHECK(rml_ctx_get_option(nullptr, RML_OPT_CHUNK, &v) < 0 && rml_ctx_reserve_workspace(nullptr, 1 << 20) < 0 && rml_ctx_workspace_bytes(nullptr) == 0);
         CHECK(rml_dnn_trunk_x3_supported(80, 80) == 1 && rml_dnn_trunk_x3_supported(128, 128) == 0 && rml_dnn_trunk_x3_supported(81, 80) == 0);
+        CHECK(rml_dnn_trunk_kblock_supported(80, 80) == 1 && rml_dnn_trunk_kblock_supported(96, 80) == 0 && rml_dnn_trunk_kblock_supported(80, 84) == 0);
         CHECK(rml_dnn_trunk_x3(nullptr, &f, &f, &f, 1, 80, 80, &f, &f, &f, &f, 2, &f, nullptr) < 0);
         CHECK(rml_dnn_exact_features_scratch_bytes(RML_VOL_F32, 10, 22, 31, 176, 80, 80, 1) > 10 * 22 * 31 * 176 * 4);
         CHECK(rml_dnn_exact_features(nullptr, &f, RML_VOL_F32, nullptr, 1, 2, 2, 4, RML_MODE_MAX, 80, 80, &f, &f, &f, &f, 2, &f, 1, &f, nullptr) < 0);
