@@ -394,6 +394,23 @@ int rml_smo_score(rml_ctx* ctx, const double* gram, int64_t N, int64_t ld, int64
                   const rml_smo_fit* fits, int64_t n_fits, const int32_t* test_rows, const int32_t* test_y,
                   int64_t n_test_total, double* dec, int32_t* labels, int32_t* correct, void* stream);
 
+/* ---- the host-side steps of SVC(probability=True).fit -------------------------------------------------------------------
+ * libsvm's svm_train with probability = 1 runs, per class pair, svm_binary_svc_probability (scikit-learn 1.7.2,
+ * sklearn/svm/src/libsvm/svm.cpp:2107-2203) before the pair's own dual: the pair's rows shuffled, five folds of sub-duals
+ * (rml_smo_solve / rml_smo_score take them as ordinary problems), and sigmoid_train on the held-out decision values.  The
+ * two functions below are the steps around those duals.  They use no device and no context, and are thread-safe.
+ * rml_libsvm_shuffle: perm (HOST, l int32) = the Fisher-Yates pass of svm.cpp:2117-2122 over 0 .. l-1, drawn from a
+ * std::mt19937 freshly seeded with `seed` through the Lemire post-processor of sklearn/svm/src/newrand/newrand.h:21-53.
+ * (The generator IS freshly seeded for every pair: each inner svm_train re-seeds it, svm.cpp:2373-2376.)
+ * rml_platt_fit: A, B = sigmoid_train(l, dec, y) of svm.cpp:1919-2030 -- the same operation order and constants, libm's exp /
+ * log, no fused multiply-add -- so that they are SVC.probA_ / probB_ bit for bit.  dec, y: HOST, l doubles (y > 0: the
+ * pair's first class).  info (may be NULL): RML_PLATT_OK, or which of libsvm's two messages it would have printed. */
+#define RML_PLATT_OK 0
+#define RML_PLATT_LINE_SEARCH_FAILED 1
+#define RML_PLATT_MAX_ITER 2
+int rml_libsvm_shuffle(uint32_t seed, int64_t l, int32_t* perm);
+int rml_platt_fit(const double* dec, const double* y, int64_t l, double* A, double* B, int* info);
+
 /* Fused front door: volumes -> projection (mode, mask fixed at load: D must match) ->
  * SVM outputs, features never returned to the caller.  Workspace is owned by the ctx and
  * grows on demand. */

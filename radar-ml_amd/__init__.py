@@ -15,7 +15,7 @@ from .svm import GpuSVC, GpuCalibratedClassifier, GpuLinearClassifier, KernelMat
 from .predict import classifier, classify_batch, calc_proj_zoom
 from .synth import synth_volumes
 from .augment import DataGenerator, augment_planes, rotation_params
-from .train import GridSearchSVC, find_best_svm_estimator
+from .train import GridSearchSVC, find_best_svm_estimator, fit_svc
 
 __all__ = [
     "RadarMLError", "ProjMask", "ProjZoom", "DerivedTarget", "RADAR_MAX", "RADAR_MIN",
@@ -23,5 +23,5 @@ __all__ = [
     "process_samples", "process_volumes", "project", "derive_targets", "feature_len",
     "GpuSVC", "GpuCalibratedClassifier", "GpuLinearClassifier", "KernelMatrix", "from_sklearn",
     "classifier", "classify_batch", "calc_proj_zoom", "synth_volumes",
-    "DataGenerator", "augment_planes", "rotation_params", "GridSearchSVC", "find_best_svm_estimator",
+    "DataGenerator", "augment_planes", "rotation_params", "GridSearchSVC", "find_best_svm_estimator", "fit_svc",
 ]

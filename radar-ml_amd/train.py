@@ -114,7 +114,8 @@ def smo_device(Kd, plan, device=None):
 def _smo(X, kernels, plan, device=None):
     """The kernel matrices of ``kernels`` of the float32 rows ``X`` (``rml_gram``, as ``_gram``) kept ON THE DEVICE, every dual of
     ``plan`` solved on them in one ``rml_smo_solve`` call and every held-out row scored in one ``rml_smo_score`` call (``smo_device``).
-    Returns ``smo_device``'s dict plus ``matrix``: a function k -> host copy of matrix k (the search fetches the winner's only).
+    Returns ``smo_device``'s dict plus ``matrix``: a function k -> host copy of matrix k (the search fetches the winner's only), and
+    ``solve``: a function plan -> ``smo_device``'s dict of another plan on the same resident matrices (the device refit).
 
     All device work of the device search goes through this function (tests replace it to run the search logic without a GPU)."""
     import torch
@@ -123,6 +124,7 @@ def _smo(X, kernels, plan, device=None):
         Kd = _gram_device(X, kernels, dev)
         out = smo_device(Kd, plan, dev)
     out["matrix"] = lambda k: Kd[k].cpu().numpy()
+    out["solve"] = lambda plan2: smo_device(Kd, plan2, dev)
     return out
 
 
@@ -178,6 +180,215 @@ def _masked_params(candidates):
     return out
 
 
+# ---- SVC.fit as one batch of duals: libsvm's svm_train with its Platt cross-validation (sk: = sklearn/svm/src/libsvm/svm.cpp) ----
+_FIT_CARRY = ("C", "class_weight", "tol", "shrinking", "max_iter", "probability", "random_state")
+_PLATT_FOLDS = 5
+
+
+def _libsvm_seed(random_state):
+    """The seed ``SVC.fit`` hands to libsvm (sklearn/svm/_base.py); ``None`` draws one from NumPy's global state, as there."""
+    from sklearn.utils import check_random_state
+    return int(check_random_state(random_state).randint(np.iinfo("i").max))
+
+
+def libsvm_shuffle(seed, l):
+    """``rml_libsvm_shuffle``: the permutation of 0 .. l-1 that svm_binary_svc_probability draws (sk:2117-2122) from the seed."""
+    perm = np.empty(int(l), dtype=np.int32)
+    _lib.check(_lib.load().rml_libsvm_shuffle(int(seed), int(l), perm.ctypes.data), "rml_libsvm_shuffle")
+    return perm
+
+
+def platt_fit(dec, y):
+    """``rml_platt_fit``: libsvm's sigmoid_train (sk:1919-2030) on decision values ``dec`` and labels ``y`` (+1 / -1).
+    Returns (A, B, info); info 0, or 1 / 2 where libsvm prints "line search fails" / "reaching maximal iterations"."""
+    import ctypes
+    dec = np.ascontiguousarray(dec, dtype=np.float64)
+    y = np.ascontiguousarray(y, dtype=np.float64)
+    if dec.ndim != 1 or dec.shape != y.shape:
+        raise ValueError("platt_fit: dec and y are 1-D arrays of one length")
+    A, B, info = ctypes.c_double(), ctypes.c_double(), ctypes.c_int()
+    _lib.check(_lib.load().rml_platt_fit(dec.ctypes.data, y.ctypes.data, len(dec), ctypes.byref(A), ctypes.byref(B), ctypes.byref(info)),
+               "rml_platt_fit")
+    return A.value, B.value, info.value
+
+
+def _fit_plan(yi, nc, wC, seed, probability, shrinking, max_iter, tol, matrix=0):
+    """The batch of ONE ``SVC.fit`` for ``smo_device``, beside ``GridSearchSVC._smo_plan``: for class indices ``yi`` (0 .. nc-1), the
+    per-class weighted C ``wC`` and libsvm's seed, problems 0 .. P-1 are the P = nc(nc-1)/2 pairwise duals of svm_train (rows in
+    class order, Cp / Cn as ``_smo_plan`` forms them).  With ``probability`` up to 5 P sub-duals of svm_binary_svc_probability
+    (sk:2107-2203) follow: the pair's rows shuffled (``libsvm_shuffle``; the generator is re-seeded for every pair, sk:2373-2376),
+    fold f holding out perm[f l / 5 : (f+1) l / 5], each sub-dual in the order libsvm's inner svm_train gives it -- its
+    svm_group_classes sorts the labels (sk:2278-2295), so the -1 rows come first (the solver's y = +1 group, with C = Cn), each
+    group in shuffle order -- and one SMO_FIT of two classes per fold with held-out rows.  A fold whose training part misses a class
+    has no dual (sk:2161-2169: its held-out values are +1 / -1 / 0, kept in ``const_dec``); an empty fold (l < 5) is solved as libsvm
+    solves it (it can only set fit_status_) and scored by nothing.
+    Returns (plan, meta); meta: per pair ``rows`` (Gram rows, class a then b), ``n_a``, ``const_dec``, and ``held``: (pair, positions
+    in the pair's rows, offset into the batch's held-out rows) per fit."""
+    pairs = [(a, b) for a in range(nc) for b in range(a + 1, nc)]
+    cls_rows = [np.nonzero(yi == c)[0].astype(np.int32) for c in range(nc)]
+    problems, rows, fits, test_rows, held = [], [], [], [], []
+    n_rows = n_test = 0
+
+    def add(rr, n_pos, Cp, Cn):
+        nonlocal n_rows
+        problems.append((matrix, len(rr), n_pos, int(bool(shrinking)), int(max_iter), 0, n_rows, n_rows, Cp, Cn, float(tol)))
+        rows.append(rr)
+        n_rows += len(rr)
+
+    pair_rows = [np.concatenate([cls_rows[a], cls_rows[b]]) for a, b in pairs]
+    for (a, b), rr in zip(pairs, pair_rows):
+        add(rr, len(cls_rows[a]), wC[a], wC[b])
+    const_dec = []
+    for p, ((a, b), rr) in enumerate(zip(pairs, pair_rows)):
+        if not probability:
+            break
+        l = len(rr)
+        pos = np.arange(l) < len(cls_rows[a])               # y = +1: class a
+        perm = libsvm_shuffle(seed, l)
+        dec0 = np.zeros(l)
+        for f in range(_PLATT_FOLDS):
+            b0, e0 = f * l // _PLATT_FOLDS, (f + 1) * l // _PLATT_FOLDS
+            tr, te = np.concatenate([perm[:b0], perm[e0:]]), perm[b0:e0]
+            n_p = int(pos[tr].sum())
+            n_n = len(tr) - n_p
+            if n_p == 0 or n_n == 0:
+                dec0[te] = 0.0 if n_p == n_n else (1.0 if n_p > 0 else -1.0)
+                continue
+            # the sub-model's label[0] is -1: its first group is the -1 rows with C = 1 * Cn, then the +1 rows with C = 1 * Cp
+            add(rr[np.concatenate([tr[~pos[tr]], tr[pos[tr]]])], n_n, 1.0 * wC[b], 1.0 * wC[a])
+            if len(te):
+                fits.append((len(problems) - 1, len(te), n_test))
+                test_rows.append(rr[te])
+                held.append((p, te, n_test))
+                n_test += len(te)
+        const_dec.append(dec0)
+    cat = lambda parts: np.concatenate(parts).astype(np.int32) if parts else np.zeros(0, np.int32)
+    plan = {"problems": np.array(problems, dtype=SMO_PROBLEM), "rows": cat(rows), "fits": np.array(fits, dtype=SMO_FIT),
+            "test_rows": cat(test_rows), "test_y": np.zeros(n_test, np.int32), "n_classes": 2}
+    meta = {"pairs": pairs, "cls_rows": cls_rows, "rows": pair_rows, "const_dec": const_dec, "held": held}
+    return plan, meta
+
+
+def _fit_batch(params, y, run, matrix=0):
+    """libsvm's ``SVC(kernel='precomputed', **params).fit(K, y)`` from ONE batch of duals: ``run(plan)`` is ``smo_device`` on the
+    matrix K (``_smo`` or its ``solve`` hook).  Every dual of the fit -- the P pairwise ones and, with ``probability``, the sub-duals
+    of the Platt cross-validation -- is solved side by side in one ``rml_smo_solve`` call, the held-out rows are scored in one
+    ``rml_smo_score`` call, and only alpha, rho, n_iter, stopped and the held-out decision values come back; ``rml_platt_fit`` then
+    runs once per pair.  Returns the fitted attributes of that estimator (what ``vars()`` adds to the constructor parameters),
+    in libsvm's model layout and with scikit-learn's sign flip of two-class models, without calling libsvm."""
+    import warnings
+    from sklearn.exceptions import ConvergenceWarning
+    from sklearn.utils.class_weight import compute_class_weight
+    y = np.asarray(y)
+    classes, yi = np.unique(y, return_inverse=True)
+    nc = len(classes)
+    if not 2 <= nc <= 8:
+        raise ValueError("the device SVC fit takes 2..8 classes, got %d" % nc)
+    if not float(params["C"]) > 0:
+        raise ValueError("C must be > 0, got %r" % (params["C"],))
+    class_weight_ = compute_class_weight(params["class_weight"], classes=classes, y=y)
+    wC = [float(params["C"]) * float(w) for w in class_weight_]            # libsvm's weighted_C (sk:2455-2468)
+    seed = _libsvm_seed(params["random_state"])
+    probability = bool(params["probability"])
+    plan, meta = _fit_plan(yi.astype(np.int32), nc, wC, seed, probability, params["shrinking"], params["max_iter"], params["tol"], matrix)
+    out = run(plan)
+    pairs, cls_rows = meta["pairs"], meta["cls_rows"]
+    P = len(pairs)
+    probs = plan["problems"]
+    alphas = [out["alpha"][int(r["alpha_off"]):int(r["alpha_off"]) + int(r["l"])] for r in probs[:P]]
+
+    # svm_train's model (sk:2517-2627): support vectors grouped by class in row order, sv_coef[j-1] / sv_coef[i] of pair (i, j)
+    nonzero = np.zeros(len(y), dtype=bool)
+    for rr, al in zip(meta["rows"], alphas):
+        nonzero[rr[al > 0]] = True
+    keep = [nonzero[r] for r in cls_rows]
+    n_support = np.array([int(k.sum()) for k in keep], dtype=np.int32)
+    support = np.concatenate([r[k] for r, k in zip(cls_rows, keep)]).astype(np.int32)
+    start = np.concatenate([[0], np.cumsum(n_support)])
+    dual_coef = np.empty((nc - 1, int(n_support.sum())), dtype=np.float64)
+    for (a, b), al in zip(pairs, alphas):
+        n_a = len(cls_rows[a])
+        dual_coef[b - 1, start[a]:start[a + 1]] = al[:n_a][keep[a]]           # alpha * y, y = +1
+        dual_coef[a, start[b]:start[b + 1]] = -al[n_a:][keep[b]]              # y = -1
+    rho = np.asarray(out["rho"][:P], dtype=np.float64)
+    intercept = np.where(rho != 0, -rho, 0.0)                                 # copy_intercept: -rho, never -0.0
+
+    probA, probB = np.empty(0, dtype=np.float64), np.empty(0, dtype=np.float64)
+    if probability:
+        dec = [d.copy() for d in meta["const_dec"]]
+        for p, te, off in meta["held"]:
+            dec[p][te] = -out["dec"][off:off + len(te), 0]                    # times submodel->label[0] = -1 (sk:2191)
+        probA, probB = np.empty(P, dtype=np.float64), np.empty(P, dtype=np.float64)
+        for p, (a, b) in enumerate(pairs):
+            yy = np.where(np.arange(len(dec[p])) < len(cls_rows[a]), 1.0, -1.0)
+            probA[p], probB[p], _ = platt_fit(dec[p], yy)
+
+    fitted = {"_sparse": False, "class_weight_": class_weight_, "classes_": classes, "_gamma": 0.0, "support_": support,
+              "support_vectors_": np.empty((0, 0), dtype=np.float64), "_n_support": n_support, "dual_coef_": dual_coef,
+              "intercept_": intercept, "_probA": probA, "_probB": probB, "fit_status_": int(bool((out["stopped"] == 1).any())),
+              "_num_iter": np.asarray(out["n_iter"][:P], dtype=np.int32).copy(), "shape_fit_": (len(y), len(y)),
+              "n_features_in_": len(y)}
+    if fitted["fit_status_"] == 1:
+        warnings.warn("Solver terminated early (max_iter=%i).  Consider pre-processing your data with StandardScaler or MinMaxScaler."
+                      % params["max_iter"], ConvergenceWarning)
+    # SVC.fit after libsvm returns (sklearn/svm/_base.py): the internal copies, then the sign flip of two-class models
+    fitted["_intercept_"] = intercept.copy()
+    fitted["_dual_coef_"] = dual_coef
+    if nc == 2:
+        fitted["intercept_"] = intercept * -1
+        fitted["dual_coef_"] = -dual_coef
+    if not (np.isfinite(fitted["_intercept_"]).all() and np.isfinite(dual_coef).all()):
+        raise ValueError("The dual coefficients or intercepts are not finite. The input data may contain large values and need to be "
+                         "preprocessed.")
+    fitted["n_iter_"] = fitted["_num_iter"]
+    return fitted
+
+
+def _adopt(est, fitted, X32, key):
+    """Turn the ``linear`` / ``rbf`` estimator ``est`` into the fitted one from the fitted attributes of its precomputed-kernel twin
+    on the rows ``X32``: the support vectors are the training rows, shape and gamma are those of a fit on the rows."""
+    X64 = X32.astype(np.float64)
+    vars(est).update(fitted)
+    est.support_vectors_ = X64[est.support_]
+    est.shape_fit_ = X32.shape
+    est.n_features_in_ = X32.shape[1]
+    est._gamma = _sklearn_gamma(est.gamma, X64) if key[0] == "linear" else est.gamma
+    return est
+
+
+def _check_kernel(who, kernel, gamma, C):
+    if kernel not in ("linear", "rbf"):
+        raise NotImplementedError("%s: kernel %r (the HIP Gram pass computes 'linear' and 'rbf')" % (who, kernel))
+    if kernel == "rbf":
+        if isinstance(gamma, str):
+            raise NotImplementedError("%s: gamma=%r depends on each fold's rows; give numeric gammas" % (who, gamma))
+        if not np.isfinite(float(gamma)) or float(gamma) < 0:
+            raise ValueError("%s: gamma must be a finite non-negative number, got %r" % (who, gamma))
+    if not float(C) > 0:
+        raise ValueError("%s: C must be > 0, got %r" % (who, C))
+
+
+def fit_svc(estimator, X, y, device=None):
+    """``estimator.fit(X, y)`` for an unfitted ``sklearn.svm.SVC`` with kernel ``linear`` or ``rbf`` (numeric gamma), on the GPU: the
+    kernel matrix by ``rml_gram``, every dual of libsvm's fit in one ``rml_smo_solve`` call (its 5-fold Platt cross-validation
+    included when ``probability=True``), libsvm's sigmoid fit by ``rml_platt_fit``.  ``C``, ``class_weight``, ``tol``, ``shrinking``,
+    ``max_iter``, ``probability`` and ``random_state`` are honoured (``random_state=None`` draws a seed as scikit-learn does);
+    ``sample_weight`` is not supported.  On the same kernel matrix the result is what libsvm computes, bit for bit.  Returns the
+    estimator, fitted: a genuine ``SVC`` that predicts, pickles and converts (``from_sklearn``) like any other."""
+    from sklearn.svm import SVC
+    if type(estimator) is not SVC:
+        raise NotImplementedError("fit_svc fits sklearn.svm.SVC, not %s" % type(estimator).__name__)
+    params = estimator.get_params()
+    _check_kernel("fit_svc", params["kernel"], params["gamma"], params["C"])
+    X32 = _rows(X)
+    y = np.asarray(y)
+    if y.ndim != 1 or y.shape[0] != X32.shape[0]:
+        raise ValueError("Found input variables with inconsistent numbers of samples: [%d, %d]" % (X32.shape[0], len(y)))
+    key = ("linear", None) if params["kernel"] == "linear" else ("rbf", float(params["gamma"]))
+    fitted = _fit_batch({k: params[k] for k in _FIT_CARRY}, y, lambda plan: _smo(X32, [key], plan, device))
+    return _adopt(estimator, fitted, X32, key)
+
+
 class GridSearchSVC:
     """``GridSearchCV(SVC(...), param_grid)`` for C, ``linear`` / ``rbf`` kernels and numeric gamma, on GPU kernel matrices.
 
@@ -194,10 +405,15 @@ class GridSearchSVC:
     ``max_iter`` and ``class_weight`` of the base estimator are honoured (weighted C as scikit-learn forms it: ``compute_class_weight``
     on the fold's labels, times C).  A split whose training rows miss a class is fitted on the host as before.  The batch has no
     per-fit times: ``fit_time`` / ``score_time`` of a device fit are the batch's solve / score time divided evenly among its fits.
-    ``solver="host"`` (the default) is the search described above."""
+    ``solver="host"`` (the default) is the search described above.
+
+    ``refit_solver="device"`` refits the winner on the GPU as well (``fit_svc``'s batch: the duals of libsvm's fit and of its Platt
+    cross-validation in one ``rml_smo_solve`` call, ``rml_platt_fit`` per class pair) -- after a device search on the matrix still
+    resident there, so that no kernel matrix is copied back at all.  The estimator is the same, bit for bit.
+    ``refit_solver="host"`` (the default) is libsvm's fit on the host copy of the winner's matrix."""
 
     def __init__(self, estimator, param_grid, cv=5, n_jobs=4, refit=True, device=None, max_gram_bytes=8 << 30, scoring=None,
-                 verbose=0, solver="host"):
+                 verbose=0, solver="host", refit_solver="host"):
         self.estimator = estimator
         self.param_grid = param_grid
         self.cv = cv
@@ -208,6 +424,7 @@ class GridSearchSVC:
         self.scoring = scoring
         self.verbose = verbose
         self.solver = solver
+        self.refit_solver = refit_solver
 
     # ---- argument checks (before any work) ----
     def _check(self):
@@ -215,6 +432,8 @@ class GridSearchSVC:
         from sklearn.svm import SVC
         if self.solver not in ("host", "device"):
             raise ValueError("GridSearchSVC: solver must be 'host' or 'device', got %r" % (self.solver,))
+        if self.refit_solver not in ("host", "device"):
+            raise ValueError("GridSearchSVC: refit_solver must be 'host' or 'device', got %r" % (self.refit_solver,))
         if type(self.estimator) is not SVC:
             raise NotImplementedError("GridSearchSVC searches sklearn.svm.SVC, not %s" % type(self.estimator).__name__)
         if self.scoring not in (None, "accuracy"):
@@ -365,6 +584,7 @@ class GridSearchSVC:
 
         mats = {}
         fetch = {}                              # device search: kernel key -> function returning its host matrix (last group only)
+        resident = {}                           # device search: kernel key -> (matrix index, solve hook) of the resident matrices (same)
         with ThreadPoolExecutor(max_workers=nj) as pool:
             for grp in groups:
                 todo = [(ci, si) for ci, p in enumerate(candidates) if self._key(p, base) in grp for si in range(n_splits)]
@@ -372,6 +592,7 @@ class GridSearchSVC:
                     plan, on_device, todo = self._smo_plan(candidates, base, grp, splits, y)
                     out = _smo(X32, grp, plan, self.device)
                     fetch = {k: (lambda i=i, m=out["matrix"]: m(i)) for i, k in enumerate(grp)}
+                    resident = {k: (i, out["solve"]) for i, k in enumerate(grp)} if "solve" in out else {}
                     mats = {}
                     for f, (ci, si) in enumerate(on_device):
                         scores[ci, si] = float(out["correct"][f]) / len(splits[si][1])
@@ -418,20 +639,22 @@ class GridSearchSVC:
         if self.refit:
             best = self.best_params_
             key = self._key(best, base)
-            K = mats[key] if key in mats else fetch[key]() if key in fetch else _gram(X32, [key], self.device)[0]
-            t0 = time.perf_counter()
-            pre = self._svc(best, base, "precomputed").fit(K, y)
-            self.refit_time_ = time.perf_counter() - t0
-            est = clone(self.estimator).set_params(**best)
-            X64 = X32.astype(np.float64)
-            params = pre.get_params()
-            fitted = {k: v for k, v in vars(pre).items() if k not in params}
-            vars(est).update(fitted)
-            est.support_vectors_ = X64[pre.support_]
-            est.shape_fit_ = (N, D)
-            est.n_features_in_ = D
-            est._gamma = _sklearn_gamma(est.gamma, X64) if key[0] == "linear" else est.gamma
-            self.best_estimator_ = est
+            if self.refit_solver == "device":
+                # the winner's matrix where the search left it, or (host search, or a winner of an earlier group) computed again
+                matrix, run = resident.get(key, (0, lambda plan: _smo(X32, [key], plan, self.device)))
+                params = {k: base[k] for k in _FIT_CARRY}
+                params["C"] = best.get("C", base["C"])
+                t0 = time.perf_counter()
+                fitted = _fit_batch(params, y, run, matrix)
+                self.refit_time_ = time.perf_counter() - t0
+            else:
+                K = mats[key] if key in mats else fetch[key]() if key in fetch else _gram(X32, [key], self.device)[0]
+                t0 = time.perf_counter()
+                pre = self._svc(best, base, "precomputed").fit(K, y)
+                self.refit_time_ = time.perf_counter() - t0
+                params = pre.get_params()
+                fitted = {k: v for k, v in vars(pre).items() if k not in params}
+            self.best_estimator_ = _adopt(clone(self.estimator).set_params(**best), fitted, X32, key)
         self.classes_ = np.unique(y)
         return self
 
@@ -449,9 +672,10 @@ class GridSearchSVC:
         return self.best_estimator_.score(X, y)
 
 
-def find_best_svm_estimator(X, y, cv, random_seed, solver="host"):
+def find_best_svm_estimator(X, y, cv, random_seed, solver="host", refit_solver="host"):
     """Exhaustive search over specified parameter values for svm (train.py:462-491, the same grid, base estimator and log lines).
-    ``solver="device"`` runs the search's fits on the GPU (GridSearchSVC); the result is the same.
+    ``solver="device"`` runs the search's fits on the GPU and ``refit_solver="device"`` the refit of the winner (GridSearchSVC);
+    the result is the same.
 
     Returns:
         optimized svm estimator.
@@ -469,7 +693,8 @@ def find_best_svm_estimator(X, y, cv, random_seed, solver="host"):
     ]
     init_est = svm.SVC(probability=True, class_weight='balanced',
                        random_state=random_seed, cache_size=1000, verbose=False)
-    grid_search = GridSearchSVC(estimator=init_est, param_grid=param_grid, verbose=2, n_jobs=4, cv=cv, solver=solver)
+    grid_search = GridSearchSVC(estimator=init_est, param_grid=param_grid, verbose=2, n_jobs=4, cv=cv, solver=solver,
+                                refit_solver=refit_solver)
     grid_search.fit(X, y)
     logger.info('\n Best estimator:')
     logger.info(grid_search.best_estimator_)

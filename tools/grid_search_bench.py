@@ -1,6 +1,6 @@
 """SVC grid search on GPU kernel matrices (GridSearchSVC, rml_gram): one JSON line.
 
-    python tools/grid_search_bench.py [--sets 1458,7290] [--jobs 4,16] [--solver host|device] [--sklearn]
+    python tools/grid_search_bench.py [--sets 1458,7290] [--jobs 4,16] [--solver host|device] [--refit host|device] [--sklearn]
 
 Two seeded synthetic training sets at the reference's feature length D = 10 010 (three planes of the Walabot grid):
   1458 x 10010  rows on the code grid, float32(c/255) (the reference's balanced training set, train.py:534)
@@ -14,7 +14,9 @@ and the reference's grid (5 linear + 25 RBF points, 5 stratified folds).  Per se
 (used only by the refit-free host fall-backs, so the figures should agree) device_search_s_jJ end to end, plus of the last run
   smo_solve_ms / smo_score_ms   wall time of the batched rml_smo_solve / rml_smo_score calls, host-synchronised
   smo_problems, smo_iters, smo_iters_max   duals in the batch, their libsvm iterations in total and of the longest dual
-  refit_s        the host refit of the winner (libsvm with probability=True), part of every search
+  refit_s        the refit of the winner (probability=True), part of every search: --refit host (the default) is libsvm on the
+                 host copy of the winner's matrix, --refit device the same fit as one batch of duals on the resident matrix
+                 (GridSearchSVC(refit_solver="device")); refit_solver names which one the line timed
 --sklearn also runs scikit-learn's GridSearchCV on the raw rows of the 1458 set, on the sub-grid stated in the output (the full grid
 runs for about an hour), and reports its time and whether best_params_ agree with GridSearchSVC on the same sub-grid.
 """
@@ -92,12 +94,12 @@ def gram_timing(rml, X, kernels, reps=3):
     return min(ms), d2h, [host[k] for k in range(len(kernels))]
 
 
-def run_set_device(rml, N, on_grid, jobs, seed):
+def run_set_device(rml, N, on_grid, jobs, seed, refit="host"):
     """GridSearchSVC(solver="device") end to end per n_jobs, with the batch's own figures (train._smo wrapped, not replaced)"""
     from sklearn.model_selection import StratifiedKFold
     import radar_ml_amd.train as T
     X, y = synth(N, on_grid, seed)
-    res = {"rows": N, "D": D, "on_code_grid": on_grid, "solver": "device"}
+    res = {"rows": N, "D": D, "on_code_grid": on_grid, "solver": "device", "refit_solver": refit}
     real = T._smo
     seen = []
 
@@ -108,11 +110,13 @@ def run_set_device(rml, N, on_grid, jobs, seed):
         return out
     T._smo = watched
     try:
-        T.GridSearchSVC(base_svc(), GRID, cv=StratifiedKFold(5).split(X, y), n_jobs=min(jobs), solver="device").fit(X, y)   # warm-up
+        T.GridSearchSVC(base_svc(), GRID, cv=StratifiedKFold(5).split(X, y), n_jobs=min(jobs), solver="device",
+                        refit_solver=refit).fit(X, y)   # warm-up
         for j in sorted(jobs):
             del seen[:]
             t0 = time.perf_counter()
-            gs = T.GridSearchSVC(base_svc(), GRID, cv=StratifiedKFold(5).split(X, y), n_jobs=j, solver="device").fit(X, y)
+            gs = T.GridSearchSVC(base_svc(), GRID, cv=StratifiedKFold(5).split(X, y), n_jobs=j, solver="device",
+                                 refit_solver=refit).fit(X, y)
             res["device_search_s_j%d" % j] = round(time.perf_counter() - t0, 3)
             progress("%d rows: device search at n_jobs=%d: %.3f s (solve %.1f ms, score %.1f ms, refit %.3f s)"
                      % (N, j, res["device_search_s_j%d" % j], 1e3 * sum(s[1] for s in seen), 1e3 * sum(s[2] for s in seen), gs.refit_time_))
@@ -125,7 +129,7 @@ def run_set_device(rml, N, on_grid, jobs, seed):
     return res, X, y
 
 
-def run_set(rml, N, on_grid, jobs, seed):
+def run_set(rml, N, on_grid, jobs, seed, refit="host"):
     from sklearn.model_selection import StratifiedKFold
     import radar_ml_amd.train as T
     X, y = synth(N, on_grid, seed)
@@ -133,7 +137,7 @@ def run_set(rml, N, on_grid, jobs, seed):
     gram_ms, d2h_ms, mats = gram_timing(rml, X, kernels)
     progress("%d rows: rml_gram %.2f ms, copy %.0f ms" % (N, gram_ms, d2h_ms))
     flop = float(N) * (N + 1) * D
-    res = {"rows": N, "D": D, "on_code_grid": on_grid, "kernels": len(kernels), "gram_ms": round(gram_ms, 3),
+    res = {"rows": N, "D": D, "on_code_grid": on_grid, "refit_solver": refit, "kernels": len(kernels), "gram_ms": round(gram_ms, 3),
            "gram_tflops": round(flop / gram_ms / 1e9, 2), "gram_frac": round(flop / (gram_ms * 1e-3) / F64_PEAK, 3),
            "d2h_ms": round(d2h_ms, 1)}
     cached = dict(zip(kernels, mats))
@@ -143,7 +147,7 @@ def run_set(rml, N, on_grid, jobs, seed):
         T._gram = lambda Xh, ks, device=None: [cached[k] for k in ks]
         try:
             t0 = time.perf_counter()
-            gs = T.GridSearchSVC(base_svc(), GRID, cv=StratifiedKFold(5).split(X, y), n_jobs=j).fit(X, y)
+            gs = T.GridSearchSVC(base_svc(), GRID, cv=StratifiedKFold(5).split(X, y), n_jobs=j, refit_solver=refit).fit(X, y)
             res["host_s_j%d" % j] = round(time.perf_counter() - t0, 2)
             progress("%d rows: host search at n_jobs=%d: %.2f s" % (N, j, res["host_s_j%d" % j]))
             best = gs.best_params_
@@ -162,7 +166,7 @@ def run_set(rml, N, on_grid, jobs, seed):
     T._gram = timed
     try:
         t0 = time.perf_counter()
-        gs = T.GridSearchSVC(base_svc(), GRID, cv=StratifiedKFold(5).split(X, y), n_jobs=j).fit(X, y)
+        gs = T.GridSearchSVC(base_svc(), GRID, cv=StratifiedKFold(5).split(X, y), n_jobs=j, refit_solver=refit).fit(X, y)
         total = time.perf_counter() - t0
     finally:
         T._gram = real
@@ -170,6 +174,7 @@ def run_set(rml, N, on_grid, jobs, seed):
     res["device_s"] = round(spent[0], 2)
     res["total_s"] = round(total, 2)
     progress("%d rows: end to end at n_jobs=%d: %.2f s" % (N, j, total))
+    res["refit_s"] = round(gs.refit_time_, 3)
     res["best_params"] = gs.best_params_
     res["best_score"] = round(gs.best_score_, 4)
     if best is not None:
@@ -182,6 +187,7 @@ def main():
     ap.add_argument("--sets", default="1458,7290", help="training set sizes to run (1458: code grid, 7290: off-grid)")
     ap.add_argument("--jobs", default="4,16", help="n_jobs values of the host search")
     ap.add_argument("--solver", default="host", choices=["host", "device"], help="where the search's SVC duals are solved")
+    ap.add_argument("--refit", default="host", choices=["host", "device"], help="where the winner is refitted (refit_s)")
     ap.add_argument("--sklearn", action="store_true", help="also time scikit-learn's GridSearchCV on the 1458 set (sub-grid)")
     args = ap.parse_args()
     import torch
@@ -192,7 +198,7 @@ def main():
     out = {"metric": "svc_grid_search", "grid": "5 linear + 25 rbf, 5 folds", "f64_peak_tflops": F64_PEAK / 1e12, "sets": []}
     keep = None
     for n in [int(s) for s in args.sets.split(",")]:
-        r, X, y = (run_set_device if args.solver == "device" else run_set)(rml, n, n == 1458, jobs, seed=n)
+        r, X, y = (run_set_device if args.solver == "device" else run_set)(rml, n, n == 1458, jobs, seed=n, refit=args.refit)
         out["sets"].append(r)
         if n == 1458:
             keep = (X, y)

@@ -208,6 +208,43 @@ static void phase_a_thread_local_errors() {
     CHECK(ok[0] && ok[1] && ok[2] && ok[3]);
 }
 
+// the two host-side steps of SVC(probability=True).fit: every length from 0 (exact-size heap buffers: an index one past the end is a
+// report), a permutation out, finite A / B on separable, constant, empty and huge decision values, bad arguments as statuses
+static void phase_a_platt() {
+    for (int64_t l : {0, 1, 2, 3, 5, 118, 4860}) {
+        std::vector<int32_t> perm((size_t)l);
+        std::vector<char> seen((size_t)l, 0);
+        CHECK(rml_libsvm_shuffle(1234u + (uint32_t)l, l, perm.data()) == RML_OK);
+        bool is_perm = true;
+        for (int64_t i = 0; i < l; ++i) {
+            is_perm &= perm[(size_t)i] >= 0 && perm[(size_t)i] < l && !seen[(size_t)perm[(size_t)i]];
+            if (perm[(size_t)i] >= 0 && perm[(size_t)i] < l) seen[(size_t)perm[(size_t)i]] = 1;
+        }
+        CHECK(is_perm);
+        std::vector<int32_t> again((size_t)l);
+        CHECK(rml_libsvm_shuffle(1234u + (uint32_t)l, l, again.data()) == RML_OK && perm == again);
+        for (int kind = 0; kind < 4; ++kind) {
+            std::vector<double> dec((size_t)l), y((size_t)l);
+            for (int64_t i = 0; i < l; ++i) {
+                y[(size_t)i] = (i & 1) ? -1.0 : 1.0;
+                const double noise = (double)(rnd() % 2001) / 1000.0 - 1.0;
+                dec[(size_t)i] = kind == 0 ? y[(size_t)i] + 0.5 * noise : kind == 1 ? 1.0 : kind == 2 ? 1e6 * y[(size_t)i] : noise;
+            }
+            double A = NAN, B = NAN;
+            int info = -1;
+            CHECK(rml_platt_fit(dec.data(), y.data(), l, &A, &B, &info) == RML_OK);
+            CHECK(isfinite(A) && isfinite(B) && info >= RML_PLATT_OK && info <= RML_PLATT_MAX_ITER);
+            CHECK(rml_platt_fit(dec.data(), y.data(), l, &A, &B, nullptr) == RML_OK);
+        }
+    }
+    double d = 0;
+    int32_t i32 = 0;
+    CHECK(rml_libsvm_shuffle(1, -1, &i32) == RML_ERR_INVALID && strlen(rml_last_error()) > 0);
+    CHECK(rml_libsvm_shuffle(1, 3, nullptr) == RML_ERR_INVALID && rml_libsvm_shuffle(1, 0, nullptr) == RML_OK);
+    CHECK(rml_platt_fit(nullptr, &d, 1, &d, &d, nullptr) == RML_ERR_INVALID && rml_platt_fit(&d, &d, 1, nullptr, &d, nullptr) == RML_ERR_INVALID);
+    CHECK(rml_platt_fit(&d, &d, -1, &d, &d, nullptr) == RML_ERR_INVALID);
+}
+
 // ---- phase B (a device is present) -----------------------------------------------------------------------------------------
 #define HIPCK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { fprintf(stderr, "HIP error %s at line %d\n", hipGetErrorString(e_), __LINE__); ++g_fail; return; } } while (0)
 
@@ -336,6 +373,7 @@ int main(int argc, char** argv) {
     phase_a_model_packing();
     phase_a_workspace_layout(false);
     phase_a_thread_local_errors();
+    phase_a_platt();
     printf("phase A: %s\n", g_fail ? "FAILED" : "ok");
     rml_ctx* ctx = nullptr;
     const int rc = rml_ctx_create(0, &ctx);
