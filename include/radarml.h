@@ -117,7 +117,10 @@ int rml_ctx_device(const rml_ctx* ctx);
  *   RML_OPT_CHUNK (default 0 = chosen per batch): rows per chunk of the chunked front doors (>= 128; rounded up to 128).
  *   RML_OPT_C1_PK (default 1): packed first-layer kernels of the SGAN branches.
  *   RML_OPT_SMO_LDS_ROWS (default RML_SMO_LDS_ROWS_MAX = 2 768, the 160 KB of a CU at 59 bytes per row): rml_smo_solve keeps the state
- *     of a dual of at most this many rows in LDS; larger duals run the same code on the workspace.  0: every dual on the workspace. */
+ *     of a dual of at most this many rows in LDS; larger duals run the same code on the workspace.  0: every dual on the workspace.
+ *   RML_OPT_SGD_RESIDENT_D (default RML_SGD_RESIDENT_D_MAX = 10 240, ten elements per thread of a 1 024-thread workgroup):
+ *     rml_sgd_solve keeps the weights of a problem of at most this many features in registers; wider rows run the same code with
+ *     the weights on the workspace.  0: every problem on the workspace.  The results are the same bits either way. */
 #define RML_OPT_PROJECT_SHARE_CU 1
 #define RML_OPT_WAVEFRAME 2
 #define RML_OPT_LINPLANE 3
@@ -130,6 +133,8 @@ int rml_ctx_device(const rml_ctx* ctx);
 #define RML_OPT_C1_PK 10
 #define RML_OPT_SMO_LDS_ROWS 11
 #define RML_SMO_LDS_ROWS_MAX 2768
+#define RML_OPT_SGD_RESIDENT_D 12
+#define RML_SGD_RESIDENT_D_MAX 10240
 int rml_ctx_set_option(rml_ctx* ctx, int option, int value);
 int rml_ctx_get_option(const rml_ctx* ctx, int option, int* value);
 
@@ -393,6 +398,75 @@ int rml_smo_score(rml_ctx* ctx, const double* gram, int64_t N, int64_t ld, int64
                   const double* alpha, int64_t n_alpha_total, const double* rho, int n_classes,
                   const rml_smo_fit* fits, int64_t n_fits, const int32_t* test_rows, const int32_t* test_y,
                   int64_t n_test_total, double* dec, int32_t* labels, int32_t* correct, void* stream);
+
+/* ---- SGDClassifier fits on the device ---------------------------------------------------------------------------------
+ * rml_sgd_solve: a batch of independent binary logistic-regression problems (one per grid point x fold x class of a
+ * one-vs-rest SGDClassifier), each solved by one workgroup running scikit-learn 1.7.2's _plain_sgd64
+ * (sklearn/linear_model/_sgd_fast.pyx.tp:275-603) for loss='log_loss', learning_rate='optimal', dense rows, with its
+ * WeightVector (sklearn/utils/_weight_vector.pyx.tp), its shuffle (sklearn/utils/_seq_dataset.pyx.tp:137-145 on the
+ * generator of sklearn/utils/_random.pxd:20-34), the half-binomial loss on labels 0 / 1 (sklearn/_loss/_loss.pyx.tp:256-266,
+ * 686-725) and the cumulative L1 penalty (_sgd_fast.pyx.tp:631-659).  It replaces the host fits of
+ * GridSearchCV(SGDClassifier(loss='log')) at train.py:350-381 and the partial_fit of train.py:432.  Every expression outside the
+ * dot product w . x is scikit-learn's, un-fused and in its order.  The dot product is summed in this order:
+ *   thread t of 1 024 owns the elements t, t + 1024, ..; it adds its products w[e] * (double)x[e] in ascending order from 0;
+ *   the 64 threads of a wave (64 v .. 64 v + 63) combine by a butterfly, s += s of lane ^ m for m = 32, 16, 8, 4, 2, 1;
+ *   the 16 wave sums are added in wave order, ((S0 + S1) + S2) + .. + S15.
+ * A problem's result does not depend on its place in the batch, on the batch, or on RML_OPT_SGD_RESIDENT_D, and is the same
+ * bits run to run.
+ *   X: DEVICE float32, row i at X + i * ld (ld >= D), N rows (converted to double exactly, as X.astype(float64)).
+ *   probs: HOST, n_probs descriptors.  rows: DEVICE int32, n_rows_total entries in [0, N): problem p trains on the n rows at
+ *   rows + rows_off, in that order (the dataset's initial order), with the labels (0 / 1) at y + y_off (DEVICE int32,
+ *   n_y_total entries); problems may share either list.  n <= RML_SGD_MAX_ROWS.  seed is the shuffle seed fit_binary draws
+ *   (the shuffle runs before every epoch with the same seed on the persisting order, so the permutations compound).
+ *   average: 0, or the iteration at which averaging starts.  tol: -INFINITY for tol=None.  t0: 1.0 for a fresh fit.  warm != 0:
+ *   the outputs of slot `out` hold the initial coef / avg_coef / intercept / avg_intercept (partial_fit: t0 = est.t_).
+ *   Outputs, DEVICE, indexed by the problem's slot `out` < n_out: coef and avg_coef (D doubles at out * D: the standard and the
+ *   averaged weights; avg_coef is written only where average > 0), intercept, avg_intercept, n_iter (epochs run), t
+ *   (t0 + n_iter * n, as est.t_), status: 0 converged, 1 max_iter reached, 2 non-finite weights (where scikit-learn raises its
+ *   "Floating-point under-/overflow" ValueError), -1 a row index outside [0, N): that problem is not run and its other
+ *   outputs are untouched.
+ * rml_sgd_score: SGDClassifier.predict for n_fits fits of n_classes (2..8) classes.  Fit f is made of the n_classes consecutive
+ * problems prob0 .. (class order), or of ONE problem when n_classes == 2 (class 1 positive).  Per held-out row (test_rows +
+ * test_off, DEVICE int32; true class indices test_y + test_off) and class, dec = coef . x + intercept in the dot order above;
+ * the coefficients are the averaged ones where average > 0 and average <= t - 1 with t the largest t of the fit's problems, as
+ * SGDClassifier chooses.  The label is the first maximum over the classes, or dec > 0 for two classes.  It reads the outputs
+ * of rml_sgd_solve where they are.  Outputs, DEVICE: dec (n_test_total x n_dec doubles, n_dec = 1 for two classes, row-major
+ * per fit at test_off * n_dec), labels (n_test_total int32), correct (n_fits int32).  A held-out row outside [0, N) is not
+ * read: its values are NaN and its label -1.
+ * rml_sgd_shuffle: HOST helper, one call of SequentialDataset.shuffle(seed) on perm_inout (n int32), no device, no context.
+ * The two device calls use the context's workspace, are asynchronous on `stream` and read no environment variable. */
+#define RML_SGD_L1 1
+#define RML_SGD_L2 2
+#define RML_SGD_ELASTICNET 3
+#define RML_SGD_MAX_ROWS 8192
+typedef struct rml_sgd_problem {
+    int32_t n;                  /* training rows */
+    int32_t penalty;            /* RML_SGD_L1 / L2 / ELASTICNET */
+    int32_t average;            /* 0, or the iteration at which averaging starts */
+    int32_t max_iter;
+    int32_t n_iter_no_change;
+    int32_t shuffle;
+    uint32_t seed;              /* the shuffle seed */
+    int32_t warm;               /* the outputs hold the initial state */
+    int64_t rows_off;           /* into `rows` */
+    int64_t y_off;              /* into `y` */
+    int64_t out;                /* output slot: coef / avg_coef at out * D, the scalars at out */
+    double alpha, l1_ratio, tol, weight_pos, weight_neg, t0;
+} rml_sgd_problem;
+typedef struct rml_sgd_fit {
+    int32_t prob0;              /* first of the fit's class problems */
+    int32_t n_test;             /* held-out rows */
+    int64_t test_off;           /* into test_rows / test_y / labels; dec at test_off * n_dec */
+} rml_sgd_fit;
+int rml_sgd_solve(rml_ctx* ctx, const float* X, int64_t N, int64_t D, int64_t ld, const rml_sgd_problem* probs, int64_t n_probs,
+                  const int32_t* rows, int64_t n_rows_total, const int32_t* y, int64_t n_y_total, int64_t n_out, double* coef,
+                  double* avg_coef, double* intercept, double* avg_intercept, int32_t* n_iter, double* t, int32_t* status,
+                  void* stream);
+int rml_sgd_score(rml_ctx* ctx, const float* X, int64_t N, int64_t D, int64_t ld, const rml_sgd_problem* probs, int64_t n_probs,
+                  int64_t n_out, const double* coef, const double* avg_coef, const double* intercept, const double* avg_intercept,
+                  const double* t, int n_classes, const rml_sgd_fit* fits, int64_t n_fits, const int32_t* test_rows,
+                  const int32_t* test_y, int64_t n_test_total, double* dec, int32_t* labels, int32_t* correct, void* stream);
+int rml_sgd_shuffle(uint32_t seed, int64_t n, int32_t* perm_inout);
 
 /* ---- the host-side steps of SVC(probability=True).fit -------------------------------------------------------------------
  * libsvm's svm_train with probability = 1 runs, per class pair, svm_binary_svc_probability (scikit-learn 1.7.2,

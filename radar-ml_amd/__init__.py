@@ -15,7 +15,8 @@ from .svm import GpuSVC, GpuCalibratedClassifier, GpuLinearClassifier, KernelMat
 from .predict import classifier, classify_batch, calc_proj_zoom
 from .synth import synth_volumes
 from .augment import DataGenerator, augment_planes, rotation_params
-from .train import GridSearchSVC, find_best_svm_estimator, fit_svc
+from .train import (GridSearchSVC, find_best_svm_estimator, fit_svc, GridSearchSGD, find_best_sgd_svm_estimator, fit_sgd,
+                    partial_fit_sgd)
 
 __all__ = [
     "RadarMLError", "ProjMask", "ProjZoom", "DerivedTarget", "RADAR_MAX", "RADAR_MIN",
@@ -24,4 +25,5 @@ __all__ = [
     "GpuSVC", "GpuCalibratedClassifier", "GpuLinearClassifier", "KernelMatrix", "from_sklearn",
     "classifier", "classify_batch", "calc_proj_zoom", "synth_volumes",
     "DataGenerator", "augment_planes", "rotation_params", "GridSearchSVC", "find_best_svm_estimator", "fit_svc",
+    "GridSearchSGD", "find_best_sgd_svm_estimator", "fit_sgd", "partial_fit_sgd",
 ]

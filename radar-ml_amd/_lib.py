@@ -72,6 +72,12 @@ SIGNATURES = {
                               c_void_p, c_void_p, c_void_p, c_void_p]),
     "rml_smo_score": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64,
                               c_void_p, c_int, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "rml_sgd_solve": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int64,
+                              c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "rml_sgd_score": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p,
+                              c_void_p, c_void_p, c_int, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
+                              c_void_p]),
+    "rml_sgd_shuffle": (c_int, [c_uint32, c_int64, c_void_p]),
     "rml_libsvm_shuffle": (c_int, [c_uint32, c_int64, c_void_p]),
     "rml_platt_fit": (c_int, [c_void_p, c_void_p, c_int64, C.POINTER(c_double), C.POINTER(c_double), C.POINTER(c_int)]),
     "rml_project_svm": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_int, c_int, c_void_p, c_float,
@@ -132,19 +138,22 @@ SIGNATURES = {
 
 MODE_MAX, MODE_SLICE, MODE_SUM, MODE_MAX_NAN = 0, 1, 2, 3
 # rml_ctx_set_option ids (include/radarml.h RML_OPT_*)
-OPT_PROJECT_SHARE_CU, OPT_WAVEFRAME, OPT_LINPLANE, OPT_STAGE_CODES, OPT_SLICE_WAVE, OPT_DERIVE_FUSED, OPT_CODE_RMW, OPT_GEMM_BIG, OPT_CHUNK, OPT_C1_PK, OPT_SMO_LDS_ROWS = range(1, 12)
+OPT_PROJECT_SHARE_CU, OPT_WAVEFRAME, OPT_LINPLANE, OPT_STAGE_CODES, OPT_SLICE_WAVE, OPT_DERIVE_FUSED, OPT_CODE_RMW, OPT_GEMM_BIG, OPT_CHUNK, OPT_C1_PK, OPT_SMO_LDS_ROWS, OPT_SGD_RESIDENT_D = range(1, 13)
 OPTIONS = {"project_share_cu": OPT_PROJECT_SHARE_CU, "waveframe": OPT_WAVEFRAME, "linplane": OPT_LINPLANE, "stage_codes": OPT_STAGE_CODES,
            "slice_wave": OPT_SLICE_WAVE, "derive_fused": OPT_DERIVE_FUSED, "code_rmw": OPT_CODE_RMW, "gemm_big": OPT_GEMM_BIG,
            "chunk": OPT_CHUNK, "c1_pk": OPT_C1_PK}
-# options of the training-side solver (rml_smo_solve); set_option, get_option and the `options` context manager below take these
+# options of the training-side solvers (rml_smo_solve, rml_sgd_solve); set_option, get_option and the `options` context manager below take these
 # names too (kept apart from OPTIONS, whose keys are the inference paths' knobs)
-SOLVER_OPTIONS = {"smo_lds_rows": OPT_SMO_LDS_ROWS}
+SOLVER_OPTIONS = {"smo_lds_rows": OPT_SMO_LDS_ROWS, "sgd_resident_d": OPT_SGD_RESIDENT_D}
 SMO_LDS_ROWS_MAX = 2768
+SGD_RESIDENT_D_MAX = 10240
+SGD_MAX_ROWS = 8192
+SGD_L1, SGD_L2, SGD_ELASTICNET = 1, 2, 3
 # A/B runs from a shell (tools/profile_round.sh, tools/kbench.py under rocprofv3): these environment variables are read ONCE, here in
 # Python, when a context is created, and applied as options -- the library itself never reads the environment
 ENV_OPTIONS = {"RML_WAVE_SHARE": "project_share_cu", "RML_WAVEFRAME": "waveframe", "RML_LINPLANE": "linplane", "RML_STAGE_CODES": "stage_codes",
                "RML_SLICE_WAVE": "slice_wave", "RML_DERIVE_FUSED": "derive_fused", "RML_CODE_RMW": "code_rmw", "RML_GEMM_BIG": "gemm_big",
-               "RML_CHUNK": "chunk", "RML_C1_PK": "c1_pk", "RML_SMO_LDS_ROWS": "smo_lds_rows"}
+               "RML_CHUNK": "chunk", "RML_C1_PK": "c1_pk", "RML_SMO_LDS_ROWS": "smo_lds_rows", "RML_SGD_RESIDENT_D": "sgd_resident_d"}
 AUG_ROTATE, AUG_ZOOM, AUG_NOISE = 0, 1, 2
 VOL_F32, VOL_U8 = 0, 1
 MODES = {"max": MODE_MAX, "slice": MODE_SLICE, "sum": MODE_SUM, "max_nan": MODE_MAX_NAN}
@@ -155,7 +164,8 @@ PATHS = {"auto": PATH_AUTO, "f32": PATH_F32, "i8": PATH_I8, "f64": PATH_F64, "di
 
 
 def option_id(name):
-    """RML_OPT_* id of an option name (a key of OPTIONS or SOLVER_OPTIONS)."""
+    """RML_OPT_* id of an option name (a key of OPTIONS or SOLVER_OPTIONS; the header's upper-case spelling is taken too)."""
+    name = name.lower()
     return OPTIONS[name] if name in OPTIONS else SOLVER_OPTIONS[name]
 
 

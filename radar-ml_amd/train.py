@@ -180,6 +180,29 @@ def _masked_params(candidates):
     return out
 
 
+def _cv_results(candidates, n_splits, fit_t, score_t, scores):
+    """``cv_results_`` in GridSearchCV's layout from (candidate, split) arrays of fit times, score times and test scores."""
+    res = {}
+
+    def store(name, arr, splits_=False, rank=False):
+        if splits_:
+            for s in range(n_splits):
+                res["split%d_%s" % (s, name)] = arr[:, s]
+        mean = np.average(arr, axis=1)
+        res["mean_%s" % name] = mean
+        res["std_%s" % name] = np.sqrt(np.average((arr - mean[:, None]) ** 2, axis=1))
+        if rank:
+            from scipy.stats import rankdata
+            res["rank_%s" % name] = rankdata(-mean, method="min").astype(np.int32, copy=False)
+
+    store("fit_time", fit_t)
+    store("score_time", score_t)
+    res.update(_masked_params(candidates))
+    res["params"] = candidates
+    store("test_score", scores, splits_=True, rank=True)
+    return res
+
+
 # ---- SVC.fit as one batch of duals: libsvm's svm_train with its Platt cross-validation (sk: = sklearn/svm/src/libsvm/svm.cpp) ----
 _FIT_CARRY = ("C", "class_weight", "tol", "shrinking", "max_iter", "probability", "random_state")
 _PLATT_FOLDS = 5
@@ -610,24 +633,7 @@ class GridSearchSVC:
                 for j in jobs:
                     j.result()
 
-        res = {}
-
-        def store(name, arr, splits_=False, rank=False):
-            if splits_:
-                for s in range(n_splits):
-                    res["split%d_%s" % (s, name)] = arr[:, s]
-            mean = np.average(arr, axis=1)
-            res["mean_%s" % name] = mean
-            res["std_%s" % name] = np.sqrt(np.average((arr - mean[:, None]) ** 2, axis=1))
-            if rank:
-                from scipy.stats import rankdata
-                res["rank_%s" % name] = rankdata(-mean, method="min").astype(np.int32, copy=False)
-
-        store("fit_time", fit_t)
-        store("score_time", score_t)
-        res.update(_masked_params(candidates))
-        res["params"] = candidates
-        store("test_score", scores, splits_=True, rank=True)
+        res = _cv_results(candidates, n_splits, fit_t, score_t, scores)
         self.cv_results_ = res
         self.n_splits_ = n_splits
         self.scorer_ = make_scorer(accuracy_score)
@@ -695,6 +701,528 @@ def find_best_svm_estimator(X, y, cv, random_seed, solver="host", refit_solver="
                        random_state=random_seed, cache_size=1000, verbose=False)
     grid_search = GridSearchSVC(estimator=init_est, param_grid=param_grid, verbose=2, n_jobs=4, cv=cv, solver=solver,
                                 refit_solver=refit_solver)
+    grid_search.fit(X, y)
+    logger.info('\n Best estimator:')
+    logger.info(grid_search.best_estimator_)
+    logger.info('\n Best score for {}-fold search:'.format(grid_search.n_splits_))
+    logger.info(grid_search.best_score_)
+    logger.info('\n Best hyperparameters:')
+    logger.info(grid_search.best_params_)
+    return grid_search.best_estimator_
+
+
+# ---- SGDClassifier(loss='log_loss').fit on the device (sk: = sklearn/linear_model/_stochastic_gradient.py, scikit-learn 1.7.2) ----
+# rml_sgd_problem / rml_sgd_fit of include/radarml.h
+SGD_PROBLEM = np.dtype([("n", "<i4"), ("penalty", "<i4"), ("average", "<i4"), ("max_iter", "<i4"), ("n_iter_no_change", "<i4"),
+                        ("shuffle", "<i4"), ("seed", "<u4"), ("warm", "<i4"), ("rows_off", "<i8"), ("y_off", "<i8"), ("out", "<i8"),
+                        ("alpha", "<f8"), ("l1_ratio", "<f8"), ("tol", "<f8"), ("weight_pos", "<f8"), ("weight_neg", "<f8"), ("t0", "<f8")])
+SGD_FIT = np.dtype([("prob0", "<i4"), ("n_test", "<i4"), ("test_off", "<i8")])
+_SGD_PENALTY = {"l1": _lib.SGD_L1, "l2": _lib.SGD_L2, "elasticnet": _lib.SGD_ELASTICNET}
+_SGD_GRID_KEYS = ("alpha", "penalty", "l1_ratio", "average", "max_iter", "tol", "n_iter_no_change", "shuffle")
+_SGD_OVERFLOW = "Floating-point under-/overflow occurred at epoch #%d. Scaling input data with StandardScaler or MinMaxScaler might help."
+_SGD_MAX_ITER = ("Maximum number of iteration reached before convergence. Consider increasing max_iter to improve the fit.")
+
+
+def sgd_shuffle(seed, perm):
+    """``rml_sgd_shuffle``: one ``SequentialDataset.shuffle(seed)`` pass (Fisher-Yates on scikit-learn's xorshift generator) over the
+    int32 index array ``perm``; returns the permuted copy."""
+    perm = np.array(perm, dtype=np.int32)
+    _lib.check(_lib.load().rml_sgd_shuffle(int(seed), len(perm), perm.ctypes.data), "rml_sgd_shuffle")
+    return perm
+
+
+def sgd_device(Xd, plan, device=None, check=True):
+    """``rml_sgd_solve`` + ``rml_sgd_score`` on the DEVICE rows ``Xd`` (an (N, D) float32 tensor with unit column stride; its row
+    stride is the ld of the C call) for ``plan``: a dict of
+    ``problems`` (SGD_PROBLEM records), ``rows`` / ``y`` (int32: the problems' rows and 0 / 1 labels), ``n_out`` (output slots),
+    ``fits`` (SGD_FIT records), ``test_rows`` / ``test_y`` (int32: held-out rows and their class indices), ``n_classes`` and, for
+    warm problems, ``init``: host arrays ``coef`` / ``avg_coef`` (n_out, D) and ``intercept`` / ``avg_intercept`` (n_out).
+    Returns host arrays ``intercept``, ``avg_intercept``, ``n_iter``, ``t``, ``status`` per slot, ``dec``, ``labels`` per held-out
+    row, ``correct`` per fit, ``solve_s`` / ``score_s`` (the wall time of the two batched calls), and ``coefs``: a function
+    slots -> host (coef, avg_coef) of those slots (the weights stay on the device until asked for).  A problem or a held-out row
+    that names a row outside the matrix raises RadarMLError (``check=False``: status -1 / label -1 are returned instead)."""
+    import torch
+    lib = _lib.load()
+    dev = _lib.device_of(device if device is not None else Xd.device)
+    ctx = _lib.context(dev)
+    probs = np.ascontiguousarray(plan["problems"], dtype=SGD_PROBLEM)
+    fits = np.ascontiguousarray(plan.get("fits", np.zeros(0, SGD_FIT)), dtype=SGD_FIT)
+    if Xd.dtype != torch.float32 or Xd.dim() != 2 or Xd.stride(1) != 1 or Xd.stride(0) < Xd.shape[1]:
+        raise ValueError("sgd_device: the rows are an (N, D) float32 tensor with unit column stride")
+    N, D, ld = int(Xd.shape[0]), int(Xd.shape[1]), int(Xd.stride(0))
+    n_out = int(plan["n_out"])
+    C = int(plan.get("n_classes", 2))
+    n_dec = 1 if C == 2 else C
+    with torch.cuda.device(dev):
+        i32 = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(dev)
+        rows, y = i32(plan["rows"]), i32(plan["y"])
+        te_rows, te_y = i32(plan.get("test_rows", np.zeros(0, np.int32))), i32(plan.get("test_y", np.zeros(0, np.int32)))
+        n_test = int(te_rows.numel())
+        init = plan.get("init")
+        f64 = lambda a, shape: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64).reshape(shape)).to(dev)
+        if init is None:
+            coef = torch.zeros((max(n_out, 1), D), dtype=torch.float64, device=dev)
+            avg_coef = torch.zeros_like(coef)
+            icpt = torch.zeros(max(n_out, 1), dtype=torch.float64, device=dev)
+            avg_icpt = torch.zeros_like(icpt)
+        else:
+            coef, avg_coef = f64(init["coef"], (n_out, D)), f64(init["avg_coef"], (n_out, D))
+            icpt, avg_icpt = f64(init["intercept"], (n_out,)), f64(init["avg_intercept"], (n_out,))
+        n_iter = torch.zeros(max(n_out, 1), dtype=torch.int32, device=dev)
+        t = torch.zeros(max(n_out, 1), dtype=torch.float64, device=dev)
+        status = torch.zeros(max(n_out, 1), dtype=torch.int32, device=dev)
+        dec = torch.zeros(max(n_test * n_dec, 1), dtype=torch.float64, device=dev)
+        labels = torch.zeros(max(n_test, 1), dtype=torch.int32, device=dev)
+        correct = torch.zeros(max(len(fits), 1), dtype=torch.int32, device=dev)
+        st = _lib.stream_ptr(dev)
+        torch.cuda.synchronize(dev)
+        t0 = time.perf_counter()
+        _lib.check(lib.rml_sgd_solve(ctx, _lib.ptr(Xd), N, D, ld, probs.ctypes.data, len(probs), _lib.ptr(rows), int(rows.numel()),
+                                     _lib.ptr(y), int(y.numel()), n_out, _lib.ptr(coef), _lib.ptr(avg_coef), _lib.ptr(icpt),
+                                     _lib.ptr(avg_icpt), _lib.ptr(n_iter), _lib.ptr(t), _lib.ptr(status), st), "rml_sgd_solve")
+        torch.cuda.synchronize(dev)
+        t1 = time.perf_counter()
+        if len(fits):
+            _lib.check(lib.rml_sgd_score(ctx, _lib.ptr(Xd), N, D, ld, probs.ctypes.data, len(probs), n_out, _lib.ptr(coef),
+                                         _lib.ptr(avg_coef), _lib.ptr(icpt), _lib.ptr(avg_icpt), _lib.ptr(t), C, fits.ctypes.data,
+                                         len(fits), _lib.ptr(te_rows), _lib.ptr(te_y), n_test, _lib.ptr(dec), _lib.ptr(labels),
+                                         _lib.ptr(correct), st), "rml_sgd_score")
+        torch.cuda.synchronize(dev)
+        t2 = time.perf_counter()
+
+        def coefs(slots):
+            with torch.cuda.device(dev):
+                idx = torch.as_tensor(list(slots), dtype=torch.long, device=dev)
+                return coef[idx].cpu().numpy(), avg_coef[idx].cpu().numpy()
+
+        out = {"intercept": icpt.cpu().numpy()[:n_out], "avg_intercept": avg_icpt.cpu().numpy()[:n_out],
+               "n_iter": n_iter.cpu().numpy()[:n_out], "t": t.cpu().numpy()[:n_out], "status": status.cpu().numpy()[:n_out],
+               "dec": dec.cpu().numpy()[:n_test * n_dec].reshape(n_test, n_dec), "labels": labels.cpu().numpy()[:n_test],
+               "correct": correct.cpu().numpy()[:len(fits)], "solve_s": t1 - t0, "score_s": t2 - t1, "coefs": coefs}
+    if check and (out["status"][probs["out"]] < 0).any():
+        raise _lib.RadarMLError("rml_sgd_solve: a problem names a row outside the matrix")
+    if check and (out["labels"] < 0).any():
+        raise _lib.RadarMLError("rml_sgd_score: a held-out row outside the matrix")
+    return out
+
+
+def _sgd(X, plan, device=None):
+    """The float32 host rows ``X`` uploaded ONCE, every problem of ``plan`` solved on them in one ``rml_sgd_solve`` call and every
+    held-out row scored in one ``rml_sgd_score`` call (``sgd_device``).  Returns ``sgd_device``'s dict plus ``solve``: a function
+    plan -> ``sgd_device``'s dict of another plan on the same resident rows (the refit of a search's winner).
+
+    All device work of the SGD fits and of their search goes through this function (tests replace it to run the logic without a GPU)."""
+    import torch
+    dev = _lib.device_of(device)
+    with torch.cuda.device(dev):
+        Xd = torch.from_numpy(np.ascontiguousarray(X, dtype=np.float32)).to(dev)
+        out = sgd_device(Xd, plan, dev)
+    out["solve"] = lambda plan2: sgd_device(Xd, plan2, dev)
+    return out
+
+
+def _sgd_seeds(random_state, n_classes):
+    """The shuffle seed of each binary problem of one ``SGDClassifier.fit`` / ``partial_fit``, drawn as scikit-learn draws them: for
+    more than two classes _fit_multiclass draws one seed per class (sk:784-785) and fit_binary makes a generator from each; for two
+    classes fit_binary takes ``random_state`` itself (sk:736-751).  From that generator the first draw seeds the dataset
+    (make_dataset; unused by the solver) and the second is the shuffle seed (sk:460)."""
+    from sklearn.utils import check_random_state
+    max_int = np.iinfo(np.int32).max
+    if n_classes == 2:
+        states = [check_random_state(random_state)]
+    else:
+        states = [check_random_state(s) for s in check_random_state(random_state).randint(max_int, size=n_classes)]
+    seeds = []
+    for rs in states:
+        rs.randint(1, max_int)
+        seeds.append(int(rs.randint(max_int)))
+    return seeds
+
+
+def _sgd_params(params, who):
+    """The solver's view of SGDClassifier parameters; raises for what the device fit does not do, before any device work."""
+    loss = params["loss"]
+    if loss not in ("log_loss", "log"):
+        raise NotImplementedError("%s: loss=%r (the device fit is logistic regression, loss='log_loss')" % (who, loss))
+    if params["learning_rate"] != "optimal":
+        raise NotImplementedError("%s: learning_rate=%r (the device fit runs the 'optimal' schedule)" % (who, params["learning_rate"]))
+    if params["early_stopping"]:
+        raise NotImplementedError("%s: early_stopping=True" % who)
+    if not params["fit_intercept"]:
+        raise NotImplementedError("%s: fit_intercept=False" % who)
+    if params["penalty"] not in _SGD_PENALTY:
+        raise NotImplementedError("%s: penalty=%r (l2, l1 or elasticnet)" % (who, params["penalty"]))
+    alpha = float(params["alpha"])
+    if not (alpha > 0 and np.isfinite(alpha)):
+        raise ValueError("alpha must be > 0 since learning_rate is 'optimal'. alpha is used to compute the optimal learning rate.")
+    l1_ratio = 0.15 if params["l1_ratio"] is None else float(params["l1_ratio"])
+    if not 0 <= l1_ratio <= 1:
+        raise ValueError("l1_ratio must be in [0, 1], got %r" % (params["l1_ratio"],))
+    average = params["average"]
+    average = int(average) if isinstance(average, (bool, np.bool_)) or float(average) == int(average) else -1
+    if average < 0:
+        raise ValueError("average must be a bool or a non-negative integer, got %r" % (params["average"],))
+    max_iter, n_nc = int(params["max_iter"]), int(params["n_iter_no_change"])
+    if max_iter < 1 or n_nc < 1:
+        raise ValueError("max_iter and n_iter_no_change must be >= 1, got %r and %r" % (params["max_iter"], params["n_iter_no_change"]))
+    tol = params["tol"]
+    return {"penalty": _SGD_PENALTY[params["penalty"]], "alpha": alpha, "l1_ratio": l1_ratio, "average": average, "max_iter": max_iter,
+            "tol": -np.inf if tol is None else float(tol), "n_iter_no_change": n_nc, "shuffle": int(bool(params["shuffle"]))}
+
+
+def _sgd_problem(prm, n, seed, rows_off, y_off, out, weight_pos, weight_neg, t0=1.0, warm=0, max_iter=None):
+    return (n, prm["penalty"], prm["average"], prm["max_iter"] if max_iter is None else max_iter, prm["n_iter_no_change"], prm["shuffle"],
+            seed, warm, rows_off, y_off, out, prm["alpha"], prm["l1_ratio"], prm["tol"], weight_pos, weight_neg, t0)
+
+
+def _sgd_check_rows(who, n):
+    if n > _lib.SGD_MAX_ROWS:
+        raise NotImplementedError("%s: %d training rows (rml_sgd_solve takes at most %d per problem)" % (who, n, _lib.SGD_MAX_ROWS))
+
+
+def _sgd_run(est, y, max_iter, run, who):
+    """``BaseSGDClassifier._partial_fit`` (sk:583-666) after its validation, on an estimator whose ``classes_``, parameter arrays and
+    ``t_`` are in place: one problem per class (one for two classes) from the estimator's current state, solved by ``run(plan)``
+    (``_sgd`` or its ``solve`` hook on rows 0 .. len(y)-1), and the results stored by the statements of fit_binary, _fit_binary and
+    _fit_multiclass (sk:497-503, 753-768, 807-823) on the estimator's own arrays, so that what they alias stays aliased."""
+    from sklearn.utils.class_weight import compute_class_weight
+    prm = _sgd_params(est.get_params(), who)
+    classes = est.classes_
+    nc, n = len(classes), len(y)
+    _sgd_check_rows(who, n)
+    yi = np.searchsorted(classes, y)
+    if ((yi >= nc) | (classes[np.minimum(yi, nc - 1)] != y)).any():
+        raise ValueError("%s: y holds labels outside classes_ %r" % (who, classes))
+    est._expanded_class_weight = compute_class_weight(est.class_weight, classes=classes, y=y)
+    positives = [1] if nc == 2 else list(range(nc))
+    seeds = _sgd_seeds(est.random_state, nc)
+    avg = prm["average"] > 0
+    D = est.coef_.shape[-1]
+
+    def state(c):                       # _prepare_fit_binary (sk:348-365): views of the estimator's arrays
+        if nc == 2:
+            return ((est._standard_coef.ravel(), est._standard_intercept, est._average_coef.ravel(), est._average_intercept) if avg
+                    else (est.coef_.ravel(), est.intercept_, None, None)), 0
+        return ((est._standard_coef[c], est._standard_intercept, est._average_coef[c], est._average_intercept) if avg
+                else (est.coef_[c], est.intercept_, None, None)), c
+
+    K = len(positives)
+    init = {"coef": np.zeros((K, D)), "avg_coef": np.zeros((K, D)), "intercept": np.zeros(K), "avg_intercept": np.zeros(K)}
+    problems, ys = [], []
+    for k, c in enumerate(positives):
+        (coef, icpt, acoef, aicpt), j = state(c)
+        init["coef"][k], init["intercept"][k] = coef, icpt[j]
+        if avg:
+            init["avg_coef"][k], init["avg_intercept"][k] = acoef, aicpt[j]
+        wpos = est._expanded_class_weight[c]
+        wneg = est._expanded_class_weight[0] if nc == 2 else 1.0
+        problems.append(_sgd_problem(prm, n, seeds[k], 0, k * n, k, wpos, wneg, t0=float(est.t_), warm=1, max_iter=max_iter))
+        ys.append((yi == c).astype(np.int32))
+    plan = {"problems": np.array(problems, dtype=SGD_PROBLEM), "rows": np.arange(n, dtype=np.int32), "y": np.concatenate(ys),
+            "n_out": K, "init": init, "n_classes": nc}
+    out = run(plan)
+    if (out["status"] == 2).any():
+        raise ValueError(_SGD_OVERFLOW % int(out["n_iter"][np.nonzero(out["status"] == 2)[0][0]]))
+    coefs, acoefs = out["coefs"](range(K))
+    n_iter_ = 0
+    for k, c in enumerate(positives):
+        (coef, _, acoef, aicpt), j = state(c)
+        coef[:] = coefs[k]
+        if avg:
+            acoef[:] = acoefs[k]
+            aicpt[j] = out["avg_intercept"][k]
+        n_iter_ = max(n_iter_, int(out["n_iter"][k]))
+    if nc == 2:
+        intercept = float(out["intercept"][0])
+        est.t_ += n_iter_ * n
+        est.n_iter_ = n_iter_
+        if avg:
+            if prm["average"] <= est.t_ - 1:
+                est.coef_ = est._average_coef.reshape(1, -1)
+                est.intercept_ = est._average_intercept
+            else:
+                est.coef_ = est._standard_coef.reshape(1, -1)
+                est._standard_intercept = np.atleast_1d(intercept)
+                est.intercept_ = est._standard_intercept
+        else:
+            est.coef_ = est.coef_.reshape(1, -1)
+            est.intercept_ = np.atleast_1d(intercept)
+    else:
+        for k in range(K):
+            est.intercept_[k] = out["intercept"][k]
+        est.t_ += n_iter_ * n
+        est.n_iter_ = n_iter_
+        if avg:
+            if prm["average"] <= est.t_ - 1.0:
+                est.coef_ = est._average_coef
+                est.intercept_ = est._average_intercept
+            else:
+                est.coef_ = est._standard_coef
+                est._standard_intercept = np.atleast_1d(est.intercept_)
+                est.intercept_ = est._standard_intercept
+    return est
+
+
+def _sgd_prepare(est, who):
+    """Type and parameter checks of an estimator for the device fit (before any device work); the reference's old spelling
+    ``loss='log'`` and its float ``max_iter`` are rewritten to what scikit-learn 1.7 takes."""
+    from sklearn.linear_model import SGDClassifier
+    if type(est) is not SGDClassifier:
+        raise NotImplementedError("%s fits sklearn.linear_model.SGDClassifier, not %s" % (who, type(est).__name__))
+    prm = _sgd_params(est.get_params(), who)
+    est.set_params(loss="log_loss", max_iter=prm["max_iter"])
+    return prm
+
+
+def _sgd_fit(est, X32, y, run, who):
+    """``BaseSGDClassifier._fit`` (sk:668-734) of a prepared estimator on validated rows, the solver run by ``run``."""
+    import warnings
+    from sklearn.exceptions import ConvergenceWarning
+    classes = np.unique(y)
+    if not 2 <= len(classes) <= 8:
+        raise ValueError("%s takes 2..8 classes, got %d" % (who, len(classes)))
+    for name in ("classes_", "_standard_coef", "_standard_intercept", "_average_coef", "_average_intercept"):
+        if hasattr(est, name):
+            delattr(est, name)
+    est.coef_ = est.intercept_ = None
+    est.t_ = 1.0
+    est.classes_ = classes
+    est.n_features_in_ = X32.shape[1]
+    est._allocate_parameter_mem(n_classes=len(classes), n_features=X32.shape[1], input_dtype=np.float64)
+    est._loss_function_ = est._get_loss_function(est.loss)
+    _sgd_run(est, y, est.max_iter, run, who)
+    if est.tol is not None and est.tol > -np.inf and est.n_iter_ == est.max_iter:
+        warnings.warn(_SGD_MAX_ITER, ConvergenceWarning)
+    return est
+
+
+def _check_y(X32, y):
+    y = np.asarray(y)
+    if y.ndim != 1 or y.shape[0] != X32.shape[0]:
+        raise ValueError("Found input variables with inconsistent numbers of samples: [%d, %d]" % (X32.shape[0], len(y)))
+    return y
+
+
+def fit_sgd(estimator, X, y, device=None):
+    """``estimator.fit(X, y)`` for an unfitted ``sklearn.linear_model.SGDClassifier`` on the GPU: one ``rml_sgd_solve`` call, one
+    workgroup per class (one for two classes) running scikit-learn's ``_plain_sgd64``.  Supported: ``loss='log_loss'`` (or the old
+    spelling ``'log'``), ``learning_rate='optimal'``, ``early_stopping=False``, ``fit_intercept=True``, 2..8 classes; honoured:
+    ``penalty``, ``alpha``, ``l1_ratio``, ``average``, ``max_iter`` (through ``int()``), ``tol``, ``n_iter_no_change``, ``shuffle``,
+    ``random_state``, ``class_weight``; anything else raises ``NotImplementedError``; ``sample_weight`` and sparse rows are not
+    supported.  Apart from the summation order of the dot product the arithmetic is scikit-learn's.  Returns the estimator, fitted:
+    a genuine ``SGDClassifier`` that predicts, pickles, calibrates and converts (``from_sklearn``) like any other; it warns
+    (``ConvergenceWarning``) and raises (``ValueError`` on overflow) where scikit-learn would."""
+    _sgd_prepare(estimator, "fit_sgd")
+    X32 = _rows(X)
+    y = _check_y(X32, y)
+    _sgd_check_rows("fit_sgd", len(y))
+    return _sgd_fit(estimator, X32, y, lambda plan: _sgd(X32, plan, device), "fit_sgd")
+
+
+def partial_fit_sgd(estimator, X, y, classes=None, device=None):
+    """``estimator.partial_fit(X, y, classes)`` on the GPU, as train.py:432 calls it: one epoch from the estimator's current state
+    (its weights, ``t_`` and the averaged weights carried over).  The estimator and its restrictions are ``fit_sgd``'s."""
+    who = "partial_fit_sgd"
+    _sgd_prepare(estimator, who)
+    X32 = _rows(X)
+    y = _check_y(X32, y)
+    est = estimator
+    if not hasattr(est, "classes_"):
+        if est.class_weight == "balanced":
+            raise ValueError("class_weight 'balanced' is not supported for partial_fit. In order to use 'balanced' weights, use "
+                             "compute_class_weight('balanced', classes=classes, y=y).")
+        if classes is None:
+            raise ValueError("classes must be passed on the first call to partial_fit.")
+        est.classes_ = np.unique(np.asarray(classes))
+        if not 2 <= len(est.classes_) <= 8:
+            raise ValueError("%s takes 2..8 classes, got %d" % (who, len(est.classes_)))
+        est.n_features_in_ = X32.shape[1]
+    elif classes is not None and not np.array_equal(est.classes_, np.unique(np.asarray(classes))):
+        raise ValueError("`classes=%r` is not the same as on last call to partial_fit, was: %r" % (classes, est.classes_))
+    if getattr(est, "coef_", None) is None:
+        est._allocate_parameter_mem(n_classes=len(est.classes_), n_features=X32.shape[1], input_dtype=np.float64)
+    elif X32.shape[1] != est.coef_.shape[-1]:
+        raise ValueError("Number of features %d does not match previous data %d." % (X32.shape[1], est.coef_.shape[-1]))
+    est._loss_function_ = est._get_loss_function(est.loss)
+    if not hasattr(est, "t_"):
+        est.t_ = 1.0
+    return _sgd_run(est, y, 1, lambda plan: _sgd(X32, plan, device), who)
+
+
+class GridSearchSGD:
+    """``GridSearchCV(SGDClassifier(loss='log_loss'), param_grid)`` on the GPU: the counterpart of ``GridSearchSVC`` for the
+    reference's default model, with the same subset of ``GridSearchCV``'s surface (``fit(X, y)``, ``best_estimator_``,
+    ``best_params_``, ``best_score_``, ``best_index_``, ``cv_results_``, ``n_splits_``, ``refit_time_``, ``scorer_``: accuracy).
+
+    The rows are uploaded once.  Every candidate (``ParameterGrid`` order) x split x class is one problem of ONE ``rml_sgd_solve``
+    call, every held-out row is scored by ONE ``rml_sgd_score`` call from the weights where the solve left them, and the winner is
+    refitted on all rows by one more solve on the resident rows (``fit_sgd``'s path).  The grid may vary ``alpha``, ``penalty``,
+    ``l1_ratio``, ``average``, ``max_iter``, ``tol``, ``n_iter_no_change`` and ``shuffle``; everything else is the base estimator's,
+    under ``fit_sgd``'s restrictions.  ``class_weight`` is formed per fold as scikit-learn forms it.  The batch has no per-fit
+    times: ``fit_time`` / ``score_time`` are the batch's solve / score time divided evenly among its fits."""
+
+    def __init__(self, estimator, param_grid, cv=5, refit=True, device=None, scoring=None, verbose=0, n_jobs=None):
+        self.estimator = estimator
+        self.param_grid = param_grid
+        self.cv = cv
+        self.refit = refit
+        self.device = device
+        self.scoring = scoring
+        self.verbose = verbose
+        self.n_jobs = n_jobs                # accepted for GridSearchCV's signature; the batch is one launch whatever it says
+
+    def _check(self):
+        from sklearn.linear_model import SGDClassifier
+        from sklearn.model_selection import ParameterGrid
+        if type(self.estimator) is not SGDClassifier:
+            raise NotImplementedError("GridSearchSGD searches sklearn.linear_model.SGDClassifier, not %s" % type(self.estimator).__name__)
+        if self.scoring not in (None, "accuracy"):
+            raise NotImplementedError("GridSearchSGD scores by accuracy (GridSearchCV's default for a classifier), not %r" % (self.scoring,))
+        if callable(self.refit) or not isinstance(self.refit, bool):
+            raise NotImplementedError("GridSearchSGD: refit must be True or False, not %r" % (self.refit,))
+        grids = [self.param_grid] if isinstance(self.param_grid, dict) else list(self.param_grid)
+        for g in grids:
+            bad = sorted(set(g) - set(_SGD_GRID_KEYS))
+            if bad:
+                raise NotImplementedError("GridSearchSGD searches %s, not %s" % (", ".join(_SGD_GRID_KEYS), ", ".join(bad)))
+        candidates = list(ParameterGrid(self.param_grid))
+        base = self.estimator.get_params()
+        prms = [_sgd_params(dict(base, **p), "GridSearchSGD") for p in candidates]
+        return candidates, base, prms
+
+    def _plan(self, prms, base, splits, y):
+        """The batch of the search for ``_sgd``: per candidate and split one fit of one problem per class (one for two classes), on
+        the split's shared row list and per-class label lists.  Returns (plan, [(ci, si) of fit f])."""
+        from sklearn.utils.class_weight import compute_class_weight
+        classes = np.unique(y)
+        nc = len(classes)
+        yi = np.searchsorted(classes, y).astype(np.int32)
+        positives = [1] if nc == 2 else list(range(nc))
+        rows, ys, test_rows, test_y, per_split = [], [], [], [], []
+        n_rows = n_y = 0
+        for tr, te in splits:
+            if len(np.unique(yi[tr])) < nc:
+                raise NotImplementedError("GridSearchSGD: a split whose training rows miss a class (scikit-learn fits a model of fewer "
+                                          "classes there)")
+            _sgd_check_rows("GridSearchSGD", len(tr))
+            w = compute_class_weight(base["class_weight"], classes=classes, y=y[tr])
+            y_offs = []
+            for c in positives:
+                ys.append((yi[tr] == c).astype(np.int32))
+                y_offs.append(n_y)
+                n_y += len(tr)
+            per_split.append((n_rows, y_offs, w))
+            rows.append(tr)
+            n_rows += len(tr)
+        problems, fits, which = [], [], []
+        n_test = 0
+        for ci, prm in enumerate(prms):
+            for si, (tr, te) in enumerate(splits):
+                rows_off, y_offs, w = per_split[si]
+                seeds = _sgd_seeds(base["random_state"], nc)
+                fits.append((len(problems), len(te), n_test))
+                which.append((ci, si))
+                test_rows.append(te)
+                test_y.append(yi[te])
+                n_test += len(te)
+                for k, c in enumerate(positives):
+                    problems.append(_sgd_problem(prm, len(tr), seeds[k], rows_off, y_offs[k], len(problems), w[c],
+                                                 w[0] if nc == 2 else 1.0))
+        cat = lambda parts: np.concatenate(parts).astype(np.int32) if parts else np.zeros(0, np.int32)
+        plan = {"problems": np.array(problems, dtype=SGD_PROBLEM), "rows": cat(rows), "y": cat(ys), "n_out": len(problems),
+                "fits": np.array(fits, dtype=SGD_FIT), "test_rows": cat(test_rows), "test_y": cat(test_y), "n_classes": nc}
+        return plan, which
+
+    def fit(self, X, y):
+        import warnings
+        from sklearn.base import clone
+        from sklearn.exceptions import ConvergenceWarning
+        from sklearn.metrics import accuracy_score, make_scorer
+        from sklearn.model_selection import check_cv
+        candidates, base, prms = self._check()
+        X32 = _rows(X)
+        y = _check_y(X32, y)
+        if not 2 <= len(np.unique(y)) <= 8:
+            raise ValueError("GridSearchSGD takes 2..8 classes, got %d" % len(np.unique(y)))
+        cv = check_cv(self.cv, y, classifier=True)
+        splits = [(np.asarray(tr), np.asarray(te)) for tr, te in cv.split(X32, y)]
+        n_splits = len(splits)
+        if n_splits == 0 or not candidates:
+            raise ValueError("No fits were performed. Was the CV iterator empty? Were there no candidates?")
+        if self.verbose > 0:
+            print("Fitting %d folds for each of %d candidates, totalling %d fits" % (n_splits, len(candidates),
+                                                                                   n_splits * len(candidates)), flush=True)
+        plan, which = self._plan(prms, base, splits, y)
+        out = _sgd(X32, plan, self.device)
+        if (out["status"] == 2).any():
+            raise ValueError(_SGD_OVERFLOW % int(out["n_iter"][np.nonzero(out["status"] == 2)[0][0]]))
+        probs = plan["problems"]
+        if ((probs["tol"] > -np.inf) & (out["n_iter"][probs["out"]] == probs["max_iter"])).any():
+            warnings.warn(_SGD_MAX_ITER, ConvergenceWarning)
+        scores = np.zeros((len(candidates), n_splits))
+        fit_t = np.full_like(scores, out["solve_s"] / len(which))
+        score_t = np.full_like(scores, out["score_s"] / len(which))
+        for f, (ci, si) in enumerate(which):
+            scores[ci, si] = float(out["correct"][f]) / len(splits[si][1])
+            if self.verbose > 1:
+                p = candidates[ci]
+                print("[CV %d/%d] END %s; total time=%5.1fs" % (si + 1, n_splits, ", ".join("%s=%s" % (k, p[k]) for k in sorted(p)),
+                                                             fit_t[ci, si] + score_t[ci, si]), flush=True)
+        res = _cv_results(candidates, n_splits, fit_t, score_t, scores)
+        self.cv_results_ = res
+        self.n_splits_ = n_splits
+        self.scorer_ = make_scorer(accuracy_score)
+        self.multimetric_ = False
+        self.best_index_ = int(res["rank_test_score"].argmin())
+        self.best_score_ = float(res["mean_test_score"][self.best_index_])
+        self.best_params_ = candidates[self.best_index_]
+        self.solve_time_, self.score_time_ = out["solve_s"], out["score_s"]
+        if self.refit:
+            est = clone(self.estimator).set_params(**self.best_params_)
+            _sgd_prepare(est, "GridSearchSGD")
+            t0 = time.perf_counter()
+            self.best_estimator_ = _sgd_fit(est, X32, y, out["solve"], "GridSearchSGD")
+            self.refit_time_ = time.perf_counter() - t0
+        self.classes_ = np.unique(y)
+        return self
+
+    # GridSearchCV delegates these to best_estimator_
+    def predict(self, X):
+        return self.best_estimator_.predict(X)
+
+    def decision_function(self, X):
+        return self.best_estimator_.decision_function(X)
+
+    def predict_proba(self, X):
+        return self.best_estimator_.predict_proba(X)
+
+    def score(self, X, y):
+        return self.best_estimator_.score(X, y)
+
+
+def find_best_sgd_svm_estimator(X, y, cv, random_seed, device=None):
+    """Exhaustive search over specified parameter values for svm using sgd (train.py:350-381, the same grid, base estimator and
+    log lines), every fit of the search and the refit on the GPU (GridSearchSGD).
+
+    Returns:
+        optimized svm estimator.
+    """
+    from sklearn import linear_model
+    max_iter = max(np.ceil(10**6 / len(X)), 1000)
+    small_alphas = [10.0e-08, 10.0e-09, 10.0e-10]
+    alphas = [10.0e-04, 10.0e-05, 10.0e-06, 10.0e-07]
+    l1_ratios = [0.075, 0.15, 0.30]
+    param_grid = [
+        {'alpha': alphas, 'penalty': ['l1', 'l2'], 'average': [False]},
+        {'alpha': alphas, 'penalty': ['elasticnet'], 'average': [False],
+         'l1_ratio': l1_ratios},
+        {'alpha': small_alphas, 'penalty': ['l1', 'l2'], 'average': [True]},
+        {'alpha': small_alphas, 'penalty': ['elasticnet'], 'average': [True],
+         'l1_ratio': l1_ratios}
+    ]
+    init_est = linear_model.SGDClassifier(loss='log', max_iter=max_iter,
+                                          random_state=random_seed, n_jobs=-1, warm_start=True)
+    grid_search = GridSearchSGD(estimator=init_est, param_grid=param_grid, verbose=2, n_jobs=-1, cv=cv, device=device)
     grid_search.fit(X, y)
     logger.info('\n Best estimator:')
     logger.info(grid_search.best_estimator_)
