@@ -625,6 +625,44 @@ int rml_dnn_dense_tail_f32(rml_ctx* ctx, const float* feat, int64_t ld_feat, int
                            const float* w2t, const float* b2, const float* w3, const float* b3, int n_classes, float* workspace,
                            int64_t workspace_bytes, float* proba, void* stream);
 
+/* ---- dnn.py training step (dnn.py:347-390: model.fit on the model of dnn.py:45-91), float32 -----------------------------------
+ * One step on the batch rows[0..B) of RESIDENT data: three float32 plane sets xz / yz / xy, [N][H][W] each, already scaled to
+ * [-1, 1] and resized (H, W multiples of 4, W <= 128: rml_dnn_train_supported; others RML_ERR_UNSUPPORTED), labels [N] int32 in
+ * [0, C), 2 <= C <= 16.  rows: DEVICE int32, B entries in [0, N), 1 <= B <= RML_DNN_TRAIN_MAX_BATCH; no gather copy is made.
+ * Forward: per branch conv 1->64 3x3 stride 2 relu, conv 64->32 3x3 stride 2 relu (TF 'same': pad bottom / right), the branches
+ * concatenated on the channel axis, Flatten in NHWC order (K = (H/4)(W/4)*96), Dense 64 relu, dropout, Dense 64 relu, dropout,
+ * Dense C; loss_b = class_weight[y_b] * (logsumexp(z_b) - z_b[y_b]) (class_weight: DEVICE float32 [C], NULL = ones), the batch
+ * loss is sum_b loss_b / B (Keras' class_weight under SUM_OVER_BATCH_SIZE).  All operands and sums are float32.
+ *   params: HOST array of 18 DEVICE pointers in the order of the torch module's parameters(): per branch (xz, yz, xy) k1
+ *   [64][1][3][3], b1 [64], k2 [32][64][3][3], b2 [32]; then W [64][K], b [64]; W [64][64], b [64]; W [C][64], b [C] (torch Linear:
+ *   out x in).  k2_layout 0: k2 dense in (out, in, ky, kx) order; 1: channels_last, (out, ky, kx, in).
+ *   grads (mode TRAIN): 18 DEVICE pointers, the same shapes and layouts; every element is overwritten with d(batch loss)/d(param).
+ *   Dropout: unit j of dropout layer l (0, 1) of the sample at batch position b is kept iff a uniform draw that is a function of
+ *   (seed, step, l, b, j) only -- not of B, not of the launch geometry -- is >= rate; kept units are scaled by 1 / (1 - rate);
+ *   0 <= rate < 1.  rml_dnn_dropout_mask (HOST, no device, no context): keep[j] = 1 / 0 for j < n_units, the same function.
+ *   mode RML_DNN_EVAL: the same forward without dropout, no gradients (grads may be NULL).
+ *   Both modes: *loss_sum (DEVICE double) += sum_b loss_b (not divided by B), *correct (DEVICE int32) += #{b: first argmax_c z_b[c]
+ *   == y_b}: zero them where an epoch starts, read them once where it ends.
+ *   status (DEVICE int32, zeroed by the caller): set to -1 when a row index is outside [0, N) or a label outside [0, C); the step
+ *   then reads no plane, writes no gradient and leaves the accumulators alone.
+ *   workspace: rml_dnn_train_workspace_bytes(B, H, W, C) bytes, 16-byte aligned (0 is returned for unsupported arguments); the size
+ *   for B covers every batch of up to B samples (non-decreasing in B), so one workspace serves an epoch's partial last batch too.
+ * Every sum over the batch or over pixels has one owner and a fixed order (per-workgroup partial sums, then an ordered
+ * reduction; no atomics): the same call on the same inputs gives the same bits.  Asynchronous on `stream`.  The update itself is
+ * rml_adam_step below (torch.optim.Adam's form: epsilon inside the bias correction of the denominator, where Keras adds it
+ * outside -- Keras' epsilon is this one's divided by sqrt(1 - beta2^t), so the two updates differ only where sqrt(v) is itself of the
+ * order of eps = 1e-7). */
+#define RML_DNN_TRAIN 0
+#define RML_DNN_EVAL 1
+#define RML_DNN_TRAIN_MAX_BATCH 64
+int rml_dnn_train_supported(int H, int W, int C);
+int64_t rml_dnn_train_workspace_bytes(int B, int H, int W, int C);
+int rml_dnn_train_step(rml_ctx* ctx, const float* xz, const float* yz, const float* xy, const int32_t* labels, const int32_t* rows,
+                       int B, int64_t N, int H, int W, const float* class_weight, int C, const void* const* params,
+                       void* const* grads, int k2_layout, uint64_t seed, int64_t step, float rate, int mode, void* workspace,
+                       int64_t workspace_bytes, double* loss_sum, int32_t* correct, int32_t* status, void* stream);
+int rml_dnn_dropout_mask(uint64_t seed, int64_t step, int layer, int b, int n_units, float rate, uint8_t* keep);
+
 /* ---- SGAN discriminator branches: fused BatchNorm(train) + LeakyReLU + 'same' pad (sgan.py:137-158) -------------
  * x: N x H x W x C (NHWC, dense) float16 (dtype 0) or bfloat16 (dtype 1), the convolution output; y: N x (H+pad_h) x
  * (W+pad_w) x C, the zero-padded input of the next stride-2 'same' convolution (pad 0: plain output).  Batch

@@ -26,4 +26,13 @@ __all__ = [
     "classifier", "classify_batch", "calc_proj_zoom", "synth_volumes",
     "DataGenerator", "augment_planes", "rotation_params", "GridSearchSVC", "find_best_svm_estimator", "fit_svc",
     "GridSearchSGD", "find_best_sgd_svm_estimator", "fit_sgd", "partial_fit_sgd",
+    "define_classifier", "train_classifier",
 ]
+
+
+def __getattr__(name):
+    # the CNN of dnn.py -- model, fit and the reference's train() -- imported on first use: dnn.py pulls in torch.nn
+    if name in ("define_classifier", "train_classifier"):
+        from . import dnn
+        return dnn.define_classifier if name == "define_classifier" else dnn.train
+    raise AttributeError("module %r has no attribute %r" % (__name__, name))

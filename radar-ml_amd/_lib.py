@@ -115,6 +115,12 @@ SIGNATURES = {
     "rml_dnn_dense_tail_f32_workspace_bytes": (c_int64, [c_int64, c_int64]),
     "rml_dnn_dense_tail_f32": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                        c_void_p, c_int, c_void_p, c_int64, c_void_p, c_void_p]),
+    "rml_dnn_train_supported": (c_int, [c_int, c_int, c_int]),
+    "rml_dnn_train_workspace_bytes": (c_int64, [c_int, c_int, c_int, c_int]),
+    "rml_dnn_train_step": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_void_p, c_int,
+                                   c_void_p, c_void_p, c_int, c_uint64, c_int64, c_float, c_int, c_void_p, c_int64, c_void_p, c_void_p,
+                                   c_void_p, c_void_p]),
+    "rml_dnn_dropout_mask": (c_int, [c_uint64, c_int64, c_int, c_int, c_int, c_float, c_void_p]),
     "rml_bn_workspace_floats": (c_int64, [c_void_p, c_int]),
     "rml_bn_lrelu_pad_forward": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
                                          c_float, c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
@@ -149,6 +155,8 @@ SMO_LDS_ROWS_MAX = 2768
 SGD_RESIDENT_D_MAX = 10240
 SGD_MAX_ROWS = 8192
 SGD_L1, SGD_L2, SGD_ELASTICNET = 1, 2, 3
+DNN_TRAIN, DNN_EVAL = 0, 1
+DNN_TRAIN_MAX_BATCH = 64
 # A/B runs from a shell (tools/profile_round.sh, tools/kbench.py under rocprofv3): these environment variables are read ONCE, here in
 # Python, when a context is created, and applied as options -- the library itself never reads the environment
 ENV_OPTIONS = {"RML_WAVE_SHARE": "project_share_cu", "RML_WAVEFRAME": "waveframe", "RML_LINPLANE": "linplane", "RML_STAGE_CODES": "stage_codes",

@@ -1,4 +1,5 @@
-"""Multi-view CNN classifier of the reference's ``dnn.py`` (forward pass) on PyTorch-ROCm.
+"""Multi-view CNN classifier of the reference's ``dnn.py`` on PyTorch-ROCm: the forward pass, and its training (``Classifier.fit``,
+:func:`train`: one float32 HIP step per batch, csrc/dnn_train.hip + csrc/optim.hip).
 
 Architecture (dnn.py:45-91; shapes in images/dnn_model.png): per projection branch
 Conv2D(64, 3x3, stride 2, 'same', relu) -> Conv2D(32, 3x3, stride 2, 'same', relu); concatenate the three
@@ -26,6 +27,205 @@ def rescore_route(n_rows, N, fused, host):
     if n_rows is None:
         return "all"
     return "gather" if sparse else "dense_blocks"
+
+
+class History:
+    """What Keras' ``model.fit`` returns: ``.history`` maps loss / accuracy / val_loss / val_accuracy to one value per epoch run."""
+
+    def __init__(self, with_val):
+        self.epoch = []
+        self.history = {"loss": [], "accuracy": []}
+        if with_val:
+            self.history.update({"val_loss": [], "val_accuracy": []})
+        self.stopped_epoch = None           # epoch index at which early stopping ended the run (None: ran all epochs)
+
+
+class FitJob:
+    """The data of one ``fit`` / ``train_on_batch`` call as the device function takes it.  ``xs``: three (N, H, W) float32 arrays, ``y``
+    (N,) int32, ``val_xs`` / ``val_y`` the same or None, ``class_weight`` (C,) float32 (training only: Keras weighs no validation
+    sample), ``batch_size``, dropout ``rate``, ``seed``; ``trusted``: the labels were checked on the host, so the status word is read
+    with the epoch's results and not before every update.  ``dev``: what the device function keeps between epochs."""
+
+    def __init__(self, xs, y, val_xs, val_y, class_weight, batch_size, rate, seed, trusted):
+        self.xs, self.y, self.val_xs, self.val_y = xs, y, val_xs, val_y
+        self.class_weight, self.batch_size, self.rate, self.seed, self.trusted = class_weight, int(batch_size), float(rate), int(seed), trusted
+        self.dev = None          # resident tensors (_fit_upload)
+        self.fit = None          # the _DeviceFit of this job
+
+
+def _k2_layout(params):
+    """0: the second convolution kernels are dense (out, in, ky, kx); 1: channels_last (rml_dnn_train_step's k2_layout)"""
+    got = {tuple(params[4 * b + 2].stride()) for b in range(3)}
+    if got == {(576, 9, 3, 1)}:
+        return 0
+    if got == {(576, 1, 192, 64)}:
+        return 1
+    raise ValueError("fit: the second convolution kernels must all be contiguous or all channels_last, got strides %s" % sorted(got))
+
+
+def _fit_upload(model, job, dev):
+    import torch
+    from . import _lib
+    lib = _lib.load()
+    N, H, W = job.xs[0].shape
+    C = model.n_classes
+    if not lib.rml_dnn_train_supported(int(H), int(W), int(C)):
+        raise _lib.RadarMLError("fit: %d x %d planes with %d classes have no training kernel (H, W multiples of 4, W <= 128, 2..16 classes)" % (H, W, C))
+    if not 1 <= job.batch_size <= _lib.DNN_TRAIN_MAX_BATCH:
+        raise ValueError("fit: batch_size must be in 1..%d" % _lib.DNN_TRAIN_MAX_BATCH)
+    params = list(model.parameters())
+    if len(params) != 18 or any(p.dtype != torch.float32 or not p.is_cuda for p in params) or model.flat_features != (H // 4) * (W // 4) * 96:
+        raise ValueError("fit: the three-branch float32 model of define_classifier on a CUDA device, built for these planes, expected")
+    up = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a)).to(device=dev, dtype=dt)        # noqa: E731
+    st = {"x": [up(a, torch.float32) for a in job.xs], "y": up(job.y, torch.int32), "N": int(N), "H": int(H), "W": int(W),
+          "cw": up(job.class_weight, torch.float32), "acc": torch.zeros((4,), dtype=torch.float64, device=dev)}
+    if job.val_xs is not None:
+        st["vx"] = [up(a, torch.float32) for a in job.val_xs]
+        st["vy"] = up(job.val_y, torch.int32)
+        st["vrows"] = torch.arange(len(job.val_y), dtype=torch.int32, device=dev)
+    # one workspace for every call of the fit: rml_dnn_train_workspace_bytes(B) covers every batch of up to B samples -- the partial
+    # last batch of an epoch included -- and validation runs in batches of up to DNN_TRAIN_MAX_BATCH whatever batch_size is
+    top = max(job.batch_size, min(_lib.DNN_TRAIN_MAX_BATCH, len(job.val_y)) if job.val_xs is not None else 0)
+    nbytes = int(lib.rml_dnn_train_workspace_bytes(int(top), int(H), int(W), int(C)))
+    st["ws"], st["ws_bytes"] = torch.empty((nbytes,), dtype=torch.uint8, device=dev), nbytes
+    job.dev = st
+    return st
+
+
+class _DeviceFit:
+    """The enqueueing half of :func:`_fit_epoch` for one (model, job): ``train`` queues one update (rml_dnn_train_step +
+    rml_adam_step) on a batch of resident rows, ``validate`` the eval-mode pass over the validation set; neither reads device memory.
+    ``acc``: loss sum | val loss sum (float64) | correct, val correct | status, pad (int32)."""
+
+    def __init__(self, model, job):
+        import ctypes as C
+        import torch
+        from . import _lib
+        from .nn_common import DeviceAdam
+        self.C, self.torch, self._lib, self.lib = C, torch, _lib, _lib.load()
+        self.model, self.job = model, job
+        self.params = params = list(model.parameters())
+        self.dev = dev = params[0].device
+        if dev.type != "cuda":
+            raise _lib.RadarMLError("fit runs on the GPU: move the model to a CUDA device (there is no CPU path)")
+        self.st = job.dev if job.dev is not None else _fit_upload(model, job, dev)
+        opt = model._opt
+        if model._adam is None or model._adam.params[0] is not params[0]:
+            model._adam = DeviceAdam(params, opt["lr"], (opt["beta_1"], opt["beta_2"]), opt["epsilon"])
+            model._grads = [torch.empty_like(p) for p in params]
+        self.adam, self.grads = model._adam, model._grads
+        self.pp = (C.c_void_p * 18)(*[p.data_ptr() for p in params])
+        self.gp = (C.c_void_p * 18)(*[g.data_ptr() for g in self.grads])
+        self.layout = _k2_layout(params)
+        self.acc = self.st["acc"]
+        self.ctx = _lib.context(dev)
+
+    def _step(self, x, y, N, rows, off, B, cw, mode, t, slot):
+        C, _lib, st, a0 = self.C, self._lib, self.st, self.acc.data_ptr()
+        _lib.check(self.lib.rml_dnn_train_step(self.ctx, _lib.ptr(x[0]), _lib.ptr(x[1]), _lib.ptr(x[2]), _lib.ptr(y), C.c_void_p(rows.data_ptr() + 4 * off),
+                                               B, N, st["H"], st["W"], _lib.ptr(cw), self.model.n_classes, self.pp, self.gp, self.layout, self.job.seed,
+                                               t, self.job.rate, mode, _lib.ptr(st["ws"]), st["ws_bytes"], C.c_void_p(a0 + 8 * slot),
+                                               C.c_void_p(a0 + 16 + 4 * slot), C.c_void_p(a0 + 24), _lib.stream_ptr(self.dev)), "rml_dnn_train_step")
+
+    def status(self):
+        """the status word, read now (a device synchronisation)"""
+        return int(self.acc.view(self.torch.int32)[6].item())
+
+    def train(self, rows, off, B, check_status=False):
+        """one update on rows[off : off + B] (``rows``: int32 device tensor of indices into the resident training set)"""
+        st, model = self.st, self.model
+        self._step(st["x"], st["y"], st["N"], rows, off, B, st["cw"], self._lib.DNN_TRAIN, model._train_steps, 0)
+        # A set status means the step wrote no gradient: the update must not run on the previous batch's.  Callers that cannot rule
+        # it out on the host (train_on_batch) look before the update; fit has checked every label and makes the row indices itself.
+        if check_status and self.status() != 0:
+            self.bad_status()
+        self.adam.step(self.grads)
+        model._train_steps += 1
+
+    def validate(self):
+        st, top = self.st, self._lib.DNN_TRAIN_MAX_BATCH
+        nv = int(st["vy"].numel())
+        for off in range(0, nv, top):
+            self._step(st["vx"], st["vy"], nv, st["vrows"], off, min(top, nv - off), None, self._lib.DNN_EVAL, 0, 1)
+
+    def bad_status(self):
+        raise self._lib.RadarMLError("rml_dnn_train_step: a row index outside [0, N) or a label outside [0, n_classes) (status -1): no update was made")
+
+
+def _fit_epoch(model, job, perm):
+    """ALL device work of ``fit`` / ``train_on_batch``: one epoch over the training rows in the order ``perm`` (int32) in batches of
+    ``job.batch_size`` -- rml_dnn_train_step + rml_adam_step per batch, on resident data (uploaded at the first call) -- then the
+    validation set in eval mode.  Returns (loss sum, correct, val loss sum, val correct) from ONE read of device memory.  The module's
+    parameters are trained in place.  Tests replace this function by a float64 CPU restatement (tests/dnn_train_common.py)."""
+    import torch
+    f = job.fit if job.fit is not None and job.fit.params[0] is next(model.parameters()) else _DeviceFit(model, job)
+    job.fit = f
+    assert job.trusted or len(perm) <= job.batch_size       # an unchecked job is one batch, whose status is read before its update
+    with torch.no_grad(), torch.cuda.device(f.dev):
+        f.acc.zero_()
+        rows = torch.from_numpy(np.ascontiguousarray(perm, dtype=np.int32)).to(f.dev)
+        for off in range(0, len(perm), job.batch_size):
+            f.train(rows, off, min(job.batch_size, len(perm) - off), check_status=not job.trusted)
+        if "vx" in f.st:
+            f.validate()
+        host = f.acc.cpu()
+    # the library wrote the parameters through raw pointers: tell torch (the weight packs of _cached key on the version counters)
+    for p in f.params:
+        torch.autograd.graph.increment_version(p)
+    ints = host.view(torch.int32)
+    if int(ints[6]) != 0:
+        f.bad_status()
+    return float(host[0]), int(ints[4]), float(host[1]), int(ints[5])
+
+
+def _planes(a):
+    """(N, H, W) float32 numpy from what Keras feeds: (N, H, W) or (N, H, W, 1) arrays (or tensors)"""
+    a = a.detach().cpu().numpy() if hasattr(a, "detach") else np.asarray(a)
+    if a.ndim == 4 and a.shape[-1] == 1:
+        a = a[..., 0]
+    if a.ndim != 3:
+        raise ValueError("expected (N,H,W) or (N,H,W,1), got %s" % (a.shape,))
+    return np.ascontiguousarray(a, dtype=np.float32)
+
+
+def _class_weights(class_weight, n_classes):
+    """Keras' ``class_weight`` dict {class index: weight} (classes it leaves out weigh 1), or an array of n_classes weights"""
+    w = np.ones((n_classes,), np.float32)
+    if class_weight is None:
+        return w
+    if isinstance(class_weight, dict):
+        for k, v in class_weight.items():
+            if not 0 <= int(k) < n_classes:
+                raise ValueError("class_weight: class %r of %d" % (k, n_classes))
+            w[int(k)] = v
+        return w
+    w = np.asarray(class_weight, dtype=np.float32).reshape(-1)
+    if len(w) != n_classes:
+        raise ValueError("class_weight: %d weights for %d classes" % (len(w), n_classes))
+    return w
+
+
+def train(model, X, y, X_val, y_val, w_classes, results_dir, epochs=100, patience=10, logger=None):
+    """dnn.py:347-390: fit with batches of 64, up to 100 epochs, class weights, EarlyStopping(patience=10) and
+    ModelCheckpoint(save_best_only) on val_loss -- the best weights go to ``results_dir/c_model.pt`` (a ``state_dict``) -- and
+    the reference's log lines.  ``X``, ``X_val``: (N, H, W, 3) arrays, the projections xz, yz, xy on the last axis.  Returns the
+    history."""
+    import logging
+    import os
+    log = logger or logging.getLogger(__name__)
+    fp = os.path.join(results_dir, "c_model.pt")
+    log.info("Training model.")
+    hist = model.fit(x=[X[..., 0], X[..., 1], X[..., 2]], y=y, batch_size=64, epochs=epochs,
+                     validation_data=([X_val[..., 0], X_val[..., 1], X_val[..., 2]], y_val), class_weight=w_classes, patience=patience,
+                     checkpoint=fp)
+    if hist.stopped_epoch is not None:
+        log.info("Epoch %d: early stopping" % (hist.stopped_epoch + 1))
+    best_val_loss = min(hist.history["val_loss"])
+    i = hist.history["val_loss"].index(best_val_loss)
+    log.info("Best loss: %.4f, Best acc: %.2f%%" % (hist.history["loss"][i], hist.history["accuracy"][i] * 100))
+    log.info("Best val loss: %.4f, Best val acc: %.2f%%" % (best_val_loss, hist.history["val_accuracy"][i] * 100))
+    log.info("Saved best model to %s" % results_dir)
+    return hist
 
 
 def define_classifier(xz_shape=(80, 80, 1), yz_shape=(80, 80, 1), xy_shape=(80, 80, 1), n_classes=3,
@@ -63,6 +263,7 @@ class Classifier(_module_base()):
         self.drop = nn.Dropout(0.5)
         self._packs = {}                            # name -> (key of the parameters it was made from, value): _cached
         self._margin = dnn_guard.MarginGuard()
+        self._opt, self._adam, self._grads, self._train_steps, self._rng = None, None, None, 0, None     # training: compile()
         # Keras defaults: glorot_uniform kernels, zero biases
         for mod in self.modules():
             if isinstance(mod, (nn.Conv2d, nn.Linear)):
@@ -660,6 +861,85 @@ class Classifier(_module_base()):
         res = torch.empty_like(got)
         res[order.to(dev)] = got
         return res
+
+    # ---- training (dnn.py:89-90, 347-390) ------------------------------------------------------------------------
+    def compile(self, lr=0.0002, beta_1=0.5, beta_2=0.999, epsilon=1e-7, seed=0):
+        """Keras ``model.compile(optimizer=Adam(lr=0.0002, beta_1=0.5), loss='sparse_categorical_crossentropy')`` (dnn.py:89-90): a fresh
+        optimizer state (nn_common.DeviceAdam: torch.optim.Adam's form, epsilon inside the bias-corrected denominator where Keras adds it
+        outside).  ``seed`` seeds the dropout masks and the epoch permutations.  ``fit`` / ``train_on_batch`` imply it with these
+        defaults."""
+        self._opt = {"lr": float(lr), "beta_1": float(beta_1), "beta_2": float(beta_2), "epsilon": float(epsilon), "seed": int(seed)}
+        self._adam, self._grads, self._train_steps = None, None, 0
+        self._rng = np.random.default_rng(int(seed))
+        return self
+
+    def _job(self, x, y, validation_data, class_weight, batch_size, trusted):
+        if self._opt is None:
+            self.compile()
+        if len(x) != 3:
+            raise ValueError("expected the three inputs [xz, yz, xy]")
+        xs = [_planes(a) for a in x]
+        y = np.asarray(y).reshape(-1)
+        if any(a.shape != xs[0].shape for a in xs) or len(y) != len(xs[0]) or len(y) == 0:
+            raise ValueError("fit: three equal plane sets and one label per sample expected")
+        if trusted and (y.min() < 0 or y.max() >= self.n_classes):
+            raise ValueError("fit: labels outside [0, %d)" % self.n_classes)
+        val_xs = val_y = None
+        if validation_data is not None:
+            val_xs = [_planes(a) for a in validation_data[0]]
+            val_y = np.asarray(validation_data[1]).reshape(-1)
+            if len(val_xs) != 3 or any(a.shape[1:] != xs[0].shape[1:] or len(a) != len(val_y) for a in val_xs) or len(val_y) == 0:
+                raise ValueError("fit: validation_data = ([xz, yz, xy], y) with the training planes' shape expected")
+            if val_y.min() < 0 or val_y.max() >= self.n_classes:
+                raise ValueError("fit: validation labels outside [0, %d)" % self.n_classes)
+            val_y = val_y.astype(np.int32)
+        return FitJob(xs, y.astype(np.int32), val_xs, val_y, _class_weights(class_weight, self.n_classes), batch_size, self.drop.p,
+                      self._opt["seed"], trusted)
+
+    def train_on_batch(self, x, y, class_weight=None):
+        """Keras ``model.train_on_batch([xz, yz, xy], y, class_weight=...)``: one update on these samples (at most 64); returns
+        (loss, accuracy) of the batch in train mode, before the update."""
+        job = self._job(x, y, None, class_weight, len(np.asarray(y).reshape(-1)), trusted=False)
+        n = len(job.y)
+        ls, co, _, _ = _fit_epoch(self, job, np.arange(n, dtype=np.int32))
+        return ls / n, co / n
+
+    def fit(self, x, y, batch_size=64, epochs=100, validation_data=None, class_weight=None, shuffle=True, patience=None, checkpoint=None):
+        """Keras ``model.fit`` as dnn.py:373-381 calls it.  ``x`` = [xz, yz, xy] planes, (N,H,W) or (N,H,W,1), already scaled to [-1, 1];
+        ``validation_data`` = ([xz, yz, xy], y).  The data set is uploaded once; every epoch draws a permutation from the NumPy generator
+        that ``compile(seed=...)`` seeded and reads device memory once.  ``patience``: EarlyStopping(monitor='val_loss', patience) -- training
+        stops when val_loss has not been below its best for ``patience`` epochs, the model keeps its LAST weights; ``checkpoint``: a path
+        that receives ``state_dict()`` whenever val_loss improves (ModelCheckpoint(save_best_only=True)).  Returns a :class:`History`:
+        loss / accuracy are the train-mode running means of the epoch (sum of weighted losses / N, correct / N), val_loss / val_accuracy
+        the eval-mode means (unweighted, as Keras)."""
+        import torch
+        if (patience is not None or checkpoint is not None) and validation_data is None:
+            raise ValueError("fit: patience and checkpoint monitor val_loss: validation_data is needed")
+        job = self._job(x, y, validation_data, class_weight, batch_size, trusted=True)
+        n = len(job.y)
+        hist = History(validation_data is not None)
+        best = wait = None
+        for ep in range(int(epochs)):
+            perm = self._rng.permutation(n) if shuffle else np.arange(n)
+            ls, co, vls, vco = _fit_epoch(self, job, perm.astype(np.int32))
+            hist.epoch.append(ep)
+            hist.history["loss"].append(ls / n)
+            hist.history["accuracy"].append(co / n)
+            if validation_data is None:
+                continue
+            val_loss = vls / len(job.val_y)
+            hist.history["val_loss"].append(val_loss)
+            hist.history["val_accuracy"].append(vco / len(job.val_y))
+            if best is None or val_loss < best:
+                best, wait = val_loss, 0
+                if checkpoint is not None:
+                    torch.save(self.state_dict(), checkpoint)
+            else:
+                wait += 1
+                if patience is not None and wait >= patience:
+                    hist.stopped_epoch = ep
+                    break
+        return hist
 
     # ---- Keras surface -----------------------------------------------------------------------------------------
     def predict(self, inputs, batch_size=8192, autocast_dtype="bfloat16", label_guard=LABEL_GUARD, fused=None):
