@@ -120,7 +120,10 @@ int rml_ctx_device(const rml_ctx* ctx);
  *     of a dual of at most this many rows in LDS; larger duals run the same code on the workspace.  0: every dual on the workspace.
  *   RML_OPT_SGD_RESIDENT_D (default RML_SGD_RESIDENT_D_MAX = 10 240, ten elements per thread of a 1 024-thread workgroup):
  *     rml_sgd_solve keeps the weights of a problem of at most this many features in registers; wider rows run the same code with
- *     the weights on the workspace.  0: every problem on the workspace.  The results are the same bits either way. */
+ *     the weights on the workspace.  0: every problem on the workspace.  The results are the same bits either way.
+ *   RML_OPT_CONV7 (default RML_CONV7_DEFAULT; bit 0: forward, bit 1: backward): which passes of the generator's output layer the callers
+ *     of rml_conv7_tanh_* (nn_common.conv7_tanh) run on the hand-written kernels; a cleared bit sends that pass to the convolution library.
+ *     The entry points themselves always run the kernels: the option is the caller's switch, kept here so that A/B runs share one knob. */
 #define RML_OPT_PROJECT_SHARE_CU 1
 #define RML_OPT_WAVEFRAME 2
 #define RML_OPT_LINPLANE 3
@@ -135,6 +138,8 @@ int rml_ctx_device(const rml_ctx* ctx);
 #define RML_SMO_LDS_ROWS_MAX 2768
 #define RML_OPT_SGD_RESIDENT_D 12
 #define RML_SGD_RESIDENT_D_MAX 10240
+#define RML_OPT_CONV7 13
+#define RML_CONV7_DEFAULT 3
 int rml_ctx_set_option(rml_ctx* ctx, int option, int value);
 int rml_ctx_get_option(const rml_ctx* ctx, int option, int* value);
 
@@ -516,7 +521,9 @@ int rml_linear_decision(rml_ctx* ctx, const rml_linear* m, const float* feat, in
  * to Pillow.  When div != 0 the reference's [-1,1] scaling (dnn.py:202-205) is applied first: v = (p - sub) / div
  * (sub = div = RADAR_MAX/2 = 127.5).  in: B planes of H x W float32, in_stride floats from one sample to the next
  * (a plane inside a feature row [xz|yz|xy] is addressed directly); out: B x out_h x out_w contiguous, float32
- * (out_bf16 = 0) or bf16 (out_bf16 = 1, the operand type of rml_dnn_trunk). */
+ * (out_bf16 = 0) or bf16 (out_bf16 = 1, the operand type of rml_dnn_trunk).  Sizes whose plane and intermediate image do not fit
+ * the LDS together (128 x 128 -> 22 x 176, the data product of sgan.py:474-479) run Pillow's two passes as two launches through the
+ * float32 intermediate image in the context's workspace: the same bits. */
 int rml_resize_bicubic(rml_ctx* ctx, const float* in, int64_t in_stride, int64_t B, int H, int W, int out_h, int out_w,
                        float sub, float div, void* out, int out_bf16, void* stream);
 /* ---- the same preprocessing for the bf16 conv trunk, all three projections of a feature row in ONE launch ------------
@@ -692,6 +699,19 @@ int rml_conv1_bn_lrelu_pad_backward(rml_ctx* ctx, const void* image, const float
                                     int H, int W, int C, int pad_h, int pad_w, const float* gamma, const float* beta,
                                     const float* save_mean, const float* save_rstd, const float* img_stats /* from forward */,
                                     float slope, float* workspace, float* dweight, float* dgamma, float* dbeta, void* stream);
+
+/* ---- SGAN generator output layer: Conv2D(1, 7x7, 'same') + tanh (sgan.py:112-114; csrc/gen.hip) ------------------------------------
+ * x: N x H x W x C (NHWC, dense, 16-byte aligned) float16 (dtype 0) or bfloat16 (dtype 1); weight: float32 [49][C], tap = ky * 7 + kx (the
+ * Keras kernel (7, 7, C, 1) flattened), rounded to x's type on load; bias: 1 float; y, dy: N x H x W float32.  All sums in float32, in an
+ * order fixed by (H, W) alone -- no atomics: the same call gives the same bits, and y / dx of a sample do not depend on the batch around
+ * it.  backward: dz = dy (1 - y^2); dx (x's layout and type), dweight [49][C], dbias [1]; workspace of
+ * rml_conv7_workspace_floats(ctx, N, H, W, C) floats.  rml_conv7_tanh_supported: 1 for C = 128 and 1 <= H, W <= 256. */
+int rml_conv7_tanh_supported(int H, int W, int C);
+int64_t rml_conv7_workspace_floats(rml_ctx* ctx, int64_t N, int H, int W, int C);
+int rml_conv7_tanh_forward(rml_ctx* ctx, const void* x, int dtype, int64_t N, int H, int W, int C, const float* weight,
+                           const float* bias, float* y, void* stream);
+int rml_conv7_tanh_backward(rml_ctx* ctx, const void* x, const float* y, const float* dy, int dtype, int64_t N, int H, int W, int C,
+                            const float* weight, float* workspace, void* dx, float* dweight, float* dbias, void* stream);
 
 /* ---- Adam update of the SGAN discriminator (sgan.py:206, 214: Adam(lr=0.0002, beta_1=0.5) inside train_on_batch, sgan.py:525-532) ----
  * ONE pass over all parameters with the loss-scale bookkeeping of a half-precision step on the device (csrc/optim.hip).

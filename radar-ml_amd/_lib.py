@@ -132,6 +132,11 @@ SIGNATURES = {
     "rml_conv1_bn_lrelu_pad_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_int, c_int, c_int,
                                                 c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p,
                                                 c_void_p, c_void_p]),
+    "rml_conv7_tanh_supported": (c_int, [c_int, c_int, c_int]),
+    "rml_conv7_workspace_floats": (c_int64, [c_void_p, c_int64, c_int, c_int, c_int]),
+    "rml_conv7_tanh_forward": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "rml_conv7_tanh_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_int, c_void_p, c_void_p,
+                                        c_void_p, c_void_p, c_void_p, c_void_p]),
     "rml_adam_entry_bytes": (c_int, []),
     "rml_adam_step": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_float, c_float, c_float, c_float, c_void_p, c_void_p, c_void_p,
                               c_void_p, c_int, c_float, c_float, c_int, c_void_p]),
@@ -144,13 +149,15 @@ SIGNATURES = {
 
 MODE_MAX, MODE_SLICE, MODE_SUM, MODE_MAX_NAN = 0, 1, 2, 3
 # rml_ctx_set_option ids (include/radarml.h RML_OPT_*)
-OPT_PROJECT_SHARE_CU, OPT_WAVEFRAME, OPT_LINPLANE, OPT_STAGE_CODES, OPT_SLICE_WAVE, OPT_DERIVE_FUSED, OPT_CODE_RMW, OPT_GEMM_BIG, OPT_CHUNK, OPT_C1_PK, OPT_SMO_LDS_ROWS, OPT_SGD_RESIDENT_D = range(1, 13)
+OPT_PROJECT_SHARE_CU, OPT_WAVEFRAME, OPT_LINPLANE, OPT_STAGE_CODES, OPT_SLICE_WAVE, OPT_DERIVE_FUSED, OPT_CODE_RMW, OPT_GEMM_BIG, OPT_CHUNK, OPT_C1_PK, OPT_SMO_LDS_ROWS, OPT_SGD_RESIDENT_D, OPT_CONV7 = range(1, 14)
 OPTIONS = {"project_share_cu": OPT_PROJECT_SHARE_CU, "waveframe": OPT_WAVEFRAME, "linplane": OPT_LINPLANE, "stage_codes": OPT_STAGE_CODES,
            "slice_wave": OPT_SLICE_WAVE, "derive_fused": OPT_DERIVE_FUSED, "code_rmw": OPT_CODE_RMW, "gemm_big": OPT_GEMM_BIG,
            "chunk": OPT_CHUNK, "c1_pk": OPT_C1_PK}
 # options of the training-side solvers (rml_smo_solve, rml_sgd_solve); set_option, get_option and the `options` context manager below take these
 # names too (kept apart from OPTIONS, whose keys are the inference paths' knobs)
 SOLVER_OPTIONS = {"smo_lds_rows": OPT_SMO_LDS_ROWS, "sgd_resident_d": OPT_SGD_RESIDENT_D}
+# which passes of the generator's output layer run on csrc/gen.hip (bit 0 forward, bit 1 backward; nn_common.conv7_tanh reads it)
+NN_OPTIONS = {"conv7": OPT_CONV7}
 SMO_LDS_ROWS_MAX = 2768
 SGD_RESIDENT_D_MAX = 10240
 SGD_MAX_ROWS = 8192
@@ -161,7 +168,8 @@ DNN_TRAIN_MAX_BATCH = 64
 # Python, when a context is created, and applied as options -- the library itself never reads the environment
 ENV_OPTIONS = {"RML_WAVE_SHARE": "project_share_cu", "RML_WAVEFRAME": "waveframe", "RML_LINPLANE": "linplane", "RML_STAGE_CODES": "stage_codes",
                "RML_SLICE_WAVE": "slice_wave", "RML_DERIVE_FUSED": "derive_fused", "RML_CODE_RMW": "code_rmw", "RML_GEMM_BIG": "gemm_big",
-               "RML_CHUNK": "chunk", "RML_C1_PK": "c1_pk", "RML_SMO_LDS_ROWS": "smo_lds_rows", "RML_SGD_RESIDENT_D": "sgd_resident_d"}
+               "RML_CHUNK": "chunk", "RML_C1_PK": "c1_pk", "RML_SMO_LDS_ROWS": "smo_lds_rows", "RML_SGD_RESIDENT_D": "sgd_resident_d",
+               "RML_CONV7": "conv7"}
 AUG_ROTATE, AUG_ZOOM, AUG_NOISE = 0, 1, 2
 VOL_F32, VOL_U8 = 0, 1
 MODES = {"max": MODE_MAX, "slice": MODE_SLICE, "sum": MODE_SUM, "max_nan": MODE_MAX_NAN}
@@ -172,9 +180,12 @@ PATHS = {"auto": PATH_AUTO, "f32": PATH_F32, "i8": PATH_I8, "f64": PATH_F64, "di
 
 
 def option_id(name):
-    """RML_OPT_* id of an option name (a key of OPTIONS or SOLVER_OPTIONS; the header's upper-case spelling is taken too)."""
+    """RML_OPT_* id of an option name (a key of OPTIONS, SOLVER_OPTIONS or NN_OPTIONS; the header's upper-case spelling is taken too)."""
     name = name.lower()
-    return OPTIONS[name] if name in OPTIONS else SOLVER_OPTIONS[name]
+    for table in (OPTIONS, SOLVER_OPTIONS):
+        if name in table:
+            return table[name]
+    return NN_OPTIONS[name]
 
 
 def load():

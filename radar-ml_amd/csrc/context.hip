@@ -314,6 +314,11 @@ extern "C" int rml_ctx_set_option(rml_ctx* ctx, int option, int value) {
         ctx->opt.sgd_resident_d = value;
         return RML_OK;
     }
+    if (option == RML_OPT_CONV7) {
+        RML_REQUIRE(value >= 0 && value <= 3, RML_ERR_INVALID, "rml_ctx_set_option: RML_OPT_CONV7 is 0..3 (bit 0 forward, bit 1 backward)");
+        ctx->opt.conv7 = value;
+        return RML_OK;
+    }
     if (option == RML_OPT_CHUNK) {
         RML_REQUIRE(value == 0 || value >= 128, RML_ERR_INVALID, "rml_ctx_set_option: RML_OPT_CHUNK is 0 (automatic) or >= 128 rows");
         ctx->opt.chunk = value;
@@ -336,6 +341,7 @@ extern "C" int rml_ctx_get_option(const rml_ctx* ctx, int option, int* value) {
     if (option == RML_OPT_CHUNK) { *value = (int)c->opt.chunk; return RML_OK; }
     if (option == RML_OPT_SMO_LDS_ROWS) { *value = c->opt.smo_lds_rows; return RML_OK; }
     if (option == RML_OPT_SGD_RESIDENT_D) { *value = c->opt.sgd_resident_d; return RML_OK; }
+    if (option == RML_OPT_CONV7) { *value = c->opt.conv7; return RML_OK; }
     const int* slot = opt_slot(c->opt, option);
     RML_REQUIRE(slot != nullptr, RML_ERR_INVALID, "rml_ctx_get_option: unknown option %d", option);
     *value = *slot;

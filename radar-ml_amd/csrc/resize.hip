@@ -308,8 +308,17 @@ extern "C" int rml_resize_bicubic(rml_ctx* ctx, const float* in, int64_t in_stri
         lds += (size_t)out_h * a.ksv * 8 + (size_t)out_h * 8;
     }
     if (out_w != W && out_h != H) lds += (size_t)H * out_w * 4;
-    RML_REQUIRE(lds <= 150 * 1024, RML_ERR_UNSUPPORTED, "rml_resize_bicubic: %dx%d -> %dx%d does not fit the LDS-resident resize", H, W, out_h, out_w);
     hipStream_t st = static_cast<hipStream_t>(stream);
+    if (lds > 150 * 1024 && out_w != W && out_h != H) {
+        // plane + intermediate do not fit together (128 x 128 -> 22 x 176: 64 KB + 90 KB + tables): Pillow's own two passes as two
+        // launches, the horizontal one into Pillow's float32 intermediate image [B][H][out_w] in the workspace, the vertical one from it
+        rml_ctx_guard guard(ctx, st);
+        void* mid = nullptr;
+        if (int rc = rml_ws_reserve(ctx, (size_t)B * H * out_w * 4, &mid, st)) return rc;
+        if (int rc = rml_resize_bicubic(ctx, in, in_stride, B, H, W, H, out_w, sub, div, mid, 0, stream)) return rc;
+        return rml_resize_bicubic(ctx, static_cast<const float*>(mid), (int64_t)H * out_w, B, H, out_w, out_h, out_w, 0.0f, 0.0f, out, out_bf16, stream);
+    }
+    RML_REQUIRE(lds <= 150 * 1024, RML_ERR_UNSUPPORTED, "rml_resize_bicubic: %dx%d -> %dx%d does not fit the LDS-resident resize", H, W, out_h, out_w);
     const bool fixed = out_w != W && out_h != H && out_w <= 256;
     if (fixed && a.ksh <= 6) launch_resize<6>(a, lds, ctx->num_cu, st);
     else if (fixed && a.ksh <= 12) launch_resize<12>(a, lds, ctx->num_cu, st);

@@ -38,6 +38,7 @@ struct rml_opts {
     int c1_pk = 1;              // RML_OPT_C1_PK: packed first-layer kernels of the SGAN branches
     int64_t chunk = 0;          // RML_OPT_CHUNK: rows per chunk of the chunked front doors, 0 = chosen per batch
     int smo_lds_rows = RML_SMO_LDS_ROWS_MAX;   // RML_OPT_SMO_LDS_ROWS: duals of more rows run on the workspace variant of k_smo
+    int conv7 = RML_CONV7_DEFAULT;  // RML_OPT_CONV7: bit 0 forward, bit 1 backward of the generator's output layer on csrc/gen.hip
     int sgd_resident_d = RML_SGD_RESIDENT_D_MAX;   // RML_OPT_SGD_RESIDENT_D: wider problems run on the workspace variant of k_sgd
 };
 

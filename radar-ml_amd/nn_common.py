@@ -35,11 +35,14 @@ def make_same_conv(in_ch, out_ch, kernel, stride):
 
 
 def to_nchw(a, device, dtype=None):
-    """Keras feeds (N,H,W,1) or (N,H,W) numpy arrays; return an (N,1,H,W) channels_last tensor on device."""
+    """Keras feeds (N,H,W,1) or (N,H,W) numpy arrays; return an (N,1,H,W) channels_last tensor on device.  An (N,1,H,W) tensor -- what
+    ``Generator.predict(return_numpy=False)`` hands over -- is taken as it is."""
     torch = _torch()
     t = a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a))
     if t.ndim == 4 and t.shape[-1] == 1:
         t = t[..., 0]
+    elif t.ndim == 4 and t.shape[1] == 1:
+        t = t[:, 0]
     if t.ndim != 3:
         raise ValueError("expected (N,H,W) or (N,H,W,1), got %s" % (tuple(t.shape),))
     t = t.to(device=device, dtype=dtype or torch.float32).unsqueeze(1)
@@ -421,6 +424,93 @@ def conv1_bn_lrelu_pad(x_padded, conv, bn, slope, pad, dtype):
                                              bn.eps, bn.momentum, slope, pad, dtype)
     _bn_side_effects(bn, conv.bias)
     return y
+
+
+def _conv7_tanh_function():
+    """torch.autograd.Function around csrc/gen.hip: the generator's Conv2D(1, 7x7, 'same', tanh) output layer."""
+    torch = _torch()
+    if getattr(_conv7_tanh_function, "_cls", None) is not None:
+        return _conv7_tanh_function._cls
+    import torch.nn.functional as F
+    from . import _lib
+
+    class Conv7Tanh(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, x, weight, bias, mode):
+            # x (N, C, H, W) half, channels_last; weight (1, C, 7, 7) and bias (1,) float32 masters; mode: bit 0 forward, bit 1
+            # backward on the hand-written kernels (RML_OPT_CONV7), a cleared bit = the convolution library on the same operands
+            lib = _lib.load()
+            n, c, h, w = x.shape
+            dev = x.device
+            w49 = weight[0].permute(1, 2, 0).reshape(49, c).float().contiguous()          # [tap = ky * 7 + kx][c]
+            b1 = bias.float().contiguous()
+            if mode & 1:
+                y = torch.empty((n, 1, h, w), dtype=torch.float32, device=dev)
+                with torch.cuda.device(dev):
+                    _lib.check(lib.rml_conv7_tanh_forward(_lib.context(dev), _lib.ptr(x), 1 if x.dtype == torch.bfloat16 else 0, n, h, w, c,
+                                                          _lib.ptr(w49), _lib.ptr(b1), _lib.ptr(y), _lib.stream_ptr(dev)),
+                               "rml_conv7_tanh_forward")
+            else:
+                y = torch.tanh(F.conv2d(x, weight.to(x.dtype), b1.to(x.dtype), padding=3)).float().contiguous()
+            ctx.save_for_backward(x, y, w49)
+            ctx.meta = (int(mode), weight.shape, weight.dtype, bias.dtype)
+            return y
+
+        @staticmethod
+        def backward(ctx, dy):
+            lib = _lib.load()
+            x, y, w49 = ctx.saved_tensors
+            mode, wshape, wdtype, bdtype = ctx.meta
+            n, c, h, w = x.shape
+            dev = x.device
+            dy = dy.float().contiguous()
+            if mode & 2:
+                dx = torch.empty_like(x, memory_format=torch.channels_last)
+                dw = torch.empty((49, c), dtype=torch.float32, device=dev)
+                db = torch.empty((1,), dtype=torch.float32, device=dev)
+                with torch.cuda.device(dev):
+                    hctx = _lib.context(dev)
+                    ws = torch.empty((int(lib.rml_conv7_workspace_floats(hctx, n, h, w, c)),), dtype=torch.float32, device=dev)
+                    _lib.check(lib.rml_conv7_tanh_backward(hctx, _lib.ptr(x), _lib.ptr(y), _lib.ptr(dy), 1 if x.dtype == torch.bfloat16 else 0,
+                                                           n, h, w, c, _lib.ptr(w49), _lib.ptr(ws), _lib.ptr(dx), _lib.ptr(dw), _lib.ptr(db),
+                                                           _lib.stream_ptr(dev)), "rml_conv7_tanh_backward")
+                dweight = dw.reshape(7, 7, c).permute(2, 0, 1).reshape(wshape)
+            else:
+                dz = (dy * (1.0 - y * y))
+                dzh = dz.to(x.dtype).contiguous(memory_format=torch.channels_last)
+                wh = w49.reshape(7, 7, c).permute(2, 0, 1).reshape(wshape).to(x.dtype).contiguous(memory_format=torch.channels_last)
+                dx = torch.nn.grad.conv2d_input(x.shape, wh, dzh, padding=3)
+                dweight = torch.nn.grad.conv2d_weight(x, wh.shape, dzh, padding=3).float()
+                db = dz.sum().reshape(1)
+            return dx, dweight.to(wdtype), db.to(bdtype), None
+
+    _conv7_tanh_function._cls = Conv7Tanh
+    return Conv7Tanh
+
+
+def conv7_tanh_fused(x, conv):
+    """True when :func:`conv7_tanh` takes ``x`` for the nn.Conv2d(C, 1, 7, padding=3) ``conv``: a CUDA half tensor with the channel
+    count and plane sizes csrc/gen.hip is built for (``rml_conv7_tanh_supported``)."""
+    torch = _torch()
+    from . import _lib
+    return bool(x.is_cuda and x.ndim == 4 and x.dtype in (torch.float16, torch.bfloat16) and conv.out_channels == 1
+                and conv.kernel_size == (7, 7) and conv.bias is not None
+                and _lib.load().rml_conv7_tanh_supported(int(x.shape[2]), int(x.shape[3]), int(x.shape[1])))
+
+
+def conv7_tanh(x, conv, mode=None):
+    """``tanh(conv(x))`` for the generator's output layer Conv2D(1, 7x7, 'same') (sgan.py:112-114) on a CUDA half tensor: float32
+    (N, 1, H, W).  ``mode`` (default: the context option ``conv7``): bit 0 runs the forward pass, bit 1 the backward pass on the
+    hand-written kernels (csrc/gen.hip); a cleared bit runs that pass through the convolution library on the same half operands."""
+    torch = _torch()
+    from . import _lib
+    if not conv7_tanh_fused(x, conv):
+        raise ValueError("conv7_tanh: a CUDA half (N, 128, H, W) tensor with H, W <= 256 and a 7x7 one-channel convolution expected")
+    if mode is None:
+        mode = _lib.get_option("conv7", x.device)
+    if not x.is_contiguous(memory_format=torch.channels_last):
+        x = x.contiguous(memory_format=torch.channels_last)
+    return _conv7_tanh_function().apply(x, conv.weight, conv.bias, int(mode))
 
 
 class DeviceAdam:

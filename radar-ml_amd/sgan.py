@@ -10,15 +10,48 @@ RandomNormal(0, 0.02) kernels, zero biases, BatchNorm(momentum 0.99, eps 1e-3) =
 Adam eps 1e-7.  BASELINE config 5: fp16 autocast + loss scaling, data parallel over the GPUs of a node with
 DistributedDataParallel (backend "nccl" = RCCL all-reduce of ~1.86 M gradient elements per step);
 BatchNorm statistics stay per replica (what Keras does per replica).
-Only the discriminator/classifier train step is in scope; the generator is not.
+
+The generator side of the loop (sgan.py:57-122, 220-235, 439-543) is here too: :class:`Generator` (three branches of Dense ->
+4 x [Conv2DTranspose 4x4 stride 2 + BatchNorm + ReLU] -> Conv2D(1, 7x7, tanh) on one latent input), :class:`GanTrainer`
+(``gan_model.train_on_batch``: the generator and -- the reference's quirk -- the discriminator's BatchNorm gammas and betas are
+trained, every other discriminator weight is frozen for that step only), ``generate_fake_samples``, the
+``generated_data_*.pickle`` product (``generated_samples`` / ``save_generated``) and the four-update loop :func:`train`.  On
+the GPU under half-precision autocast the transposed convolutions run through the library, BatchNorm + ReLU is the fused op of the
+discriminator (slope 0) and the 7x7 one-channel output layer is csrc/gen.hip (nn_common.conv7_tanh).
 """
+import logging
 import os
+import pickle
 
 import numpy as np
 
 from .nn_common import make_same_conv, to_nchw, flatten_nhwc
 
 RESCALE = (128, 128)        # sgan.py:39
+# original (cols, rows) of the radar projections (sgan.py:43-45)
+XZ_SIZE = (176, 22)
+YZ_SIZE = (176, 31)
+XY_SIZE = (31, 22)
+
+logger = logging.getLogger(__name__)
+
+# the fused HIP layers of both models (on by default wherever they apply); `plain_layers()` runs the plain PyTorch layers instead
+# -- the library's kernels under the same autocast -- for A/B timings and for the tests that measure one path against the other
+_FUSED_LAYERS = True
+
+
+class plain_layers:
+    """``with sgan.plain_layers(): ...``: the discriminator and the generator run their plain PyTorch layers inside the block."""
+
+    def __enter__(self):
+        global _FUSED_LAYERS
+        self.prev, _FUSED_LAYERS = _FUSED_LAYERS, False
+        return self
+
+    def __exit__(self, *exc):
+        global _FUSED_LAYERS
+        _FUSED_LAYERS = self.prev
+        return False
 
 
 def _nn():
@@ -71,7 +104,7 @@ class Discriminator(_nn().Module):
         nlayer = len(layers) // 3
         even = all(s % (2 ** nlayer) == 0 for s in x.shape[-2:])
         adt = torch.get_autocast_dtype("cuda") if (x.is_cuda and torch.is_autocast_enabled("cuda")) else None
-        if not (x.is_cuda and br.training and even and adt in (torch.float16, torch.bfloat16)):
+        if not (_FUSED_LAYERS and x.is_cuda and br.training and even and adt in (torch.float16, torch.bfloat16)):
             return br(x)
         ph, pw = tf_same_pad(x.shape[-2], 3, 2), tf_same_pad(x.shape[-1], 3, 2)
         # the 1-channel input of the first convolution; tagged channels_last explicitly (for C = 1 the strides alone do
@@ -95,7 +128,7 @@ class Discriminator(_nn().Module):
         import torch.nn.functional as F
         from .nn_common import cast_all, fused_step_scope
         adt = torch.get_autocast_dtype("cuda") if (xz.is_cuda and torch.is_autocast_enabled("cuda")) else None
-        if not (self.training and adt in (torch.float16, torch.bfloat16)):
+        if not (_FUSED_LAYERS and self.training and adt in (torch.float16, torch.bfloat16)):
             outs = [self._branch(x, br) for x, br in zip((xz, yz, xy), self.branches)]
             fv = flatten_nhwc(torch.cat(outs, dim=1))
             h = self.drop(self.act(self.bn1(self.fc1(fv))))
@@ -491,3 +524,354 @@ def define_discriminator(xz_shape=(128, 128, 1), yz_shape=(128, 128, 1), xy_shap
     dev = torch.device(device) if device is not None else (
         torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu"))
     return Discriminator([xz_shape, yz_shape, xy_shape], n_classes).to(dev).to(memory_format=torch.channels_last)
+
+
+# ---- generator (sgan.py:57-122) ------------------------------------------------------------------------------------------
+
+class Generator(_nn().Module):
+    """g_model of sgan.py:57-122: three independent branches on one latent input (n, latent_dim); a branch is
+    Dense(base*base*channels) -> ReLU -> Reshape (base, base, channels) [NHWC: unit j = (h*base + w)*channels + c] ->
+    n_up x [Conv2DTranspose(channels, 4x4, stride 2, 'same') + BatchNormalization + ReLU] -> Conv2D(1, 7x7, 'same', tanh).
+    ``forward`` returns three (n, 1, S, S) float32 tensors, S = base * 2**n_up (128 at the default size).
+
+    Keras semantics.  The Dense stays in Keras order and its (n, base, base, channels) result is taken as the channels_last
+    storage of an (n, channels, base, base) tensor (a view).  Conv2DTranspose 'same' with stride 2 and kernel 4 is the input
+    gradient of a stride-2 4x4 'same' convolution, which TensorFlow pads 1 before and 1 after:
+    out[oy, ox, co] = b[co] + sum in[iy, ix, ci] K[ky, kx, co, ci] over oy = 2 iy + ky - 1, ox = 2 ix + kx - 1, i.e.
+    torch's ConvTranspose2d(k 4, s 2, padding 1) with weight[ci, co, ky, kx] = K[ky, kx, co, ci] and no flip.  The output
+    convolution pads 3 on every side.  RandomNormal(0, 0.02) kernels, zero biases, BatchNorm momentum 0.99 (torch 0.01), eps 1e-3.
+
+    In training mode batch norm cancels the bias of the transposed convolution in front of it, so the bias is not added (its
+    gradient is exactly zero and none is handed back: the optimizer leaves it alone) and the moving mean is corrected by
+    momentum * bias, which keeps inference -- where the bias is added -- in step."""
+
+    def __init__(self, latent_dim=100, channels=128, base=8, n_up=4):
+        nn = _nn()
+        super().__init__()
+        self.latent_dim, self.channels, self.base, self.n_up = int(latent_dim), int(channels), int(base), int(n_up)
+        self.size = self.base * 2 ** self.n_up
+        self.branches = nn.ModuleList()
+        for _ in range(3):
+            br = nn.Module()
+            br.dense = nn.Linear(self.latent_dim, self.base * self.base * self.channels)
+            br.ups = nn.ModuleList([nn.ConvTranspose2d(self.channels, self.channels, 4, stride=2, padding=1) for _ in range(self.n_up)])
+            br.bns = nn.ModuleList([nn.BatchNorm2d(self.channels, eps=1e-3, momentum=0.01) for _ in range(self.n_up)])
+            br.out = nn.Conv2d(self.channels, 1, 7, padding=3)
+            self.branches.append(br)
+        for mod in self.modules():
+            if isinstance(mod, (nn.Conv2d, nn.ConvTranspose2d, nn.Linear)):
+                nn.init.normal_(mod.weight, 0.0, 0.02)      # RandomNormal(stddev=0.02), sgan.py:60
+                nn.init.zeros_(mod.bias)
+
+    def _branch(self, z, br, adt):
+        import torch
+        import torch.nn.functional as F
+        from .nn_common import bn_lrelu_pad, conv7_tanh, conv7_tanh_fused
+        n = z.shape[0]
+        h = F.relu(br.dense(z)).reshape(n, self.base, self.base, self.channels).permute(0, 3, 1, 2)      # NHWC storage, no copy
+        fused = _FUSED_LAYERS and z.is_cuda and self.training and adt in (torch.float16, torch.bfloat16)
+        for up, bn in zip(br.ups, br.bns):
+            if not self.training:
+                h = F.relu(bn(up(h)))
+                continue
+            zt = F.conv_transpose2d(h, up.weight, None, stride=2, padding=1)
+            if fused:
+                h = bn_lrelu_pad(zt, bn, slope=0.0, pad=0, conv_bias=up.bias)
+            else:
+                if bn.track_running_stats and bn.momentum is not None:
+                    # the statistics are those of conv(x) + bias, whose mean is larger by exactly the bias: new = (1 - m) old + m (mean + b).
+                    # Applied to the old value, in front of the layer (autograd keeps the buffer the layer saw)
+                    m = float(bn.momentum)
+                    with torch.no_grad():
+                        bn.running_mean.add_(up.bias.detach().to(bn.running_mean.dtype), alpha=m / (1.0 - m))
+                h = F.relu(bn(zt))
+        if fused and conv7_tanh_fused(h, br.out):
+            return conv7_tanh(h, br.out)
+        return torch.tanh(br.out(h)).float() if h.dtype in (torch.float16, torch.bfloat16) else torch.tanh(br.out(h))
+
+    def forward(self, z):
+        """[xz, yz, xy] images in [-1, 1], each (n, 1, S, S)."""
+        import torch
+        adt = torch.get_autocast_dtype("cuda") if (z.is_cuda and torch.is_autocast_enabled("cuda")) else None
+        return [self._branch(z, br, adt) for br in self.branches]
+
+    def predict(self, z, batch_size=256, return_numpy=True, amp_dtype=None):
+        """``g_model.predict(z)`` (sgan.py:450): inference mode (moving statistics), a list of three (n, S, S, 1) float32 arrays
+        in [-1, 1]; with ``return_numpy=False`` three (n, 1, S, S) float32 tensors on the model's device, which
+        ``DiscriminatorTrainer.train_on_batch_d`` takes without a host trip.  ``amp_dtype``: run the layers under autocast."""
+        import torch
+        dev = next(self.parameters()).device
+        dt = next(self.parameters()).dtype
+        zt = z if isinstance(z, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(z))
+        zt = zt.to(device=dev, dtype=dt)
+        was_training = self.training
+        self.eval()
+        outs = [[], [], []]
+        try:
+            with torch.no_grad():
+                for s in range(0, zt.shape[0], batch_size):
+                    if amp_dtype is not None and dev.type == "cuda":
+                        with torch.autocast("cuda", dtype=amp_dtype):
+                            imgs = self(zt[s:s + batch_size])
+                    else:
+                        imgs = self(zt[s:s + batch_size])
+                    for o, im in zip(outs, imgs):
+                        o.append(im.float())
+        finally:
+            self.train(was_training)
+        cat = [torch.cat(o) if o else torch.zeros((0, 1, self.size, self.size), device=dev) for o in outs]
+        if not return_numpy:
+            return [c.contiguous() for c in cat]
+        return [c.permute(0, 2, 3, 1).contiguous().cpu().numpy() for c in cat]
+
+    # ---- Keras layout in / out -------------------------------------------------------------------------
+    def keras_weights(self):
+        """Parameters and moving statistics in Keras layouts, float64 numpy; per branch
+        ``[(dense kernel (latent, base*base*channels), bias), [(ConvT kernel (4, 4, out, in), bias, gamma, beta, moving_mean,
+        moving_variance)] x n_up, (output kernel (7, 7, channels, 1), bias)]``."""
+        def a(t):
+            return t.detach().double().cpu().numpy()
+        out = []
+        for br in self.branches:
+            ups = [(a(up.weight.permute(2, 3, 1, 0)), a(up.bias), a(bn.weight), a(bn.bias), a(bn.running_mean), a(bn.running_var))
+                   for up, bn in zip(br.ups, br.bns)]
+            out.append([(a(br.dense.weight.t()), a(br.dense.bias)), ups, (a(br.out.weight.permute(2, 3, 1, 0)), a(br.out.bias))])
+        return out
+
+    def set_keras_weights(self, branches):
+        """Inverse of :meth:`keras_weights` (what ``layer.get_weights()`` of a trained ``g_model_XXXX.h5`` holds, sgan.py:496-497)."""
+        import torch
+        if len(branches) != len(self.branches):
+            raise ValueError("expected %d branches" % len(self.branches))
+
+        def put(dst, arr, what):
+            t = torch.as_tensor(np.asarray(arr), dtype=dst.dtype)
+            if tuple(t.shape) != tuple(dst.shape):
+                raise ValueError("%s: Keras array gives %s, the layer holds %s" % (what, tuple(t.shape), tuple(dst.shape)))
+            dst.copy_(t.to(dst.device))
+
+        with torch.no_grad():
+            for bi, (br, (dense, ups, outc)) in enumerate(zip(self.branches, branches)):
+                if len(ups) != len(br.ups):
+                    raise ValueError("branch %d: expected %d (transposed convolution + batch-norm) tuples" % (bi, len(br.ups)))
+                put(br.dense.weight, np.asarray(dense[0]).T, "branch %d dense kernel" % bi)
+                put(br.dense.bias, dense[1], "branch %d dense bias" % bi)
+                for li, (up, bn, (k, b, g, be, mu, var)) in enumerate(zip(br.ups, br.bns, ups)):
+                    what = "branch %d layer %d" % (bi, li)
+                    put(up.weight, np.asarray(k).transpose(3, 2, 0, 1), what + " kernel")
+                    put(up.bias, b, what + " bias")
+                    put(bn.weight, g, what + " gamma"); put(bn.bias, be, what + " beta")
+                    put(bn.running_mean, mu, what + " moving_mean"); put(bn.running_var, var, what + " moving_variance")
+                put(br.out.weight, np.asarray(outc[0]).transpose(3, 2, 0, 1), "branch %d output kernel" % bi)
+                put(br.out.bias, outc[1], "branch %d output bias" % bi)
+        return self
+
+
+def define_generator(latent_dim=100, device=None):
+    """Counterpart of sgan.define_generator (sgan.py:90-122): the model on the device, channels_last."""
+    import torch
+    dev = torch.device(device) if device is not None else (
+        torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu"))
+    return Generator(latent_dim=latent_dim).to(dev).to(memory_format=torch.channels_last)
+
+
+class GanTrainer:
+    """``define_gan`` + ``gan_model.train_on_batch`` (sgan.py:220-235, 534-537): the loss is ``d_loss(D(G(z)), y)``.
+    ``define_gan`` freezes every discriminator layer except BatchNormalization, so this optimizer -- its own
+    Adam(2e-4, beta1 0.5, eps 1e-7) -- updates all generator parameters and the discriminator's BatchNorm gammas and betas
+    (1 600 values at the default size).  During the step the discriminator runs in training mode (batch statistics, moving
+    statistics and counters advance, dropout active); its other weights get no gradient at all (``torch.autograd.grad`` over the
+    trained parameters only: the weight-gradient convolutions are skipped) and nothing is frozen afterwards.  The loss scale is the
+    discriminator trainer's.  ``.grad`` is never touched, so a trainer with captured heads keeps its gradient tensors."""
+
+    def __init__(self, generator, disc_trainer, lr=2e-4, beta1=0.5):
+        import torch
+        import torch.distributed as dist
+        nn = _nn()
+        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+            raise NotImplementedError("GanTrainer: data parallelism of the generator step is not implemented")
+        self.generator, self.disc_trainer, self.disc = generator, disc_trainer, disc_trainer.model
+        self.device = disc_trainer.device
+        if next(generator.parameters()).device != self.device:
+            raise ValueError("GanTrainer: generator and discriminator live on different devices")
+        self.bn_params = [p for m in self.disc.modules() if isinstance(m, (nn.BatchNorm1d, nn.BatchNorm2d)) for p in (m.weight, m.bias)]
+        self.params = [p for p in generator.parameters() if p.requires_grad] + self.bn_params
+        ids = {id(p): k for k, p in self.disc.named_parameters()}
+        self.param_names = ["g." + k for k, p in generator.named_parameters() if p.requires_grad] + ["d." + ids[id(p)] for p in self.bn_params]
+        self.opt = torch.optim.Adam(self.params, lr=lr, betas=(beta1, 0.999), eps=1e-7, fused=self.device.type == "cuda")
+        self._dev_adam = None
+        if disc_trainer._dev_adam is not None:
+            from .nn_common import DeviceAdam
+            shared = next(iter(disc_trainer._dev_adam.values())).state
+            self._dev_adam = DeviceAdam(self.params, lr, (beta1, 0.999), 1e-7, scale=disc_trainer._scale_t, scaler_state=shared, mirror=self.opt)
+
+    def _loss(self, z, y):
+        import torch
+        dt = self.disc_trainer
+        self.generator.train()
+        self.disc.train()
+        zt = (z if isinstance(z, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(z))).to(
+            device=self.device, dtype=next(self.generator.parameters()).dtype)
+        yt = (y if isinstance(y, torch.Tensor) else torch.as_tensor(np.asarray(y))).to(self.device).float()
+        if dt.amp_dtype is not None:
+            with torch.autocast("cuda", dtype=dt.amp_dtype):
+                logits = self.disc(*self.generator(zt))
+        else:
+            logits = self.disc(*self.generator(zt))
+        return d_loss(logits, yt)
+
+    def gradients(self, z, y):
+        """(loss, gradients of the SCALED loss for ``self.params``, None where a parameter takes no part) without an update."""
+        import torch
+        loss = self._loss(z, y)
+        grads = list(torch.autograd.grad(self.disc_trainer._scaled(loss), self.params, allow_unused=True))
+        for i, (p, g) in enumerate(zip(self.params, grads)):
+            # laid out like the parameter (channels_last kernels), as the accumulation into .grad would have done: the fused Adam
+            # runs over the storage order
+            if g is not None and (g.stride() != p.stride() or g.dtype != p.dtype):
+                grads[i] = torch.empty_like(p, memory_format=torch.preserve_format).copy_(g)
+        return loss.detach(), grads
+
+    def train_on_batch_g(self, z, y, sync=True):
+        """gan_model.train_on_batch(z, y) -> loss (float, or a 0-d tensor with ``sync=False``); ``y``: the smoothed positives."""
+        loss, grads = self.disc_trainer._tuned(self.gradients, z, y)
+        if self._dev_adam is not None:
+            self._dev_adam.step(grads)
+        else:
+            # torch's optimizers read .grad: lend it the gradients for the update and hand back what was there
+            kept = [p.grad for p in self.params]
+            try:
+                for p, g in zip(self.params, grads):
+                    p.grad = g
+                self.disc_trainer.scaler.step(self.opt)
+                self.disc_trainer.scaler.update()
+            finally:
+                for p, g in zip(self.params, kept):
+                    p.grad = g
+        return float(loss) if sync else loss
+
+
+# ---- fake samples, the data product, the loop (sgan.py:396-543) ----------------------------------------------------------
+
+def smooth_positive_labels(y, rng):
+    """class 1 -> [0.7, 1.2) (sgan.py:396-398)"""
+    return y - 0.3 + rng.random(y.shape) * 0.5
+
+
+def smooth_negative_labels(y, rng):
+    """class 0 -> [0, 0.3) (sgan.py:401-403)"""
+    return y + rng.random(y.shape) * 0.3
+
+
+def generate_latent_points(latent_dim, n, rng):
+    """sgan.py:439-442: (n, latent_dim) standard normal points."""
+    return rng.standard_normal(size=(n, latent_dim))
+
+
+def generate_fake_samples(generator, latent_dim, n, rng, return_numpy=True, amp_dtype=None):
+    """sgan.py:445-454: ``generator.predict`` on n latent points, and their labels in [0, 0.3)."""
+    z = generate_latent_points(latent_dim, n, rng)
+    images = generator.predict(z, return_numpy=return_numpy, amp_dtype=amp_dtype)
+    return images, smooth_negative_labels(np.zeros((n, 1)), rng)
+
+
+def generated_samples(generator, latent_dim, n, rng, sizes=(XZ_SIZE, YZ_SIZE, XY_SIZE)):
+    """The samples of ``summarize_performance`` (sgan.py:462-483): n fake images scaled to RADAR_MAX * (v + 1) / 2 and resized back
+    to the radar arena with Pillow's BICUBIC (csrc/resize.hip, bit-identical to Pillow); ``sizes`` in Pillow's (cols, rows) order.
+    Returns a list of (xz, yz, xy) float32 tuples."""
+    from .common import RADAR_MAX
+    from .nn_common import resize_bicubic
+    fake, _ = generate_fake_samples(generator, latent_dim, n, rng, return_numpy=False)
+    planes = []
+    for v, (cols, rows) in zip(fake, sizes):
+        p = (float(RADAR_MAX) * (v[:, 0] + 1.0) / 2.0).contiguous()
+        planes.append(resize_bicubic(p, (int(rows), int(cols)), scale=False).cpu().numpy())
+    return [(planes[0][i], planes[1][i], planes[2][i]) for i in range(n)]
+
+
+def save_generated(path, samples):
+    """``generated_data_XXXX.pickle`` (sgan.py:483-488): the data-set format of datasets.py with every label 'generated_data'."""
+    data = {"samples": [tuple(np.asarray(p, np.float32) for p in s) for s in samples], "labels": ["generated_data"] * len(samples)}
+    with open(path, "wb") as fp:
+        pickle.dump(data, fp)
+    return len(data["labels"])
+
+
+def _flatten_weights(obj, prefix="w"):
+    if isinstance(obj, (list, tuple)):
+        out = {}
+        for i, o in enumerate(obj):
+            out.update(_flatten_weights(o, "%s_%d" % (prefix, i)))
+        return out
+    return {prefix: np.asarray(obj)}
+
+
+def save_model_npz(path, model):
+    """``model.keras_weights()`` as an ``.npz`` (keys w_<index path>): the stand-in for the reference's ``.h5`` files."""
+    np.savez(path, **_flatten_weights(model.keras_weights()))
+
+
+def select_supervised_samples(dataset, rng, n_samples=150, n_classes=3):
+    """sgan.py:406-422: a class-balanced supervised subset (drawn with replacement from the samples flagged ``sup``)."""
+    X, y, sup = dataset
+    y, sup = np.asarray(y), np.asarray(sup, dtype=bool)
+    n_per_class = int(n_samples / n_classes)
+    ix_all, y_all = [], []
+    for c in range(n_classes):
+        cand = np.nonzero((y == c) & sup)[0]
+        if len(cand) == 0:
+            raise ValueError("no supervised samples of class %d" % c)
+        ix_all.append(cand[rng.integers(0, len(cand), n_per_class)])
+        y_all += [c] * n_per_class
+    return np.concatenate(ix_all), np.asarray(y_all)
+
+
+def train(g_model, disc_trainer, gan, train_set, val_set, n_classes, w_classes=None, latent_dim=100, n_epochs=15, n_batch=32,
+          results_dir=None, seed=1234):
+    """The training loop of sgan.py:504-543: per step the four updates c, d on real samples, d on fake samples, g; per epoch the
+    classifier's accuracy on ``val_set``, ``generated_data_%04d.pickle`` and the models (``.npz`` of ``keras_weights()``).
+    ``train_set`` = (X (N, H, W, 3), y, sup), ``val_set`` = (X, y, ...).  The data set is uploaded once and batches are gathered
+    on the device; every draw comes from one ``np.random.default_rng(seed)``.  Returns the per-step (c_loss, c_acc, dr_loss,
+    df_loss, g_loss)."""
+    import torch
+    rng = np.random.default_rng(seed)
+    dev = disc_trainer.device
+    X = torch.as_tensor(np.asarray(train_set[0]), dtype=torch.float32).to(dev)
+    planes = [X[..., i].unsqueeze(1).contiguous() for i in range(3)]          # three (N, 1, H, W), resident
+    sup_ix, y_sup = select_supervised_samples(train_set, rng, n_classes=n_classes)
+    bat_per_epo = int(X.shape[0] / n_batch)
+    n_steps = bat_per_epo * n_epochs
+    half_batch = int(n_batch / 2)
+    logger.info("Starting training loop.")
+    logger.info("n_epochs=%d, n_batch=%d, 1/2=%d, b/e=%d, steps=%d" % (n_epochs, n_batch, half_batch, bat_per_epo, n_steps))
+
+    def gather(ix):
+        it = torch.as_tensor(ix, dtype=torch.long, device=dev)
+        return [p.index_select(0, it) for p in planes]
+
+    history = []
+    for i in range(n_steps):
+        ix = rng.integers(0, len(sup_ix), half_batch)
+        c_l, c_acc = disc_trainer.train_on_batch_c(gather(sup_ix[ix]), y_sup[ix])
+        ix = rng.integers(0, X.shape[0], half_batch)
+        y_real = smooth_positive_labels(np.ones((half_batch, 1)), rng)
+        dr_l = disc_trainer.train_on_batch_d(gather(ix), y_real, class_weight=w_classes)
+        x_fake, y_fake = generate_fake_samples(g_model, latent_dim, half_batch, rng, return_numpy=False, amp_dtype=disc_trainer.amp_dtype)
+        df_l = disc_trainer.train_on_batch_d(x_fake, y_fake)
+        z = generate_latent_points(latent_dim, n_batch, rng)
+        g_l = gan.train_on_batch_g(z, smooth_positive_labels(np.ones((n_batch, 1)), rng))
+        logger.debug("Training results at step %d: c[%.3f,%.0f], d_r[%.3f], d_f[%.3f], g[%.3f]" % (i + 1, c_l, c_acc * 100, dr_l, df_l, g_l))
+        history.append((c_l, c_acc, dr_l, df_l, g_l))
+        if bat_per_epo and (i + 1) % bat_per_epo == 0:
+            Xv = np.asarray(val_set[0])
+            _, acc = disc_trainer.evaluate([Xv[..., 0], Xv[..., 1], Xv[..., 2]], val_set[1])
+            logger.info("Classifier accuracy at step %d: %.2f%%" % (i + 1, acc * 100))
+            if results_dir is not None:
+                f1 = os.path.join(results_dir, "generated_data_%04d.pickle" % (i + 1))
+                f2 = os.path.join(results_dir, "g_model_%04d.npz" % (i + 1))
+                f3 = os.path.join(results_dir, "c_model_%04d.npz" % (i + 1))
+                save_generated(f1, generated_samples(g_model, latent_dim, 100, rng))
+                save_model_npz(f2, g_model)
+                save_model_npz(f3, disc_trainer.model)
+                logger.info("Saved: %s, %s, and %s" % (f1, f2, f3))
+    return history
