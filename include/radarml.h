@@ -632,6 +632,34 @@ int rml_dnn_dense_tail_f32(rml_ctx* ctx, const float* feat, int64_t ld_feat, int
                            const float* w2t, const float* b2, const float* w3, const float* b3, int n_classes, float* workspace,
                            int64_t workspace_bytes, float* proba, void* stream);
 
+/* ---- SGAN classifier at inference (sgan.py:132-199, c_model.predict), fused -----------------------------------------------------
+ * The trunk: per branch Conv2D(1->128, 3x3, s2, 'same') -> Conv2D(128->64, s2) -> Conv2D(64->32, s2), each followed by BatchNorm and
+ * LeakyReLU(slope); in inference mode the BatchNorm is an affine map and the CALLER folds it into the weights: s = gamma /
+ * sqrt(moving_variance + eps), w' = w * s, b' = beta + (bias - moving_mean) * s.  Inputs as rml_dnn_trunk: three (B, H, W) planes in
+ * [-1, 1], float32 (in_bf16 = 0, rounded to bf16 on load) or bf16 (in_bf16 = 1): identical results.  A window is loaded as
+ * aligned pairs; the neighbouring value a pair brings along is masked to zero, so a non-finite plane value reaches only the pixels
+ * whose 3x3 window holds it, as in the reference convolution.  Folded weights (DEVICE), k =
+ * (ky*3+kx)*Cin + cin: w1 [3][128][9] float32, b1 [3][128]; w2t [3][64][1152] bf16, b2 [3][64] float32; w3t [3][32][576] bf16, b3
+ * [3][32] float32.  feat[b][(h*(W/8)+w)*96 + branch*32 + n] bf16 -- Keras' Flatten of the concatenated branches.  bf16 operands on the
+ * matrix cores, float32 accumulation; biases and LeakyReLU in float32 before the rounding to bf16; 0 <= slope <= 1.  The layer-1
+ * activation is recomputed where layer 2 reads it and never stored; the layer-2 activation goes through the workspace.  No atomics:
+ * a sample's features are the same bits alone, at any position of any batch, and on a second call.
+ * rml_sgan_trunk_supported (HOST, no device): H and W multiples of 8 (every stride-2 'same' layer then sees an even size and pads
+ * bottom / right only), W <= 128, H <= 32 768; anything else: 0, and rml_sgan_trunk returns RML_ERR_UNSUPPORTED without a launch.
+ * workspace: rml_sgan_trunk_workspace_bytes(B, H, W) bytes (0 for unsupported planes; non-decreasing in B), 16-byte aligned, as are
+ * the planes, w2t, w3t and feat. */
+int rml_sgan_trunk_supported(int H, int W);
+int64_t rml_sgan_trunk_workspace_bytes(int64_t B, int H, int W);
+int rml_sgan_trunk(rml_ctx* ctx, const void* xz, const void* yz, const void* xy, int in_bf16, int64_t B, int H, int W,
+                   const float* w1, const float* b1, const uint16_t* w2t, const float* b2, const uint16_t* w3t, const float* b3,
+                   float slope, uint16_t* feat, void* workspace, int64_t workspace_bytes, void* stream);
+/* rml_dnn_dense_tail (row-major features, kblock = 0) with LeakyReLU(slope) instead of relu behind the two hidden layers: x > 0 ? x :
+ * slope * x.  The BatchNorm1d layers behind fc1 / fc2 fold into w1 / b1 and w2t / b2 on the host.  The same split-K first layer
+ * (fixed K pieces, summed in order), the same workspace size (rml_dnn_dense_workspace_bytes). */
+int rml_dense_tail_lrelu(rml_ctx* ctx, const uint16_t* feat, int64_t ld_feat, int64_t N, int64_t K, const uint16_t* w1, const float* b1,
+                         const float* w2t, const float* b2, const float* w3, const float* b3, int n_classes, float slope,
+                         float* workspace, int64_t workspace_bytes, float* proba, void* stream);
+
 /* ---- dnn.py training step (dnn.py:347-390: model.fit on the model of dnn.py:45-91), float32 -----------------------------------
  * One step on the batch rows[0..B) of RESIDENT data: three float32 plane sets xz / yz / xy, [N][H][W] each, already scaled to
  * [-1, 1] and resized (H, W multiples of 4, W <= 128: rml_dnn_train_supported; others RML_ERR_UNSUPPORTED), labels [N] int32 in

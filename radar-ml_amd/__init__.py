@@ -26,7 +26,7 @@ __all__ = [
     "classifier", "classify_batch", "calc_proj_zoom", "synth_volumes",
     "DataGenerator", "augment_planes", "rotation_params", "GridSearchSVC", "find_best_svm_estimator", "fit_svc",
     "GridSearchSGD", "find_best_sgd_svm_estimator", "fit_sgd", "partial_fit_sgd",
-    "define_classifier", "train_classifier",
+    "define_classifier", "train_classifier", "define_discriminator", "fold_batchnorm", "folded_packs",
 ]
 
 
@@ -35,4 +35,8 @@ def __getattr__(name):
     if name in ("define_classifier", "train_classifier"):
         from . import dnn
         return dnn.define_classifier if name == "define_classifier" else dnn.train
+    # the SGAN classifier (sgan.py): the model whose forward_fused / predict_volumes run csrc/sgan_infer.hip, and its folded weights
+    if name in ("define_discriminator", "fold_batchnorm", "folded_packs"):
+        from . import sgan
+        return getattr(sgan, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

@@ -115,6 +115,12 @@ SIGNATURES = {
     "rml_dnn_dense_tail_f32_workspace_bytes": (c_int64, [c_int64, c_int64]),
     "rml_dnn_dense_tail_f32": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                        c_void_p, c_int, c_void_p, c_int64, c_void_p, c_void_p]),
+    "rml_sgan_trunk_supported": (c_int, [c_int, c_int]),
+    "rml_sgan_trunk_workspace_bytes": (c_int64, [c_int64, c_int, c_int]),
+    "rml_sgan_trunk": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                               c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_int64, c_void_p]),
+    "rml_dense_tail_lrelu": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                     c_void_p, c_int, c_float, c_void_p, c_int64, c_void_p, c_void_p]),
     "rml_dnn_train_supported": (c_int, [c_int, c_int, c_int]),
     "rml_dnn_train_workspace_bytes": (c_int64, [c_int, c_int, c_int, c_int]),
     "rml_dnn_train_step": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_void_p, c_int,

@@ -16,6 +16,8 @@
 //  * k_dense_finish: one wave per sample sums the partials in piece order (deterministic), adds the bias, relu; the two small
 //    layers run in float32 in the wave (lane = output unit, the previous layer's activations broadcast with v_readlane), softmax in
 //    lane order.  Activations between the layers stay float32 (the autocast chain this replaces rounded them to bf16).
+//    Instantiated per activation: relu (this tail), LeakyReLU (rml_dense_tail_lrelu: the SGAN classifier's tail, sgan.py:187-199, on
+//    the 24 576-long rows of sgan_infer.hip with the BatchNorm layers folded into the kernels by the caller).
 #include "rml_internal.h"
 
 namespace {
@@ -189,6 +191,7 @@ struct FinishArgs {
     const float* b3;            // [C]
     int C;
     float* out;                 // [N][C] probabilities
+    float slope;                // k_dense_finish<true>: LeakyReLU slope of the two hidden layers
 };
 
 template <int CTRL, int ROW_MASK, bool BOUND>
@@ -207,6 +210,15 @@ __device__ __forceinline__ float wave_sum(float r) {
     return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(r), 63));
 }
 
+// LRELU = false: relu as fmaxf(x, 0) -- the CNN's tail, whose bits are pinned (a LeakyReLU with slope 0 is NOT the same function:
+// 0 * x gives -0.0 where fmaxf gives +0.0); true: x > 0 ? x : slope * x (the SGAN classifier's hidden layers)
+template <bool LRELU>
+__device__ __forceinline__ float dense_act(float x, float slope) {
+    if constexpr (LRELU) return x > 0.0f ? x : slope * x;
+    else return fmaxf(x, 0.0f);
+}
+
+template <bool LRELU>
 __global__ __launch_bounds__(256) void k_dense_finish(FinishArgs a) {
     __shared__ float w2s[kHidden * kHidden];
     const int tid = threadIdx.x, lane = tid & 63;
@@ -234,7 +246,7 @@ __global__ __launch_bounds__(256) void k_dense_finish(FinishArgs a) {
     int64_t n = (int64_t)blockIdx.x * 4 + (tid >> 6);
     float hn = gather(n);
     for (; n < a.N; n += nw) {
-        const float h = fmaxf(hn + b1, 0.0f);
+        const float h = dense_act<LRELU>(hn + b1, a.slope);
         hn = gather(n + nw);
         // second layer: lane = output unit; four independent chains over the 64 inputs (each input broadcast with v_readlane)
         float g0 = b2, g1 = 0.0f, g2 = 0.0f, g3 = 0.0f;
@@ -245,7 +257,7 @@ __global__ __launch_bounds__(256) void k_dense_finish(FinishArgs a) {
             g2 = fmaf(__int_as_float(__builtin_amdgcn_readlane(__float_as_int(h), k + 2)), w2s[(k + 2) * kHidden + lane], g2);
             g3 = fmaf(__int_as_float(__builtin_amdgcn_readlane(__float_as_int(h), k + 3)), w2s[(k + 3) * kHidden + lane], g3);
         }
-        const float g = fmaxf((g0 + g1) + (g2 + g3), 0.0f);
+        const float g = dense_act<LRELU>((g0 + g1) + (g2 + g3), a.slope);
         // logits in every lane (C <= 16), softmax in float32 like torch.softmax(lg.float())
         float lg[16];
         float mx = -INFINITY;
@@ -389,19 +401,20 @@ extern "C" int64_t rml_dnn_dense_workspace_bytes(rml_ctx* ctx, int64_t N, int64_
     return (int64_t)fixed_pieces((int)(K / 64)) * N * kHidden * (int64_t)sizeof(float);
 }
 
-extern "C" int rml_dnn_dense_tail(rml_ctx* ctx, const uint16_t* feat, int64_t ld_feat, int kblock, int64_t N, int64_t K, const uint16_t* w1, const float* b1,
-                                  const float* w2t, const float* b2, const float* w3, const float* b3, int n_classes, float* workspace,
-                                  int64_t workspace_bytes, float* proba, void* stream) {
-    RML_REQUIRE(ctx && N >= 0 && K > 0, RML_ERR_INVALID, "rml_dnn_dense_tail: bad arguments");
+// the bf16 tail with either activation: k_fc1_splitk is shared, the finishing kernel is instantiated per activation
+static int dense_tail_bf16(const char* who, rml_ctx* ctx, const uint16_t* feat, int64_t ld_feat, int kblock, int64_t N, int64_t K, const uint16_t* w1, const float* b1,
+                           const float* w2t, const float* b2, const float* w3, const float* b3, int n_classes, bool lrelu, float slope,
+                           float* workspace, int64_t workspace_bytes, float* proba, void* stream) {
+    RML_REQUIRE(ctx && N >= 0 && K > 0, RML_ERR_INVALID, "%s: bad arguments", who);
     RML_REQUIRE(K % 64 == 0 && (kblock || (ld_feat >= K && ld_feat % 8 == 0)), RML_ERR_UNSUPPORTED,
-                "rml_dnn_dense_tail: K = %lld must be a multiple of 64 (ld_feat of 8)", (long long)K);
-    RML_REQUIRE(n_classes >= 1 && n_classes <= 16, RML_ERR_UNSUPPORTED, "rml_dnn_dense_tail: 1..16 classes");
+                "%s: K = %lld must be a multiple of 64 (ld_feat of 8)", who, (long long)K);
+    RML_REQUIRE(n_classes >= 1 && n_classes <= 16, RML_ERR_UNSUPPORTED, "%s: 1..16 classes", who);
     if (N == 0) return RML_OK;
-    RML_REQUIRE(feat && w1 && b1 && w2t && b2 && w3 && b3 && workspace && proba, RML_ERR_INVALID, "rml_dnn_dense_tail: NULL argument");
+    RML_REQUIRE(feat && w1 && b1 && w2t && b2 && w3 && b3 && workspace && proba, RML_ERR_INVALID, "%s: NULL argument", who);
     RML_REQUIRE(((reinterpret_cast<uintptr_t>(feat) | reinterpret_cast<uintptr_t>(w1) | reinterpret_cast<uintptr_t>(workspace)) & 15) == 0,
-                RML_ERR_INVALID, "rml_dnn_dense_tail: feat, w1 and the workspace need 16-byte alignment");
-    RML_REQUIRE(N < (int64_t)1 << 31 && K < (int64_t)1 << 30, RML_ERR_UNSUPPORTED, "rml_dnn_dense_tail: too large");
-    RML_REQUIRE(workspace_bytes >= rml_dnn_dense_workspace_bytes(ctx, N, K), RML_ERR_INVALID, "rml_dnn_dense_tail: workspace too small");
+                RML_ERR_INVALID, "%s: feat, w1 and the workspace need 16-byte alignment", who);
+    RML_REQUIRE(N < (int64_t)1 << 31 && K < (int64_t)1 << 30, RML_ERR_UNSUPPORTED, "%s: too large", who);
+    RML_REQUIRE(workspace_bytes >= rml_dnn_dense_workspace_bytes(ctx, N, K), RML_ERR_INVALID, "%s: workspace too small", who);
     RML_HIP(hipSetDevice(ctx->device));
     hipStream_t st = static_cast<hipStream_t>(stream);
     const int64_t tiles = (N + kXRows - 1) / kXRows;
@@ -420,10 +433,25 @@ extern "C" int rml_dnn_dense_tail(rml_ctx* ctx, const uint16_t* feat, int64_t ld
     hipLaunchKernelGGL(k_fc1_splitk, dim3((unsigned)(tiles * fa.S)), dim3(256), 0, st, fa);
     FinishArgs fi{};
     fi.partial = workspace; fi.S = nf; fi.N = N; fi.b1 = b1; fi.w2t = w2t; fi.b2 = b2; fi.w3 = w3; fi.b3 = b3; fi.C = n_classes; fi.out = proba;
+    fi.slope = slope;
     const int64_t blocks = (N + 3) / 4;
-    hipLaunchKernelGGL(k_dense_finish, dim3((unsigned)(blocks < 2 * ctx->num_cu ? blocks : 2 * ctx->num_cu)), dim3(256), 0, st, fi);
+    const dim3 grid((unsigned)(blocks < 2 * ctx->num_cu ? blocks : 2 * ctx->num_cu));
+    if (lrelu) hipLaunchKernelGGL(k_dense_finish<true>, grid, dim3(256), 0, st, fi);
+    else hipLaunchKernelGGL(k_dense_finish<false>, grid, dim3(256), 0, st, fi);
     RML_HIP(hipGetLastError());
     return RML_OK;
+}
+
+extern "C" int rml_dnn_dense_tail(rml_ctx* ctx, const uint16_t* feat, int64_t ld_feat, int kblock, int64_t N, int64_t K, const uint16_t* w1, const float* b1,
+                                  const float* w2t, const float* b2, const float* w3, const float* b3, int n_classes, float* workspace,
+                                  int64_t workspace_bytes, float* proba, void* stream) {
+    return dense_tail_bf16("rml_dnn_dense_tail", ctx, feat, ld_feat, kblock, N, K, w1, b1, w2t, b2, w3, b3, n_classes, false, 0.0f, workspace, workspace_bytes, proba, stream);
+}
+
+extern "C" int rml_dense_tail_lrelu(rml_ctx* ctx, const uint16_t* feat, int64_t ld_feat, int64_t N, int64_t K, const uint16_t* w1, const float* b1,
+                                    const float* w2t, const float* b2, const float* w3, const float* b3, int n_classes, float slope,
+                                    float* workspace, int64_t workspace_bytes, float* proba, void* stream) {
+    return dense_tail_bf16("rml_dense_tail_lrelu", ctx, feat, ld_feat, 0, N, K, w1, b1, w2t, b2, w3, b3, n_classes, true, slope, workspace, workspace_bytes, proba, stream);
 }
 
 extern "C" int64_t rml_dnn_dense_tail_f32_workspace_bytes(int64_t N, int64_t K) {
@@ -458,7 +486,7 @@ extern "C" int rml_dnn_dense_tail_f32(rml_ctx* ctx, const float* feat, int64_t l
     FinishArgs fi{};
     fi.partial = workspace; fi.S = fa.S; fi.N = N; fi.b1 = b1; fi.w2t = w2t; fi.b2 = b2; fi.w3 = w3; fi.b3 = b3; fi.C = n_classes; fi.out = proba;
     const int64_t blocks = (N + 3) / 4;
-    hipLaunchKernelGGL(k_dense_finish, dim3((unsigned)(blocks < 2 * ctx->num_cu ? blocks : 2 * ctx->num_cu)), dim3(256), 0, st, fi);
+    hipLaunchKernelGGL(k_dense_finish<false>, dim3((unsigned)(blocks < 2 * ctx->num_cu ? blocks : 2 * ctx->num_cu)), dim3(256), 0, st, fi);
     RML_HIP(hipGetLastError());
     return RML_OK;
 }

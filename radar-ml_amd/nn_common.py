@@ -593,4 +593,9 @@ class DeviceAdam:
                 _lib.ptr(self.step_count), _lib.ptr(self.scale), _lib.ptr(self.state), _lib.ptr(self.inv_scale),
                 1 if self.scale is not None else 0, self.growth, self.backoff, self.growth_interval, _lib.stream_ptr(self.device)),
                 "rml_adam_step")
+        # the library wrote the parameters through raw pointers: tell torch (weight packs key on the version counters:
+        # Discriminator._cached, Classifier._cached).  Also after a step the loss-scale rule skipped on the device (the host does
+        # not know: a pack is then rebuilt from unchanged weights), and it is the ONLY signal after a step whose forward and backward
+        # were replayed from a captured graph -- a replay advances num_batches_tracked without touching its version counter.
+        torch.autograd.graph.increment_version(self.params)
 

@@ -84,6 +84,7 @@ class Discriminator(_nn().Module):
         # backward of the fused conv + batch-norm layers: zeros for the (cancelled) convolution bias, or no gradient at all
         # (nn_common.fused_step_scope; DiscriminatorTrainer turns the zeros off unless torch's DDP wraps the model)
         self.zero_bias_grads = True
+        self._packs = {}                            # name -> (key of the tensors it was made from, value): _cached
         for mod in self.modules():
             if isinstance(mod, (nn.Conv2d, nn.Linear)):
                 nn.init.normal_(mod.weight, 0.0, 0.02)      # RandomNormal(stddev=0.02), sgan.py:176
@@ -147,6 +148,135 @@ class Discriminator(_nn().Module):
         return F.linear(h, half[self.fc3.weight], half[self.fc3.bias])
 
 
+    # ---- inference on the fused HIP chain (csrc/sgan_infer.hip + the LeakyReLU tail of csrc/dense.hip) ---------------
+    def _cached(self, name, tensors, make):
+        """``make()``, kept under ``name`` until one of ``tensors`` is written: the key holds the version counter and the storage
+        of every parameter AND every BatchNorm buffer, so an optimizer step, a training-mode forward (``num_batches_tracked``
+        advances), ``set_keras_weights``, ``load_state_dict`` or ``.to()`` in between makes the next call rebuild the packs."""
+        key = tuple((t._version, t.data_ptr()) for t in tensors)
+        hit = self._packs.get(name)
+        if hit is None or hit[0] != key:
+            hit = self._packs[name] = (key, make())
+        return hit[1]
+
+    def folded_packs(self):
+        """:func:`folded_packs` of this model, cached (:meth:`_cached`)."""
+        return self._cached("folded", list(self.parameters()) + list(self.buffers()), lambda: folded_packs(self))
+
+    def fused_supported(self, H, W):
+        """True when the fused inference chain takes (H, W) planes on this model: three one-channel branches of that size,
+        H and W multiples of 8, W <= 128 (``rml_sgan_trunk_supported``), the reference's 64 / 64 / n dense layers, n <= 16."""
+        from . import _lib
+        H, W = int(H), int(W)
+        return (len(self.branches) == 3 and all(tuple(sh) == (H, W, 1) for sh in self.shapes) and self.n_classes <= 16
+                and bool(_lib.load().rml_sgan_trunk_supported(H, W)))
+
+    def features_fused(self, xz, yz, xy):
+        """The flattened trunk output ``flatten_nhwc(cat(branches))`` in inference mode, (N, (H/8)(W/8)*96) bfloat16, from the fused
+        HIP trunk (csrc/sgan_infer.hip: BatchNorm folded into the weights, the layer-1 activation recomputed in registers, no
+        atomics -- a row depends on its own planes only).  Inputs (N, H, W) or (N, 1, H, W) CUDA tensors, float32 or bfloat16
+        (same results).  Raises ValueError for planes the trunk does not take (there is no fall-back)."""
+        import torch
+        from . import _lib
+        H, W = int(xz.shape[-2]), int(xz.shape[-1])
+        if not self.fused_supported(H, W):
+            raise ValueError("the fused SGAN trunk takes planes of the model's own size (%s) whose height and width are multiples of 8, "
+                             "width <= 128: got %dx%d planes" % ("x".join(str(v) for v in self.shapes[0][:2]), H, W))
+        if not xz.is_cuda:
+            raise RuntimeError("features_fused runs on the GPU (there is no CPU path)")
+        lib = _lib.load()
+        bf = all(x.dtype == torch.bfloat16 for x in (xz, yz, xy))
+        xs = [x.reshape(x.shape[0], x.shape[-2], x.shape[-1]) for x in (xz, yz, xy)]
+        xs = [(x if bf else x.float()).contiguous() for x in xs]
+        if any(tuple(x.shape) != tuple(xs[0].shape) for x in xs):
+            raise ValueError("features_fused: three plane sets of one shape expected")
+        n, dev = int(xs[0].shape[0]), xs[0].device
+        pk = self.folded_packs()
+        feat = torch.empty((n, (H // 8) * (W // 8) * 96), dtype=torch.bfloat16, device=dev)
+        if n == 0:
+            return feat
+        nbytes = int(lib.rml_sgan_trunk_workspace_bytes(n, H, W))
+        ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(lib.rml_sgan_trunk(_lib.context(dev), _lib.ptr(xs[0]), _lib.ptr(xs[1]), _lib.ptr(xs[2]), 1 if bf else 0, n, H, W,
+                                          _lib.ptr(pk["w1"]), _lib.ptr(pk["b1"]), _lib.ptr(pk["w2t"]), _lib.ptr(pk["b2"]),
+                                          _lib.ptr(pk["w3t"]), _lib.ptr(pk["b3"]), float(pk["slope"]), _lib.ptr(feat), _lib.ptr(ws), nbytes,
+                                          _lib.stream_ptr(dev)), "rml_sgan_trunk")
+        return feat
+
+    def dense_tail_fused(self, fv):
+        """Dense 64 + BatchNorm + LeakyReLU, twice, Dense n, softmax (inference: no dropout) on bf16 feature rows: csrc/dense.hip's
+        split-K first layer and finishing kernel with LeakyReLU (``rml_dense_tail_lrelu``); the BatchNorm1d layers are folded into
+        the dense kernels.  (N, n_classes) float32 probabilities."""
+        import torch
+        from . import _lib
+        lib = _lib.load()
+        pk = self.folded_packs()
+        n, K, dev = int(fv.shape[0]), int(fv.shape[1]), fv.device
+        if not (fv.is_cuda and fv.dtype == torch.bfloat16 and fv.ndim == 2 and fv.is_contiguous() and K % 64 == 0
+                and tuple(pk["fc1_w"].shape) == (64, K) and tuple(pk["fc2_wt"].shape) == (64, 64) and self.n_classes <= 16):
+            raise ValueError("dense_tail_fused: contiguous CUDA bfloat16 (N, %d) feature rows expected" % int(pk["fc1_w"].shape[1]))
+        out = torch.empty((n, self.n_classes), dtype=torch.float32, device=dev)
+        if n == 0:
+            return out
+        ctx = _lib.context(dev)
+        nbytes = int(lib.rml_dnn_dense_workspace_bytes(ctx, n, K))
+        ws = torch.empty((nbytes // 4,), dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(lib.rml_dense_tail_lrelu(ctx, _lib.ptr(fv), K, n, K, _lib.ptr(pk["fc1_w"]), _lib.ptr(pk["fc1_b"]), _lib.ptr(pk["fc2_wt"]),
+                                                _lib.ptr(pk["fc2_b"]), _lib.ptr(pk["fc3_w"]), _lib.ptr(pk["fc3_b"]), self.n_classes,
+                                                float(pk["slope"]), _lib.ptr(ws), nbytes, _lib.ptr(out), _lib.stream_ptr(dev)),
+                       "rml_dense_tail_lrelu")
+        return out
+
+    def forward_fused(self, xz, yz, xy):
+        """``softmax(c_model)`` in inference mode on the fused HIP chain: (N, n_classes) float32 class probabilities on the device
+        from float32 or bfloat16 planes (same results).  Raises for planes the trunk does not take."""
+        import torch
+        with torch.no_grad():
+            return self.dense_tail_fused(self.features_fused(xz, yz, xy))
+
+    def predict_volumes(self, volumes, rescale=RESCALE, mode="max", ijk=None, batch_size=8192, exact_resize=False, return_numpy=True):
+        """Radar volumes -> class probabilities on the GPU: (N, X, Y, Z) volumes (float32 or uint8; numpy or torch, host or device)
+        -> projections -> ``(p - 127.5) / 127.5`` and the bicubic resize of sgan.py:636-681 to ``rescale`` (Pillow's (width, height))
+        -> fused trunk -> LeakyReLU tail.  Grids the fused preprocessing kernel takes (``nn_common.preprocess_supported``: at 128x128 the
+        Walabot grid does, 64x64x128 does not) go from uint8 code rows to bf16 planes in one launch (Pillow's windows in float32: the planes are within one bf16 ulp
+        of the exact ones); other grids, mode "max_nan" and ``exact_resize=True`` take float32 rows and the Pillow-bit-identical
+        resize.  ``mode="slice"`` needs ``ijk`` (N, 3).  ``batch_size``: frames per pass; a row's result does not depend on it.
+        There is no margin guard: rows whose two largest probabilities are closer than the bf16 chain's error (a few 1e-3) can
+        take the other label than float32 Keras would give."""
+        import torch
+        from . import common, nn_common
+        if not isinstance(volumes, torch.Tensor):
+            volumes = torch.as_tensor(np.asarray(volumes))
+        n = int(volumes.shape[0])
+        dev = volumes.device if volumes.is_cuda else next(self.parameters()).device
+        if dev.type != "cuda":
+            raise RuntimeError("predict_volumes runs on the GPU: move the model to a CUDA device (there is no CPU path)")
+        oh, ow = int(rescale[1]), int(rescale[0])
+        if not self.fused_supported(oh, ow):
+            raise ValueError("predict_volumes: the fused SGAN trunk does not take %dx%d planes on this model" % (oh, ow))
+        if mode == "slice" and ijk is None:
+            raise ValueError("predict_volumes: mode='slice' needs ijk")
+        out = torch.empty((n, self.n_classes), dtype=torch.float32, device=dev)
+        dims = tuple(int(v) for v in volumes.shape[1:])
+        fused = not exact_resize and mode != "max_nan" and nn_common.preprocess_supported(dims, rescale)
+        bs = max(1, int(batch_size))
+        with torch.no_grad(), torch.cuda.device(dev):
+            for s0 in range(0, n, bs):
+                s1 = min(n, s0 + bs)
+                v = volumes[s0:s1] if volumes.is_cuda else volumes[s0:s1].to(dev)
+                if v.dtype != torch.uint8:
+                    v = v.float()
+                idx = None if ijk is None else ijk[s0:s1]
+                if fused:
+                    xs = nn_common.preprocess_volumes(v, rescale, mode=mode, ijk=idx)
+                else:
+                    feat = common.process_volumes(v, mode=mode, ijk=idx, scale=False)
+                    xs = nn_common.preprocess_features(feat, dims, rescale, out_dtype="bfloat16")
+                out[s0:s1] = self.forward_fused(*xs)
+        return out.cpu().numpy() if return_numpy else out
+
     # ---- Keras layout in / out -------------------------------------------------------------------------
     def _conv_bn_pairs(self):
         out = []
@@ -206,6 +336,44 @@ class Discriminator(_nn().Module):
             k, b = dense[2]
             put(self.fc3.weight, np.asarray(k).T, "dense_2 kernel"); put(self.fc3.bias, b, "dense_2 bias")
         return self
+
+
+def fold_batchnorm(model):
+    """The inference-mode model with every BatchNorm folded into the layer in front of it, float64 on the model's device:
+    ``s = gamma / sqrt(moving_variance + eps)``, ``w' = w * s`` (per output channel / unit), ``b' = beta + (bias - moving_mean) * s``.
+    Returns ``{"conv": [[(w (out, in, 3, 3), b)] x 3 per branch], "fc": [(w (out, in), b)] x 3, "slope": LeakyReLU slope}``; a layer is
+    then ``LeakyReLU(conv_same_stride2(x, w) + b)`` / ``LeakyReLU(x @ w.T + b)`` and the last one ``x @ w.T + b``."""
+    def fold(w, b, bn):
+        sc = bn.weight.detach().double() / (bn.running_var.detach().double() + float(bn.eps)).sqrt()
+        wf = w.detach().double() * sc.reshape((-1,) + (1,) * (w.ndim - 1))
+        return wf, bn.bias.detach().double() + (b.detach().double() - bn.running_mean.detach().double()) * sc
+    conv = [[fold(cv.weight, cv.bias, bn) for cv, bn in pairs] for pairs in model._conv_bn_pairs()]
+    fc = [fold(model.fc1.weight, model.fc1.bias, model.bn1), fold(model.fc2.weight, model.fc2.bias, model.bn2),
+          (model.fc3.weight.detach().double(), model.fc3.bias.detach().double())]
+    return {"conv": conv, "fc": fc, "slope": float(model.act.negative_slope)}
+
+
+def folded_packs(model):
+    """:func:`fold_batchnorm` in the layouts of ``rml_sgan_trunk`` and ``rml_dense_tail_lrelu``, computed in float64 and cast once, on
+    the model's device (CPU tensors for a CPU model): ``w1`` (3, 128, 9) and ``b1`` (3, 128) float32; ``w2t`` (3, 64, 1152) and ``w3t``
+    (3, 32, 576) bfloat16 with k = (ky * 3 + kx) * Cin + cin, ``b2`` (3, 64) and ``b3`` (3, 32) float32; ``fc1_w`` (64, K) bfloat16 in
+    Keras' row order, ``fc1_b``; ``fc2_wt`` (64 in, 64 out), ``fc2_b``, ``fc3_w`` (n, 64), ``fc3_b`` float32; ``slope``.  Three branches of
+    one-channel planes expected (the reference's model)."""
+    import torch
+    f = fold_batchnorm(model)
+    if len(f["conv"]) != 3 or any(len(br) != 3 or br[0][0].shape[1] != 1 for br in f["conv"]):
+        raise ValueError("folded_packs: three branches of three convolutions on one-channel planes expected")
+
+    def taps(w):            # (out, in, ky, kx) -> (out, ky, kx, in) -> (out, 9 * in)
+        return w.permute(0, 2, 3, 1).reshape(w.shape[0], -1)
+    st = lambda li, what, dt: torch.stack([(taps(br[li][0]) if what == "w" else br[li][1]) for br in f["conv"]]).to(dt).contiguous()
+    (w1, b1), (w2, b2), (w3, b3) = f["fc"]
+    return {"w1": st(0, "w", torch.float32), "b1": st(0, "b", torch.float32),
+            "w2t": st(1, "w", torch.bfloat16), "b2": st(1, "b", torch.float32),
+            "w3t": st(2, "w", torch.bfloat16), "b3": st(2, "b", torch.float32),
+            "fc1_w": w1.to(torch.bfloat16).contiguous(), "fc1_b": b1.float().contiguous(),
+            "fc2_wt": w2.float().t().contiguous(), "fc2_b": b2.float().contiguous(),
+            "fc3_w": w3.float().contiguous(), "fc3_b": b3.float().contiguous(), "slope": f["slope"]}
 
 
 def class_weight_to_sample_weight(y, class_weight):
@@ -484,11 +652,21 @@ class DiscriminatorTrainer:
             loss, _ = self._step(self.opt_d, lambda lg: d_loss(lg, yt, sw), x)
         return float(loss) if sync else loss
 
-    def predict(self, x, batch_size=4096):
-        """c_model.predict: softmax class probabilities, float32 numpy."""
+    def predict(self, x, batch_size=4096, fused=False):
+        """c_model.predict: softmax class probabilities, float32 numpy.  ``fused=True``: the planes go through
+        ``Discriminator.forward_fused`` (csrc/sgan_infer.hip, bf16 on the matrix cores with the BatchNorm layers folded in) instead
+        of the PyTorch layers under this trainer's autocast; planes that chain does not take raise."""
         import torch
         self.model.eval()
         outs = []
+        if fused:
+            H, W = (int(v) for v in self._inputs([x[0][:1]])[0].shape[-2:]) if len(x[0]) else self.model.shapes[0][:2]
+            if not self.model.fused_supported(H, W):
+                raise ValueError("predict(fused=True): the fused SGAN trunk does not take %dx%d planes on this model (height and "
+                                 "width multiples of 8, width <= 128, the model's own plane size)" % (H, W))
+            for s in range(0, len(x[0]), batch_size):
+                outs.append(self.model.forward_fused(*self._inputs([a[s:s + batch_size] for a in x])).cpu())
+            return torch.cat(outs).numpy() if outs else np.zeros((0, self.model.n_classes), np.float32)
         with torch.no_grad():
             for s in range(0, len(x[0]), batch_size):
                 xs = self._inputs([a[s:s + batch_size] for a in x])
@@ -501,10 +679,10 @@ class DiscriminatorTrainer:
         return torch.cat(outs).numpy()
 
 
-def _evaluate_c(trainer, x, y, batch_size=4096):
+def _evaluate_c(trainer, x, y, batch_size=4096, fused=False):
     """c_model.evaluate([xz, yz, xy], y) (sgan.py:491: ``_, acc = c_model.evaluate(...)``): (sparse categorical
-    cross-entropy, accuracy) over all samples, inference mode (BatchNorm moving statistics, no dropout)."""
-    p = trainer.predict(x, batch_size=batch_size).astype(np.float64)
+    cross-entropy, accuracy) over all samples, inference mode (BatchNorm moving statistics, no dropout).  ``fused``: as ``predict``."""
+    p = trainer.predict(x, batch_size=batch_size, fused=fused).astype(np.float64)
     yi = np.asarray(y).reshape(-1).astype(np.int64)
     if len(yi) != len(p):
         raise ValueError("evaluate: %d label(s) for %d sample(s)" % (len(yi), len(p)))
