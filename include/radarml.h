@@ -330,6 +330,26 @@ int rml_svm_pairwise_proba(rml_ctx* ctx, const rml_svm* m, const double* dec_ovo
 #define RML_AUG_NOISE  2
 int rml_augment(rml_ctx* ctx, int op, const float* src, int64_t B, int H, int W, const double* params, float* dst, void* stream);
 
+/* The augmentation chain of the network trainers (dnn.py:94-182 augment_data; sgan.py:238-326 is the same function) with the
+ * scaling of preprocess_data (dnn.py:202-205) in front, ONE launch for B equally shaped planes; per plane, in this order:
+ *   scaling           v = (p - sub) / div in float32 when div != 0 (sub = div = 127.5: [0, 255] -> [-1, 1]); div == 0: v = p
+ *   RML_CHAIN_ROTATE  scipy.ndimage.rotate(v, angle, reshape=False) (order 3, mode 'constant', cval 0, float64 prefilter), clamp
+ *   RML_CHAIN_ZOOM    clipped_zoom(v, factor) (centre paste below 1, centre crop + trim above 1, the input itself at 1), clamp
+ *   RML_CHAIN_NOISE   v += draw on EVERY entry (dnn.py:160; train.py's sparse noise of rml_augment is another function), clamp
+ * Each stage of the mask `stages` works on the previous one's result; the clamp is to [lo, hi] ([-1, 1] in the reference) and lets
+ * NaN pass; stages == 0 is the scaling alone.  Unlike rml_augment the planes between the stages never leave the workgroup.
+ * src: DEVICE, plane b at src + b * in_stride floats (in_stride >= H*W); dst: DEVICE B*H*W float32, dense; may not alias.
+ * params: DEVICE 8 doubles per plane: m00 m01 m10 m11 off0 off1 (the affine map of ndimage.rotate, see RML_AUG_ROTATE), the zoom
+ * factor, the noise draw -- all eight slots are there whatever `stages` is; NULL only with stages == 0.  A zoom factor outside
+ * [1/1024, 1024] (or NaN) has no region to resample and gives a zero plane.  The random draws are the caller's.
+ * RML_ERR_UNSUPPORTED: a plane whose float32 copy and float64 coefficient image (12 bytes per pixel, 4 without a spline stage)
+ * exceed the 150 KB of LDS that rml_augment allows, too.  B == 0 is a no-op.  Follow it with rml_resize_bicubic(div = 0). */
+#define RML_CHAIN_ROTATE 1
+#define RML_CHAIN_ZOOM   2
+#define RML_CHAIN_NOISE  4
+int rml_augment_chain(rml_ctx* ctx, int stages, const float* src, int64_t in_stride, int64_t B, int H, int W, float sub, float div,
+                      float lo, float hi, const double* params, float* dst, void* stream);
+
 /* Kernel values against the model's support vectors, K[n][m] = k(x_n, sv_m) for m < M, float64, exact to the
  * same arithmetic as rml_svm_decision (path AUTO / I8 / F64).  With the training rows loaded as the "support vectors"
  * of a model (any coefficients) this is the Gram matrix sklearn's SVC(kernel='precomputed') is fitted on and

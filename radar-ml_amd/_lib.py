@@ -147,6 +147,8 @@ SIGNATURES = {
     "rml_adam_step": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_float, c_float, c_float, c_float, c_void_p, c_void_p, c_void_p,
                               c_void_p, c_int, c_float, c_float, c_int, c_void_p]),
     "rml_augment": (c_int, [c_void_p, c_int, c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "rml_augment_chain": (c_int, [c_void_p, c_int, c_void_p, c_int64, c_int64, c_int, c_int, c_float, c_float, c_float, c_float, c_void_p,
+                                  c_void_p, c_void_p]),
     "rml_code_rmw_default": (c_int, [c_int64, c_int64, c_int, c_int]),
     "rml_probe_stream": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p]),
     "rml_synth_volumes": (c_int, [c_void_p, c_uint64, c_int64, c_int64, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
@@ -177,6 +179,7 @@ ENV_OPTIONS = {"RML_WAVE_SHARE": "project_share_cu", "RML_WAVEFRAME": "waveframe
                "RML_CHUNK": "chunk", "RML_C1_PK": "c1_pk", "RML_SMO_LDS_ROWS": "smo_lds_rows", "RML_SGD_RESIDENT_D": "sgd_resident_d",
                "RML_CONV7": "conv7"}
 AUG_ROTATE, AUG_ZOOM, AUG_NOISE = 0, 1, 2
+CHAIN_ROTATE, CHAIN_ZOOM, CHAIN_NOISE = 1, 2, 4
 VOL_F32, VOL_U8 = 0, 1
 MODES = {"max": MODE_MAX, "slice": MODE_SLICE, "sum": MODE_SUM, "max_nan": MODE_MAX_NAN}
 KERNEL_RBF, KERNEL_LINEAR = 0, 1

@@ -32,25 +32,6 @@ struct AugArgs {
 
 __device__ __forceinline__ float clamp01(float v) { return v > 1.0f ? 1.0f : (v < 0.0f ? 0.0f : v); }     // NaN passes, as in the reference
 
-// value of the spline with coefficients coef (h x w, row stride w) at (c0, c1); 0 outside [0,h-1] x [0,w-1]
-__device__ __forceinline__ float sample(const double* coef, int h, int w, double c0, double c1) {
-    if (!(c0 >= 0.0 && c0 <= (double)(h - 1) && c1 >= 0.0 && c1 <= (double)(w - 1))) return 0.0f;
-    const int f0 = (int)floor(c0), f1 = (int)floor(c1);
-    double w0[4], w1[4];
-    bspline3(c0 - f0, w0);
-    bspline3(c1 - f1, w1);
-    double s = 0.0;
-#pragma unroll
-    for (int p = 0; p < 4; ++p) {
-        const double* row = coef + (int64_t)mirror_idx(f0 - 1 + p, h) * w;
-        double t = 0.0;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) t += w1[q] * row[mirror_idx(f1 - 1 + q, w)];
-        s += w0[p] * t;
-    }
-    return (float)s;
-}
-
 __global__ __launch_bounds__(256) void k_augment(AugArgs a) {
     extern __shared__ __align__(16) double coef[];
     const int64_t b = blockIdx.x;

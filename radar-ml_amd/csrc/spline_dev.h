@@ -1,5 +1,6 @@
 // Device pieces of SciPy's order-3 B-spline resampling (scipy/ndimage/src/ni_splines.c, ni_interpolation.c), shared by
-// zoom.hip (ndimage.zoom inside common.process_samples) and augment.hip (ndimage.rotate / clipped zoom of train.DataGenerator).
+// zoom.hip (ndimage.zoom inside common.process_samples), augment.hip (ndimage.rotate / clipped zoom of train.DataGenerator) and
+// augment_chain.hip (the same two resamplings chained, dnn.py / sgan.py augment_data).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -38,6 +39,25 @@ __device__ __forceinline__ void bspline3(double t, double w[4]) {
     w[1] = (3.0 * t3 - 6.0 * t2 + 4.0) / 6.0;
     w[2] = (-3.0 * t3 + 3.0 * t2 + 3.0 * t + 1.0) / 6.0;
     w[3] = t3 / 6.0;
+}
+
+// value of the spline with coefficients coef (h x w, row stride w) at (c0, c1); 0 outside [0,h-1] x [0,w-1]
+__device__ __forceinline__ float sample(const double* coef, int h, int w, double c0, double c1) {
+    if (!(c0 >= 0.0 && c0 <= (double)(h - 1) && c1 >= 0.0 && c1 <= (double)(w - 1))) return 0.0f;
+    const int f0 = (int)floor(c0), f1 = (int)floor(c1);
+    double w0[4], w1[4];
+    bspline3(c0 - f0, w0);
+    bspline3(c1 - f1, w1);
+    double s = 0.0;
+#pragma unroll
+    for (int p = 0; p < 4; ++p) {
+        const double* row = coef + (int64_t)mirror_idx(f0 - 1 + p, h) * w;
+        double t = 0.0;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) t += w1[q] * row[mirror_idx(f1 - 1 + q, w)];
+        s += w0[p] * t;
+    }
+    return (float)s;
 }
 
 }  // namespace rml_spline

@@ -12,10 +12,16 @@ through PyTorch, which the north star allows for these layers.
 import numpy as np
 
 from . import dnn_guard
+from . import prep
 from .dnn_guard import LABEL_GUARD, LABEL_GUARD_X3, LABEL_GUARD_X6, LABEL_GUARD_F32      # noqa: F401  (the margin guard's levels)
 from .nn_common import make_same_conv, to_nchw, flatten_nhwc, tf_same_pad
 
 RESCALE = (80, 80)          # dnn.py:33
+rng = np.random.default_rng(prep.RANDOM_SEED)       # dnn.py:30: the noise draws and the shuffle of preprocess_data
+
+
+def _rng(given):
+    return given if given is not None else rng
 
 
 def rescore_route(n_rows, N, fused, host):
@@ -76,7 +82,8 @@ def _fit_upload(model, job, dev):
     params = list(model.parameters())
     if len(params) != 18 or any(p.dtype != torch.float32 or not p.is_cuda for p in params) or model.flat_features != (H // 4) * (W // 4) * 96:
         raise ValueError("fit: the three-branch float32 model of define_classifier on a CUDA device, built for these planes, expected")
-    up = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a)).to(device=dev, dtype=dt)        # noqa: E731
+    # a contiguous CUDA float32 tensor on the model's device (what preprocess_data(return_numpy=False) returns) stays as it is
+    up = lambda a, dt: (a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a))).to(device=dev, dtype=dt).contiguous()        # noqa: E731
     st = {"x": [up(a, torch.float32) for a in job.xs], "y": up(job.y, torch.int32), "N": int(N), "H": int(H), "W": int(W),
           "cw": up(job.class_weight, torch.float32), "acc": torch.zeros((4,), dtype=torch.float64, device=dev)}
     if job.val_xs is not None:
@@ -179,13 +186,23 @@ def _fit_epoch(model, job, perm):
 
 
 def _planes(a):
-    """(N, H, W) float32 numpy from what Keras feeds: (N, H, W) or (N, H, W, 1) arrays (or tensors)"""
-    a = a.detach().cpu().numpy() if hasattr(a, "detach") else np.asarray(a)
+    """(N, H, W) float32 from what Keras feeds: (N, H, W) or (N, H, W, 1) arrays (or tensors).  NumPy for host data; a CUDA tensor stays
+    on its device (contiguous float32 ones as they are), so a data set prepared there is not pulled back to be uploaded again."""
+    on_dev = hasattr(a, "detach") and a.is_cuda
+    a = a.detach() if on_dev else (a.detach().cpu().numpy() if hasattr(a, "detach") else np.asarray(a))
     if a.ndim == 4 and a.shape[-1] == 1:
         a = a[..., 0]
     if a.ndim != 3:
-        raise ValueError("expected (N,H,W) or (N,H,W,1), got %s" % (a.shape,))
+        raise ValueError("expected (N,H,W) or (N,H,W,1), got %s" % (tuple(a.shape),))
+    if on_dev:
+        import torch
+        return a.to(torch.float32).contiguous()
     return np.ascontiguousarray(a, dtype=np.float32)
+
+
+def _labels(y):
+    """(N,) host array of the labels (a tensor is read back: N integers)"""
+    return (y.detach().cpu().numpy() if hasattr(y, "detach") else np.asarray(y)).reshape(-1)
 
 
 def _class_weights(class_weight, n_classes):
@@ -205,11 +222,37 @@ def _class_weights(class_weight, n_classes):
     return w
 
 
+def augment_data(x, rotation_range=1.0, zoom_range=0.3, noise_sd=1.0, rng=None, device=None):
+    """``augment_data`` of dnn.py:94-182 on the GPU (one ``rml_augment_chain`` launch per projection): ``x`` = (xz, yz, xy) already in
+    [-1, 1]; rotate every projection by its own angle, zoom all by one factor, add one noise draw per projection, clamp to [-1, 1] after
+    each stage.  Same arguments and order of draws as the reference: one ``np.random.uniform`` per projection for the angles, one for
+    the zoom factor, one ``rng.normal(scale=noise_sd)`` per projection from this module's ``rng`` (``default_rng(1234)``) unless ``rng``
+    is given; a range that is None skips its stage and its draws.  Returns float32 planes (integer / float64 input is converted first):
+    NumPy arrays, or CUDA tensors where ``x`` held CUDA tensors."""
+    return prep.augment_data(x, rotation_range, zoom_range, noise_sd, _rng(rng), device)
+
+
+def preprocess_data(args, data, labels, *, rng=None, device=None, return_numpy=True):
+    """``preprocess_data`` of dnn.py:185-277 with the arrays on the GPU.  ``args``: anything with ``.augment`` and ``.train_split``;
+    ``data``: [(xz, yz, xy), ...] planes in [0, 255] (arenas may be mixed); ``labels``: one name per sample.  Returns
+    ``X_train, y_train, X_val, y_val, n_classes, w_classes`` as the reference does: (N, 80, 80, 3) float32 in [-1, 1], label-encoded
+    ``y``, ``w_classes = {cls: round(largest class / n, 2)}``.
+
+    All draws of the data set are made first, on the host, in the reference's order (see :func:`augment_data`); ``rng.shuffle`` of the
+    index follows the noise draws on the same generator (this module's ``rng`` unless one is given), so a seeded run gives the
+    reference's data set in the reference's order.  Then one ``rml_augment_chain`` and one ``rml_resize_bicubic`` launch per (projection,
+    plane shape); shuffle and split are one device gather.  Without ``augment`` the result is bit-identical to the reference's; with it
+    the spline stages are within 4e-6 each.  ``return_numpy=False`` leaves ``X_train`` / ``X_val`` as CUDA tensors,
+    which ``fit`` / ``train`` take without a host round trip.  Planes are handled in float32: integer / float64 data-set planes are
+    converted first (the reference would scale those in float64)."""
+    return prep.preprocess_dnn(args, data, labels, RESCALE, _rng(rng), device, return_numpy)
+
+
 def train(model, X, y, X_val, y_val, w_classes, results_dir, epochs=100, patience=10, logger=None):
     """dnn.py:347-390: fit with batches of 64, up to 100 epochs, class weights, EarlyStopping(patience=10) and
     ModelCheckpoint(save_best_only) on val_loss -- the best weights go to ``results_dir/c_model.pt`` (a ``state_dict``) -- and
-    the reference's log lines.  ``X``, ``X_val``: (N, H, W, 3) arrays, the projections xz, yz, xy on the last axis.  Returns the
-    history."""
+    the reference's log lines.  ``X``, ``X_val``: (N, H, W, 3) arrays or CUDA tensors (``preprocess_data(return_numpy=False)``), the
+    projections xz, yz, xy on the last axis.  Returns the history."""
     import logging
     import os
     log = logger or logging.getLogger(__name__)
@@ -879,7 +922,7 @@ class Classifier(_module_base()):
         if len(x) != 3:
             raise ValueError("expected the three inputs [xz, yz, xy]")
         xs = [_planes(a) for a in x]
-        y = np.asarray(y).reshape(-1)
+        y = _labels(y)
         if any(a.shape != xs[0].shape for a in xs) or len(y) != len(xs[0]) or len(y) == 0:
             raise ValueError("fit: three equal plane sets and one label per sample expected")
         if trusted and (y.min() < 0 or y.max() >= self.n_classes):
@@ -887,7 +930,7 @@ class Classifier(_module_base()):
         val_xs = val_y = None
         if validation_data is not None:
             val_xs = [_planes(a) for a in validation_data[0]]
-            val_y = np.asarray(validation_data[1]).reshape(-1)
+            val_y = _labels(validation_data[1])
             if len(val_xs) != 3 or any(a.shape[1:] != xs[0].shape[1:] or len(a) != len(val_y) for a in val_xs) or len(val_y) == 0:
                 raise ValueError("fit: validation_data = ([xz, yz, xy], y) with the training planes' shape expected")
             if val_y.min() < 0 or val_y.max() >= self.n_classes:
@@ -899,7 +942,7 @@ class Classifier(_module_base()):
     def train_on_batch(self, x, y, class_weight=None):
         """Keras ``model.train_on_batch([xz, yz, xy], y, class_weight=...)``: one update on these samples (at most 64); returns
         (loss, accuracy) of the batch in train mode, before the update."""
-        job = self._job(x, y, None, class_weight, len(np.asarray(y).reshape(-1)), trusted=False)
+        job = self._job(x, y, None, class_weight, len(_labels(y)), trusted=False)
         n = len(job.y)
         ls, co, _, _ = _fit_epoch(self, job, np.arange(n, dtype=np.int32))
         return ls / n, co / n

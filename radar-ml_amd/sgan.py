@@ -25,9 +25,11 @@ import pickle
 
 import numpy as np
 
+from . import prep
 from .nn_common import make_same_conv, to_nchw, flatten_nhwc
 
 RESCALE = (128, 128)        # sgan.py:39
+rng = np.random.default_rng(prep.RANDOM_SEED)       # sgan.py:36: the noise draws and the shuffles of preprocess_data / balance_classes
 # original (cols, rows) of the radar projections (sgan.py:43-45)
 XZ_SIZE = (176, 22)
 YZ_SIZE = (176, 31)
@@ -989,6 +991,34 @@ def save_model_npz(path, model):
     np.savez(path, **_flatten_weights(model.keras_weights()))
 
 
+def _rng(given):
+    return given if given is not None else rng
+
+
+def augment_data(x, rotation_range=1.0, zoom_range=0.3, noise_sd=1.0, rng=None, device=None):
+    """``augment_data`` of sgan.py:238-326, the function of dnn.py:94-182: see ``radar_ml_amd.dnn.augment_data``.  The noise comes from
+    this module's ``rng`` (``default_rng(1234)``) unless ``rng`` is given."""
+    return prep.augment_data(x, rotation_range, zoom_range, noise_sd, _rng(rng), device)
+
+
+def balance_classes(data, labels, samples_sup, shuffle=True, rng=None):
+    """``balance_classes`` of sgan.py:329-393: every class is upsampled to the size of the largest one -- per class, from the most common
+    down, the rows ``sklearn.utils.resample(..., replace=True, random_state=1234)`` picks on the host -- and the result is shuffled with
+    ``rng`` (this module's unless given).  ``data`` may be a CUDA tensor: the gather then runs on the device and the result stays there.
+    Classes that are balanced already: the three inputs themselves are returned and nothing is drawn."""
+    return prep.balance_classes(data, labels, samples_sup, shuffle, _rng(rng))
+
+
+def preprocess_data(args, data, labels, samples_sup, *, rng=None, device=None, return_numpy=True):
+    """``preprocess_data`` of sgan.py:617-727 with the arrays on the GPU: as ``radar_ml_amd.dnn.preprocess_data`` (same draws, same order,
+    same launches) with a resize to 128 x 128, the supervised mask ``samples_sup`` carried through shuffle and split, and
+    :func:`balance_classes` on the training part (its shuffle is the last use of ``rng``).  Returns ``train_set, val_set, n_classes,
+    w_classes`` with ``train_set = (X, y, sup)`` balanced and ``val_set = (X_val, y_val)``, or -- the reference's rule for an empty
+    validation set (``train_split`` 1.0) -- the training part as it was before balancing.  ``return_numpy=False`` leaves the ``X`` as CUDA
+    tensors, which :func:`train` takes as they are.  Planes are handled in float32: integer / float64 planes are converted first."""
+    return prep.preprocess_sgan(args, data, labels, samples_sup, RESCALE, _rng(rng), device, return_numpy)
+
+
 def select_supervised_samples(dataset, rng, n_samples=150, n_classes=3):
     """sgan.py:406-422: a class-balanced supervised subset (drawn with replacement from the samples flagged ``sup``)."""
     X, y, sup = dataset
@@ -1014,7 +1044,8 @@ def train(g_model, disc_trainer, gan, train_set, val_set, n_classes, w_classes=N
     import torch
     rng = np.random.default_rng(seed)
     dev = disc_trainer.device
-    X = torch.as_tensor(np.asarray(train_set[0]), dtype=torch.float32).to(dev)
+    # a CUDA tensor (preprocess_data(return_numpy=False)) stays on its device
+    X = (train_set[0] if isinstance(train_set[0], torch.Tensor) else torch.as_tensor(np.asarray(train_set[0]))).to(device=dev, dtype=torch.float32)
     planes = [X[..., i].unsqueeze(1).contiguous() for i in range(3)]          # three (N, 1, H, W), resident
     sup_ix, y_sup = select_supervised_samples(train_set, rng, n_classes=n_classes)
     bat_per_epo = int(X.shape[0] / n_batch)
@@ -1041,7 +1072,7 @@ def train(g_model, disc_trainer, gan, train_set, val_set, n_classes, w_classes=N
         logger.debug("Training results at step %d: c[%.3f,%.0f], d_r[%.3f], d_f[%.3f], g[%.3f]" % (i + 1, c_l, c_acc * 100, dr_l, df_l, g_l))
         history.append((c_l, c_acc, dr_l, df_l, g_l))
         if bat_per_epo and (i + 1) % bat_per_epo == 0:
-            Xv = np.asarray(val_set[0])
+            Xv = val_set[0] if isinstance(val_set[0], torch.Tensor) else np.asarray(val_set[0])
             _, acc = disc_trainer.evaluate([Xv[..., 0], Xv[..., 1], Xv[..., 2]], val_set[1])
             logger.info("Classifier accuracy at step %d: %.2f%%" % (i + 1, acc * 100))
             if results_dir is not None:
