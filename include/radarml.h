@@ -737,7 +737,8 @@ int rml_bn_lrelu_pad_backward(rml_ctx* ctx, const void* x, const void* dy, int d
 /* First layer of a branch, [3x3 stride-2 'same' convolution of a 1-channel image] + BatchNorm + LeakyReLU + pad with the
  * convolution folded in (the image needs no gradient): the convolution output is never stored; every pass recomputes
  * it (9 FMAs per element) from the zero-padded half-precision image N x (2H+1) x (2W+1) and the float32 weights
- * weight[tap][c].  forward: image -> y; backward: image, dy -> dweight[tap][c], dgamma, dbeta. */
+ * weight[tap][c].  forward: image -> y; backward: image, dy -> dweight[tap][c], dgamma, dbeta (rows of at most 340 pixels:
+ * RML_ERR_UNSUPPORTED beyond, except for the packed shapes C = 128, W = 16 / 32 / 64). */
 int rml_conv1_bn_lrelu_pad_forward(rml_ctx* ctx, const void* image, const float* weight, int dtype, int64_t N, int H, int W,
                                    int C, int pad_h, int pad_w, const float* gamma, const float* beta, float eps,
                                    float momentum, float slope, float* running_mean, float* running_var, float* save_mean,

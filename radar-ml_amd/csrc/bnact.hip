@@ -7,7 +7,10 @@
 // normalise + LeakyReLU written straight into the padded layout the next convolution reads) and the backward two
 // (per-channel sums of g and g*x_hat with g = dy * leaky'(z); then dx), all HBM-bound streaming over 16-byte
 // (8-channel) lanes.  Statistics are float32 partial sums per workgroup, combined in a fixed order in float64:
-// deterministic.  Algorithmic bytes per element (2-byte activations): forward 2 + 2 + 2, backward 2*(2 + 2) + 2.
+// deterministic.  The forward sums are taken around a per-channel pivot, the channel's value at pixel 0: sum (x - k) and
+// sum (x - k)^2 give mean = k + s/M and var = q/M - (s/M)^2 without the cancellation of E[x^2] - mean^2 (relative error of rstd
+// <= (L + 2) 2^-24 (1 + (k - mean)^2 / (var + eps)) for summation chains of length L).  Algorithmic bytes per element (2-byte
+// activations): forward 2 + 2 + 2, backward 2*(2 + 2) + 2.
 //
 // Semantics = torch.nn.BatchNorm2d(training) (biased variance for the normalisation, unbiased for the running
 // estimate, momentum m: running = (1-m)*running + m*batch) followed by LeakyReLU(slope) and F.pad(0, pw, 0, ph).
@@ -66,7 +69,11 @@ __device__ __forceinline__ void block_channel_sums(const float (&a)[8], const fl
     (void)cg; (void)pl;
 }
 
-// ---- forward pass 1: per-channel sum and sum of squares ---------------------------------------------------------
+// ---- forward pass 1: per-channel sums of (x - k) and (x - k)^2 around the pivot k[c] = x[pixel 0][c] ---------------------------
+// Float32 sums of x and x^2 lose the variance where |mean| >> std (var = E[x^2] - mean^2 cancels: fp16 activations with mean 8 and
+// std 0.05 gave rstd 0.2 % off).  Around a value of the channel itself the two sums are of the size of the spread: the same pass,
+// one subtraction per element.  The pivot is a single pixel: where pixel 0 is an outlier of its channel, d = |k - mean| >> std, the
+// error of rstd grows with d^2 / (var + eps) -- for a channel with mean near 0 that is worse than the plain sums were.
 template <bool BF>
 __global__ __launch_bounds__(kT) void k_bn_stats(const uint16_t* __restrict__ x, int64_t M, int C, float* part) {
     __shared__ float lds[kT * 16];
@@ -76,21 +83,24 @@ __global__ __launch_bounds__(kT) void k_bn_stats(const uint16_t* __restrict__ x,
 #pragma unroll
     for (int i = 0; i < 8; ++i) { s[i] = 0.0f; q[i] = 0.0f; }
     if (pl < PL) {
+        float k[8];
+        unpack8<BF>(*reinterpret_cast<const uint4*>(x + cg * 8), k);
         for (int64_t p = (int64_t)blockIdx.x * PL + pl; p < M; p += (int64_t)gridDim.x * PL) {
             float v[8];
             unpack8<BF>(*reinterpret_cast<const uint4*>(x + p * C + cg * 8), v);
 #pragma unroll
-            for (int i = 0; i < 8; ++i) { s[i] += v[i]; q[i] = fmaf(v[i], v[i], q[i]); }
+            for (int i = 0; i < 8; ++i) { const float d = v[i] - k[i]; s[i] += d; q[i] = fmaf(d, d, q[i]); }
         }
     }
     block_channel_sums(s, q, CG, C, part, lds);
 }
 
 // ---- combine the workgroup partials in a fixed order (float64) -----------------------------------------------------
-// mode 0 (forward): a = sum x, b = sum x^2 -> mean, rstd, running statistics.  mode 1 (backward): a = sum g,
-// b = sum g*x_hat -> dbeta, dgamma, c1 = a/M, c2 = b/M.
+// mode 0 (forward): a = sum (x - k), b = sum (x - k)^2 with the pivot k = x[pixel 0][c] (pivot: the activations, bf: their type)
+// -> mean = k + a/M, var = b/M - (a/M)^2, rstd, running statistics.  mode 1 (backward): a = sum g, b = sum g*x_hat -> dbeta,
+// dgamma, c1 = a/M, c2 = b/M.
 __global__ __launch_bounds__(kT) void k_bn_finalize(const float* part, int G, int C, double M, int mode, float eps, float momentum,
-                                                    float* o0, float* o1, float* o2, float* o3) {
+                                                    float* o0, float* o1, float* o2, float* o3, const uint16_t* pivot, int bf) {
     // one workgroup per channel: strided float64 partial sums, then a fixed-shape tree
     __shared__ double sa[kT], sb[kT];
     const int c = blockIdx.x, t = threadIdx.x;
@@ -105,8 +115,9 @@ __global__ __launch_bounds__(kT) void k_bn_finalize(const float* part, int G, in
     if (t != 0) return;
     a = sa[0]; b = sb[0];
     if (mode == 0) {
-        const double mean = a / M;
-        double var = b / M - mean * mean;
+        const double k = bf ? (double)h2f<true>(pivot[c]) : (double)h2f<false>(pivot[c]);
+        const double sm = a / M, mean = k + sm;
+        double var = b / M - sm * sm;
         var = var > 0.0 ? var : 0.0;
         o0[c] = (float)mean;
         o1[c] = (float)(1.0 / sqrt(var + (double)eps));
@@ -790,7 +801,7 @@ extern "C" int rml_bn_lrelu_pad_forward(rml_ctx* ctx, const void* x, int dtype, 
     if (dtype) hipLaunchKernelGGL(k_bn_stats<true>, dim3(G), dim3(kT), 0, st, xs, M, C, workspace);
     else hipLaunchKernelGGL(k_bn_stats<false>, dim3(G), dim3(kT), 0, st, xs, M, C, workspace);
     hipLaunchKernelGGL(k_bn_finalize, dim3(C), dim3(kT), 0, st, workspace, G, C, (double)M, 0, eps, momentum,
-                       save_mean, save_rstd, running_mean, running_var);
+                       save_mean, save_rstd, running_mean, running_var, xs, dtype);
     const unsigned rows = (unsigned)(N * (H + pad_h));
     if (dtype) hipLaunchKernelGGL(k_bn_apply_pad<true>, dim3(rows), dim3(kT), 0, st, xs, ys, H, W, C, pad_h, pad_w, save_mean, save_rstd, gamma, beta, slope);
     else hipLaunchKernelGGL(k_bn_apply_pad<false>, dim3(rows), dim3(kT), 0, st, xs, ys, H, W, C, pad_h, pad_w, save_mean, save_rstd, gamma, beta, slope);
@@ -820,7 +831,8 @@ extern "C" int rml_bn_lrelu_pad_backward(rml_ctx* ctx, const void* x, const void
     float* c2 = c1 + C;
     if (dtype) hipLaunchKernelGGL(k_bn_bwd_reduce<true>, dim3(G), dim3(kT), 0, st, xs, ds, N, H, W, C, pad_h, pad_w, save_mean, save_rstd, gamma, beta, slope, workspace);
     else hipLaunchKernelGGL(k_bn_bwd_reduce<false>, dim3(G), dim3(kT), 0, st, xs, ds, N, H, W, C, pad_h, pad_w, save_mean, save_rstd, gamma, beta, slope, workspace);
-    hipLaunchKernelGGL(k_bn_finalize, dim3(C), dim3(kT), 0, st, workspace, G, C, (double)M, 1, 0.0f, 0.0f, dbeta, dgamma, c1, c2);
+    hipLaunchKernelGGL(k_bn_finalize, dim3(C), dim3(kT), 0, st, workspace, G, C, (double)M, 1, 0.0f, 0.0f, dbeta, dgamma, c1, c2,
+                       static_cast<const uint16_t*>(nullptr), 0);
     const unsigned rows = (unsigned)(N * H);
     if (dtype) hipLaunchKernelGGL(k_bn_bwd_apply<true>, dim3(rows), dim3(kT), 0, st, xs, ds, os, H, W, C, pad_h, pad_w, save_mean, save_rstd, gamma, beta, c1, c2, slope);
     else hipLaunchKernelGGL(k_bn_bwd_apply<false>, dim3(rows), dim3(kT), 0, st, xs, ds, os, H, W, C, pad_h, pad_w, save_mean, save_rstd, gamma, beta, c1, c2, slope);
@@ -897,6 +909,9 @@ extern "C" int rml_conv1_bn_lrelu_pad_backward(rml_ctx* ctx, const void* image, 
     // C = 128 and rows of 16 / 32 / 64 pixels: the packed kernel (RML_OPT_C1_PK = 0: the general one)
     const bool pk_on = ctx->opt.c1_pk != 0;
     const bool pk = pk_on && C == 128 && (W == 16 || W == 32 || W == 64);
+    // k_c1_bwd1 stages the three image rows of an output row, 3 * (2 W + 1) floats, in its kT * 8 floats of LDS
+    RML_REQUIRE(pk || 3 * (2 * (int64_t)W + 1) <= kT * 8, RML_ERR_UNSUPPORTED,
+                "rml_conv1_bn_lrelu_pad_backward: rows of %d pixels (at most %d)", W, (kT * 8 / 3 - 1) / 2);
     if (pk) {
         // one round of resident workgroups (166 registers at W = 64: three per CU), rows strided over them
         auto go = [&](auto bf, auto nb) {
