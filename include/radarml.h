@@ -123,7 +123,10 @@ int rml_ctx_device(const rml_ctx* ctx);
  *     the weights on the workspace.  0: every problem on the workspace.  The results are the same bits either way.
  *   RML_OPT_CONV7 (default RML_CONV7_DEFAULT; bit 0: forward, bit 1: backward): which passes of the generator's output layer the callers
  *     of rml_conv7_tanh_* (nn_common.conv7_tanh) run on the hand-written kernels; a cleared bit sends that pass to the convolution library.
- *     The entry points themselves always run the kernels: the option is the caller's switch, kept here so that A/B runs share one knob. */
+ *     The entry points themselves always run the kernels: the option is the caller's switch, kept here so that A/B runs share one knob.
+ *   RML_OPT_ZOOM_ROWS (default 0): how the workgroups of k_zoom_rows (rml_project_zoom, rml_project_zoom_svm) share a row.  0: one
+ *     workgroup per (row, plane) -- the measured choice; 1: one workgroup per row, the float64 images of its planes together in LDS
+ *     (where they fit 150 KB); 2: one workgroup per row, one plane after the other.  The rows are the same bits in every mode. */
 #define RML_OPT_PROJECT_SHARE_CU 1
 #define RML_OPT_WAVEFRAME 2
 #define RML_OPT_LINPLANE 3
@@ -140,6 +143,7 @@ int rml_ctx_device(const rml_ctx* ctx);
 #define RML_SGD_RESIDENT_D_MAX 10240
 #define RML_OPT_CONV7 13
 #define RML_CONV7_DEFAULT 3
+#define RML_OPT_ZOOM_ROWS 14
 int rml_ctx_set_option(rml_ctx* ctx, int option, int value);
 int rml_ctx_get_option(const rml_ctx* ctx, int option, int* value);
 
@@ -261,6 +265,19 @@ int rml_assemble_features(rml_ctx* ctx, const float* xz, const float* yz, const 
 int rml_zoom_features(rml_ctx* ctx, const float* xz, const float* yz, const float* xy,
                       int64_t B, int X, int Y, int Z, const int32_t* out_shape,
                       float scale_div, uint32_t mask, float* feat, int64_t ld_feat, void* stream);
+
+/* Volumes from a radar arena that differs from the training arena -> feature rows at the MODEL's geometry, on the device:
+ * the body of predict.py:98-116 for B frames at once -- the projections (predict.py:102-107, or mode MAX), calc_proj_zoom's
+ * factors (predict.py:34-54,109-111) applied by common.process_samples (common.py:141-148: scipy.ndimage.zoom per plane, ravel,
+ * concatenate, optional "/ RADAR_MAX").  The projection runs at the source grid X x Y x Z into a chunk of the context's
+ * workspace (float32 rows; uint8 volumes: code rows, a quarter of the bytes), k_zoom_rows resamples every row to out_shape
+ * (HOST, 6 ints as in rml_zoom_features) -- the arithmetic of rml_zoom_features, bit for bit.  No host synchronisation.
+ *   mode   as rml_project; RML_MODE_SLICE with ijk NULL derives the T strongest targets of every frame at the source grid
+ *   ijk    B*T*3 int32 (frame-major) or NULL;  T targets per frame (1 unless mode is RML_MODE_SLICE)
+ *   feat   B*T rows of D = sum of the selected output planes, stride ld_feat >= D
+ * RML_ERR_UNSUPPORTED: a selected plane whose float64 image exceeds 150 KB (the LDS-resident spline filter), as rml_zoom_features. */
+int rml_project_zoom(rml_ctx* ctx, const void* V, int vdtype, int64_t B, int X, int Y, int Z, int mode, const int32_t* ijk, int T,
+                     const int32_t* out_shape, float scale_div, uint32_t mask, float* feat, int64_t ld_feat, void* stream);
 
 /* Quantise float32 feature rows to uint8 codes + row stats, for callers that bring (N,D)
  * features instead of volumes.  A value v is on the code grid iff it is bit-identical to
@@ -526,6 +543,17 @@ int rml_derive_project_svm(rml_ctx* ctx, const rml_svm* m, const void* V, int vd
                            float scale_div, uint32_t mask, int32_t* ijk_out,
                            double* dec_ovo, double* dec_ovr, double* proba,
                            int32_t* label_vote, int32_t* label_calib, void* stream);
+
+/* The front door for a recording from a foreign arena (predict.py:98-119 with calc_proj_zoom != 1, predict.py:34-54): projection
+ * at the source grid X x Y x Z, the zoom of rml_project_zoom to out_shape (the selected output planes must sum to the model's D:
+ * RML_ERR_INVALID otherwise), the SVM of rml_svm_decision on the zoomed rows -- off the code grid: the float64 kernel, or the
+ * multi-digit int8 kernel for batches that fill it, as RML_PATH_AUTO picks for float rows.  One target per frame; mode
+ * RML_MODE_SLICE with ijk NULL derives it at the source grid.  Chunked like rml_project_svm (the GEMM of a chunk beside the
+ * projection and zoom of the next); at most 128 frames run on the caller's stream alone. */
+int rml_project_zoom_svm(rml_ctx* ctx, const rml_svm* m, const void* V, int vdtype, int64_t B, int X, int Y, int Z,
+                         int mode, const int32_t* ijk, const int32_t* out_shape, float scale_div, uint32_t mask,
+                         double* dec_ovo, double* dec_ovr, double* proba,
+                         int32_t* label_vote, int32_t* label_calib, void* stream);
 
 /* ---- linear classifier (SGDClassifier(loss='log'), train.py:350-381; predict 421,433) --- */
 int rml_linear_load(rml_ctx* ctx, const double* coef /* host (C,D) */, const double* intercept /* host C */,

@@ -10,7 +10,7 @@ from . import _lib
 from ._lib import RadarMLError
 from .common import (ProjMask, ProjZoom, DerivedTarget, RADAR_MAX, RADAR_MIN,
                      cartesian_to_spherical, spherical_to_cartesian, calculate_matrix_indices,
-                     process_samples, process_volumes, project, derive_targets, feature_len)
+                     process_samples, process_volumes, project, derive_targets, feature_len, zoom_out_shapes)
 from .svm import GpuSVC, GpuCalibratedClassifier, GpuLinearClassifier, KernelMatrix, from_sklearn
 from .predict import classifier, classify_batch, calc_proj_zoom
 from .synth import synth_volumes
@@ -21,7 +21,7 @@ from .train import (GridSearchSVC, find_best_svm_estimator, fit_svc, GridSearchS
 __all__ = [
     "RadarMLError", "ProjMask", "ProjZoom", "DerivedTarget", "RADAR_MAX", "RADAR_MIN",
     "cartesian_to_spherical", "spherical_to_cartesian", "calculate_matrix_indices",
-    "process_samples", "process_volumes", "project", "derive_targets", "feature_len",
+    "process_samples", "process_volumes", "project", "derive_targets", "feature_len", "zoom_out_shapes",
     "GpuSVC", "GpuCalibratedClassifier", "GpuLinearClassifier", "KernelMatrix", "from_sklearn",
     "classifier", "classify_batch", "calc_proj_zoom", "synth_volumes",
     "DataGenerator", "augment_planes", "rotation_params", "GridSearchSVC", "find_best_svm_estimator", "fit_svc",

@@ -53,6 +53,10 @@ SIGNATURES = {
                                       c_uint32, c_void_p, c_int64, c_void_p]),
     "rml_zoom_features": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_float,
                                   c_uint32, c_void_p, c_int64, c_void_p]),
+    "rml_project_zoom": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_float,
+                                 c_uint32, c_void_p, c_int64, c_void_p]),
+    "rml_project_zoom_svm": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_float,
+                                     c_uint32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "rml_quantize_rows": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_float, c_void_p, c_int64,
                                   c_void_p, c_void_p, c_void_p, c_void_p]),
     "rml_svm_load": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int, c_int,
@@ -157,7 +161,7 @@ SIGNATURES = {
 
 MODE_MAX, MODE_SLICE, MODE_SUM, MODE_MAX_NAN = 0, 1, 2, 3
 # rml_ctx_set_option ids (include/radarml.h RML_OPT_*)
-OPT_PROJECT_SHARE_CU, OPT_WAVEFRAME, OPT_LINPLANE, OPT_STAGE_CODES, OPT_SLICE_WAVE, OPT_DERIVE_FUSED, OPT_CODE_RMW, OPT_GEMM_BIG, OPT_CHUNK, OPT_C1_PK, OPT_SMO_LDS_ROWS, OPT_SGD_RESIDENT_D, OPT_CONV7 = range(1, 14)
+OPT_PROJECT_SHARE_CU, OPT_WAVEFRAME, OPT_LINPLANE, OPT_STAGE_CODES, OPT_SLICE_WAVE, OPT_DERIVE_FUSED, OPT_CODE_RMW, OPT_GEMM_BIG, OPT_CHUNK, OPT_C1_PK, OPT_SMO_LDS_ROWS, OPT_SGD_RESIDENT_D, OPT_CONV7, OPT_ZOOM_ROWS = range(1, 15)
 OPTIONS = {"project_share_cu": OPT_PROJECT_SHARE_CU, "waveframe": OPT_WAVEFRAME, "linplane": OPT_LINPLANE, "stage_codes": OPT_STAGE_CODES,
            "slice_wave": OPT_SLICE_WAVE, "derive_fused": OPT_DERIVE_FUSED, "code_rmw": OPT_CODE_RMW, "gemm_big": OPT_GEMM_BIG,
            "chunk": OPT_CHUNK, "c1_pk": OPT_C1_PK}
@@ -166,6 +170,8 @@ OPTIONS = {"project_share_cu": OPT_PROJECT_SHARE_CU, "waveframe": OPT_WAVEFRAME,
 SOLVER_OPTIONS = {"smo_lds_rows": OPT_SMO_LDS_ROWS, "sgd_resident_d": OPT_SGD_RESIDENT_D}
 # which passes of the generator's output layer run on csrc/gen.hip (bit 0 forward, bit 1 backward; nn_common.conv7_tanh reads it)
 NN_OPTIONS = {"conv7": OPT_CONV7}
+# how k_zoom_rows holds a row (0 by the LDS rule, 1 the planes together, 2 plane by plane): an A/B knob of tools/foreign_arena_bench.py
+ZOOM_OPTIONS = {"zoom_rows": OPT_ZOOM_ROWS}
 SMO_LDS_ROWS_MAX = 2768
 SGD_RESIDENT_D_MAX = 10240
 SGD_MAX_ROWS = 8192
@@ -191,7 +197,7 @@ PATHS = {"auto": PATH_AUTO, "f32": PATH_F32, "i8": PATH_I8, "f64": PATH_F64, "di
 def option_id(name):
     """RML_OPT_* id of an option name (a key of OPTIONS, SOLVER_OPTIONS or NN_OPTIONS; the header's upper-case spelling is taken too)."""
     name = name.lower()
-    for table in (OPTIONS, SOLVER_OPTIONS):
+    for table in (OPTIONS, SOLVER_OPTIONS, ZOOM_OPTIONS):
         if name in table:
             return table[name]
     return NN_OPTIONS[name]

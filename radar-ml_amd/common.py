@@ -195,8 +195,71 @@ def project(volumes, mode="max", ijk=None, return_numpy=None):
     return out
 
 
+def is_unit_zoom(proj_zoom, proj_mask=ProjMask(xz=True, yz=True, xy=True)):
+    """True when ``proj_zoom`` is None or 1.0 (within 1e-12) on every selected plane: ``process_samples`` and the volume entry
+    points then take the identity path (what calc_proj_zoom gives when the predict arena is the training arena)."""
+    if proj_zoom is None:
+        return True
+    return all((not proj_mask[i]) or all(abs(float(z) - 1.0) <= 1e-12 for z in np.ravel(proj_zoom[i])) for i in range(3))
+
+
+def zoom_out_shapes(size_x, size_y, size_z, proj_zoom):
+    """Shapes of the zoomed projections ((rows, cols) of xz, yz, xy) exactly as scipy.ndimage.zoom computes them:
+    ``int(round(size * zoom))`` with Python's round() (half to even) -- common.py:141-148 on planes of an (X,Y,Z) arena.
+    A plane's zoom is a pair of factors (predict.py:51-54) or one factor for both axes."""
+    expect = [(size_x, size_z), (size_y, size_z), (size_x, size_y)]
+    shapes = []
+    for i in range(3):
+        zf = list(np.ravel(proj_zoom[i]).astype(float)) if np.ndim(proj_zoom[i]) else [float(proj_zoom[i])] * 2
+        shapes.append((int(round(expect[i][0] * zf[0])), int(round(expect[i][1] * zf[1]))))
+    return tuple(shapes)
+
+
+def _zoomed_len(shapes, proj_mask):
+    return sum(shapes[i][0] * shapes[i][1] for i in range(3) if proj_mask[i])
+
+
+def _shape_array(shapes):
+    import ctypes as C
+    return (C.c_int32 * 6)(*[v for s in shapes for v in s])
+
+
+def _process_volumes_zoom(v, vdt, m, ijk, proj_mask, proj_zoom, scale, out, num_targets, return_ijk):
+    """process_volumes for a foreign arena: the rows of the volumes' own grid never leave the library (rml_project_zoom)."""
+    import ctypes as C
+    torch = _torch()
+    lib = _lib.load()
+    B, X, Y, Z = v.shape
+    dev = v.device
+    shapes = zoom_out_shapes(X, Y, Z, proj_zoom)
+    D = _zoomed_len(shapes, proj_mask)
+    ijk_t, T = None, 1
+    if m == _lib.MODE_SLICE:
+        derived = ijk is None
+        if derived:
+            # no SDK targets: the strongest return(s) of every frame (common.py:49-80), derived inside the call at the volumes' own
+            # grid -- or here, when the caller wants the indices back
+            T = int(num_targets)
+            if return_ijk:
+                ijk = derive_targets(v, T)
+        if ijk is not None:
+            ijk_t, T = _slice_indices(ijk, B, X, Y, Z, dev, validate=not derived)
+    R = B * T
+    feat = out if out is not None else torch.empty((R, D), dtype=torch.float32, device=dev)
+    if feat.shape[0] != R or feat.shape[1] < D or feat.device != dev:
+        raise ValueError("out must be a (%d, >=%d) float32 tensor on %s" % (R, D, dev))
+    arr = _shape_array(shapes)
+    with torch.cuda.device(dev):
+        _lib.check(lib.rml_project_zoom(_lib.context(dev), _lib.ptr(v), vdt, B, X, Y, Z, m, _lib.ptr(ijk_t), T, C.cast(arr, C.c_void_p),
+                                        float(RADAR_MAX) if scale else 0.0, _mask_bits(proj_mask), _lib.ptr(feat), feat.stride(0),
+                                        _lib.stream_ptr(dev)), "rml_project_zoom")
+    if return_ijk:
+        return feat, (ijk_t.reshape(B, T, 3) if ijk_t is not None else None)
+    return feat
+
+
 def process_volumes(volumes, mode="max", ijk=None, proj_mask=ProjMask(xz=True, yz=True, xy=True), scale=False,
-                    out=None, codes=False, num_targets=1, device=None, return_ijk=False):
+                    out=None, codes=False, num_targets=1, device=None, return_ijk=False, proj_zoom=None):
     """Fused batched front door: (B,X,Y,Z) volumes -> (B,D) float32 feature rows in one pass over
     the volumes (projection + ``process_samples`` at zoom 1).  Returns a CUDA tensor; with
     ``codes=True`` returns ``(feat, codes_u8, row_isum, row_isq, row_flags)`` for the exact SVM path; ``codes='only'`` writes no float
@@ -206,12 +269,21 @@ def process_volumes(volumes, mode="max", ijk=None, proj_mask=ProjMask(xz=True, y
     image (predict.py:93-119) -- (B,T,3): the result then has B*T rows, frame-major (row b*T+t), and no volume is
     duplicated.  Without ``ijk`` the ``num_targets`` strongest derived targets of every frame are used (common.py:49-80);
     ``return_ijk=True`` appends the (B,T,3) int32 indices the rows were sliced at to the result.
+
+    ``proj_zoom`` (a ProjZoom, as ``process_samples`` takes it): volumes from an arena that differs from the training arena
+    (predict.py:109-116) -- the projections are taken at the volumes' own grid and spline-zoomed on the device to
+    ``zoom_out_shapes``; the rows have the zoomed length.  None or a unit zoom: the call above, unchanged.  No code rows with a
+    zoom (zoomed rows are off the code grid).
     """
     torch = _torch()
     lib = _lib.load()
     v, vdt = _as_device_volumes(volumes, device)
     if v.ndim == 3:
         v = v.unsqueeze(0)
+    if not is_unit_zoom(proj_zoom, proj_mask):
+        if codes:
+            raise ValueError("proj_zoom gives rows off the code grid: no code rows")
+        return _process_volumes_zoom(v, vdt, _lib.MODES[mode], ijk, proj_mask, proj_zoom, scale, out, num_targets, return_ijk)
     B, X, Y, Z = v.shape
     dev = v.device
     ctx = _lib.context(dev)
@@ -292,7 +364,7 @@ def process_samples(samples, proj_mask=ProjMask(xz=True, yz=True, xy=True),
     """
     torch = _torch()
     lib = _lib.load()
-    unit = all((not proj_mask[i]) or all(abs(float(z) - 1.0) <= 1e-12 for z in np.ravel(proj_zoom[i])) for i in range(3))
+    unit = is_unit_zoom(proj_zoom, proj_mask)
     samples = list(samples)
     n = len(samples)
     if n == 0:
@@ -343,13 +415,10 @@ def process_samples(samples, proj_mask=ProjMask(xz=True, yz=True, xy=True),
     if not unit:
         import ctypes as C
         # output shapes exactly as scipy.ndimage.zoom computes them: int(round(size * zoom)), Python round()
-        oshape = []
-        for i in range(3):
-            zf = list(np.ravel(proj_zoom[i]).astype(float)) if np.ndim(proj_zoom[i]) else [float(proj_zoom[i])] * 2
-            oshape += [int(round(expect[i][0] * zf[0])), int(round(expect[i][1] * zf[1]))]
-        D = sum(oshape[2 * i] * oshape[2 * i + 1] for i in range(3) if proj_mask[i])
+        zshapes = zoom_out_shapes(X, Y, Z, proj_zoom)
+        D = _zoomed_len(zshapes, proj_mask)
         feat = torch.empty((n, D), dtype=torch.float32, device=dev)
-        arr = (C.c_int32 * 6)(*oshape)
+        arr = _shape_array(zshapes)
         with torch.cuda.device(dev):
             _lib.check(lib.rml_zoom_features(ctx, _lib.ptr(dplanes[0]), _lib.ptr(dplanes[1]), _lib.ptr(dplanes[2]), n, X, Y, Z,
                                              C.cast(arr, C.c_void_p), float(RADAR_MAX) if scale else 0.0, bits,

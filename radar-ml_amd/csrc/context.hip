@@ -319,6 +319,11 @@ extern "C" int rml_ctx_set_option(rml_ctx* ctx, int option, int value) {
         ctx->opt.conv7 = value;
         return RML_OK;
     }
+    if (option == RML_OPT_ZOOM_ROWS) {
+        RML_REQUIRE(value >= 0 && value <= 2, RML_ERR_INVALID, "rml_ctx_set_option: RML_OPT_ZOOM_ROWS is 0 (by LDS size), 1 (whole row) or 2 (plane by plane)");
+        ctx->opt.zoom_rows = value;
+        return RML_OK;
+    }
     if (option == RML_OPT_CHUNK) {
         RML_REQUIRE(value == 0 || value >= 128, RML_ERR_INVALID, "rml_ctx_set_option: RML_OPT_CHUNK is 0 (automatic) or >= 128 rows");
         ctx->opt.chunk = value;
@@ -342,6 +347,7 @@ extern "C" int rml_ctx_get_option(const rml_ctx* ctx, int option, int* value) {
     if (option == RML_OPT_SMO_LDS_ROWS) { *value = c->opt.smo_lds_rows; return RML_OK; }
     if (option == RML_OPT_SGD_RESIDENT_D) { *value = c->opt.sgd_resident_d; return RML_OK; }
     if (option == RML_OPT_CONV7) { *value = c->opt.conv7; return RML_OK; }
+    if (option == RML_OPT_ZOOM_ROWS) { *value = c->opt.zoom_rows; return RML_OK; }
     const int* slot = opt_slot(c->opt, option);
     RML_REQUIRE(slot != nullptr, RML_ERR_INVALID, "rml_ctx_get_option: unknown option %d", option);
     *value = *slot;

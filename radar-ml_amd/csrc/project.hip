@@ -904,6 +904,15 @@ static void rows_out(ProjOut& o, int X, int Y, int Z, uint32_t mask, float scale
 
 static int derive_two_kernels(rml_ctx* ctx, const void* V, int vdtype, int64_t B, int X, int Y, int Z, int num_targets, int32_t* ijk,
                               float* profiles, hipStream_t st);
+static int derive_two_kernels_at(rml_ctx* ctx, const void* V, int vdtype, int64_t B, int X, int Y, int Z, int num_targets, int32_t* ijk,
+                                 float* profiles, float* xzs, hipStream_t st);
+
+int rml_launch_derive(rml_ctx* ctx, const void* V, int vdtype, int64_t B, int X, int Y, int Z, int num_targets, int32_t* ijk,
+                      float* sums, hipStream_t st) {
+    ProjOut none{};
+    const int rc = rml_launch_derive_slice(ctx, V, vdtype, B, X, Y, Z, num_targets, ijk, nullptr, none, st);
+    return rc != RML_ERR_UNSUPPORTED ? rc : derive_two_kernels_at(ctx, V, vdtype, B, X, Y, Z, num_targets, ijk, nullptr, sums, st);
+}
 
 extern "C" int rml_derive_slice_supported(const rml_ctx* ctx, const void* V, int vdtype, int X, int Y, int Z, int num_targets) {
     if (X <= 0 || Y <= 0 || Z <= 0 || (vdtype != RML_VOL_F32 && vdtype != RML_VOL_U8)) return 0;
@@ -1026,7 +1035,13 @@ static int derive_two_kernels(rml_ctx* ctx, const void* V, int vdtype, int64_t B
     void* ws = nullptr;
     int rc = rml_ws_reserve(ctx, need, &ws, st);
     if (rc) return rc;
-    float* xzs = static_cast<float*>(ws);
+    return derive_two_kernels_at(ctx, V, vdtype, B, X, Y, Z, num_targets, ijk, profiles, static_cast<float*>(ws), st);
+}
+
+// the same with the sum planes at xzs (B * (X*Z + Y*Z) floats)
+static int derive_two_kernels_at(rml_ctx* ctx, const void* V, int vdtype, int64_t B, int X, int Y, int Z, int num_targets, int32_t* ijk,
+                                 float* profiles, float* xzs, hipStream_t st) {
+    int rc;
     float* yzs = xzs + (size_t)B * X * Z;
     ProjOut o{};
     o.p[0] = xzs; o.stride[0] = (int64_t)X * Z;

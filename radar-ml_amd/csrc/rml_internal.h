@@ -40,6 +40,7 @@ struct rml_opts {
     int smo_lds_rows = RML_SMO_LDS_ROWS_MAX;   // RML_OPT_SMO_LDS_ROWS: duals of more rows run on the workspace variant of k_smo
     int conv7 = RML_CONV7_DEFAULT;  // RML_OPT_CONV7: bit 0 forward, bit 1 backward of the generator's output layer on csrc/gen.hip
     int sgd_resident_d = RML_SGD_RESIDENT_D_MAX;   // RML_OPT_SGD_RESIDENT_D: wider problems run on the workspace variant of k_sgd
+    int zoom_rows = 0;          // RML_OPT_ZOOM_ROWS: k_zoom_rows 0 = one workgroup per (row, plane), 1 / 2 one per row: planes together / in turn
 };
 
 struct rml_ws_retired {         // a workspace block that was outgrown: freed once the work queued before its retirement is done
@@ -228,6 +229,30 @@ int rml_launch_project_split(rml_ctx* ctx, const void* V, int vdtype, int64_t B,
 // pass over the frames; o.sel == 0: derive only.  RML_ERR_UNSUPPORTED (no message set) when the shape has no fused kernel.
 int rml_launch_derive_slice(rml_ctx* ctx, const void* V, int vdtype, int64_t B, int X, int Y, int Z, int num_targets,
                             int32_t* ijk_out, float* profiles, const ProjOut& o, hipStream_t st);
+
+// the strongest targets of B frames (rml_derive_targets) with the sum planes in the caller's scratch: B * (X*Z + Y*Z) floats, touched
+// only by shapes without the fused derive kernel.  For callers whose own chunks live in the context's workspace.
+int rml_launch_derive(rml_ctx* ctx, const void* V, int vdtype, int64_t B, int X, int Y, int Z, int num_targets, int32_t* ijk,
+                      float* sums, hipStream_t st);
+
+// ---- projection rows zoomed to a model's geometry (zoom_rows.hip) ------------------------
+// One validated geometry of rml_project_zoom / rml_project_zoom_svm: the source grid, the output planes, and how a chunk of
+// source-grid rows is kept -- float32 rows of stride Dsrc, or (uint8 volumes: codes by construction) code rows of stride round_up(Dsrc, 128).
+struct rml_zoom_plan {
+    int vdtype, X, Y, Z, T; uint32_t mask; int32_t out_shape[6];
+    bool codes;               // the source rows are code rows
+    bool derive;              // mode SLICE without ijk: the T strongest targets of every frame, derived at the source grid
+    int64_t Dsrc, Dout, ld_src;
+    size_t lds; int by_plane; // dynamic LDS of k_zoom_rows; 0: the planes of a row together, 1: one after the other, 2: a workgroup each
+};
+// RML_ERR_INVALID / RML_ERR_UNSUPPORTED (a plane whose float64 image exceeds 150 KB) with a message that starts with `who`
+int rml_zoom_plan_make(const rml_ctx* ctx, const char* who, int vdtype, int mode, int X, int Y, int Z, int T, bool derive, const int32_t* out_shape,
+                       uint32_t mask, rml_zoom_plan* zp);
+size_t rml_zoom_stage_bytes(const rml_zoom_plan& zp, int64_t frames);      // scratch of one chunk of `frames` frames (a multiple of 256)
+// projection of `frames` frames at the source grid into `scratch`, then k_zoom_rows: frames * T float rows at feat (stride ld_feat,
+// columns [Dout, pad_to) zeroed), their float64 squared norms (the sum order of k_prepare_rows) and row flags 0 ("not on the code grid")
+int rml_zoom_stage_run(rml_ctx* ctx, const rml_zoom_plan& zp, void* scratch, const void* V, int64_t frames, int mode, const int32_t* ijk,
+                       float scale_div, float* feat, int64_t ld_feat, int64_t pad_to, double* row_nsq, int32_t* row_flags, hipStream_t st);
 
 // ---- SVM (svm.hip) ------------------------------------------------------------------------
 struct rml_svm {

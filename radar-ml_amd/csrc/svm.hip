@@ -828,6 +828,90 @@ extern "C" int rml_derive_project_svm(rml_ctx* ctx, const rml_svm* m, const void
                              DecisionOut{dec_ovo, dec_ovr, proba, label_vote, label_calib}, stream);
 }
 
+// ---- the front door for a foreign arena: projection at the source grid -> k_zoom_rows -> SVM -----------------------------
+namespace {
+// One chunk.  The caller's stream: the projection at the source grid into the chunk's stage, k_zoom_rows into the workspace (float
+// rows at the model's stride, norms, flags -- what chunk_off_grid asks a projection for) and the digit planes of the zoomed rows;
+// then the GEMM stream takes the chunk over, as in chunk_off_grid.
+int chunk_zoom(const FrontCall& f, const FrontChunk& ck, const rml_zoom_plan& zp, void* stage) {
+    int rc = rml_zoom_stage_run(f.ctx, zp, stage, ck.V, ck.n, f.mode, ck.ijk, f.scale_div, ck.w.f32, f.m->Df, f.m->Df, ck.w.nsq, ck.w.flags,
+                                f.caller);
+    if (rc) return rc;
+    if (f.use_dig) { launch_digit_rows(f.m, ck.w, ck.n, f.caller); RML_HIP(hipGetLastError()); }
+    RML_HIP(hipEventRecord(ck.ev_proj, f.caller));
+    RML_HIP(hipStreamWaitEvent(f.ctx->aux_stream, ck.ev_proj, 0));
+    return gemm_stage(f, ck);
+}
+
+int front_zoom(FrontCall f, const rml_zoom_plan& zp) {
+    rml_ctx* ctx = f.ctx; const rml_svm* m = f.m;
+    // zoomed rows are off the code grid whatever the model: the float64 kernel, or the multi-digit kernel under the rule of
+    // rml_svm_decision for float rows (so that the call computes what rml_project_zoom + rml_svm_decision compute)
+    f.use_dig = use_dig_gemm(m, RML_PATH_AUTO, f.B, ctx->num_cu);
+    f.plan.policy = RML_PATH_F64; f.plan.dig_ready = f.use_dig;
+    ChunkNeeds need{};
+    need.f32 = true; need.dig = f.use_dig;
+    if (f.B <= kTile) {
+        // a single observation (predict.py:98-119) or any batch of one sample tile: everything on the caller's stream, as front_single_tile
+        ChunkWs w; void* stage = nullptr;
+        int rc = reserve_chunks(ctx, m, kTile, need, f.caller, &w, 1, rml_zoom_stage_bytes(zp, f.B), &stage);
+        if (rc) return rc;
+        rc = rml_zoom_stage_run(ctx, zp, stage, f.V, f.B, f.mode, f.ijk, f.scale_div, w.f32, m->Df, m->Df, w.nsq, w.flags, f.caller);
+        if (rc) return rc;
+        if (f.use_dig) { launch_digit_rows(m, w, f.B, f.caller); RML_HIP(hipGetLastError()); }
+        return run_chunk(ctx, m, ws_rows(m, w, f.B), f.plan, w, f.out, f.caller);
+    }
+    const int64_t CH = f.use_dig ? pick_chunk(ctx, m, f.B, 8192, true) : std::min<int64_t>(round_up(f.B, kTile), pick_chunk_opt(ctx, 8192));
+    constexpr int NBUF = 2;         // workspaces and stages in rotation, as front_chunked
+    ChunkWs w2[NBUF];
+    const size_t sbytes = rml_zoom_stage_bytes(zp, CH);
+    void* stages = nullptr;
+    int rc = reserve_chunks(ctx, m, CH, need, f.caller, w2, NBUF, NBUF * sbytes, &stages);
+    if (rc) return rc;
+    RML_HIP(hipEventRecord(ctx->ev_fork, f.caller));
+    RML_HIP(hipStreamWaitEvent(ctx->aux_stream, ctx->ev_fork, 0));
+    int64_t c = 0;
+    for (int64_t r0 = 0; r0 < f.B; r0 += CH, ++c) {
+        const int b = (int)(c % NBUF);
+        if (c >= NBUF) RML_HIP(hipStreamWaitEvent(f.caller, ctx->ev_done[b], 0));    // workspace reuse
+        const FrontChunk ck{r0, std::min(CH, f.B - r0), w2[b], ctx->ev_proj[b], static_cast<const unsigned char*>(f.V) + r0 * f.frame_bytes(),
+                            f.ijk ? f.ijk + r0 * 3 : nullptr, nullptr};
+        rc = chunk_zoom(f, ck, zp, static_cast<unsigned char*>(stages) + (size_t)b * sbytes);
+        if (rc) return rc;
+        RML_HIP(hipEventRecord(ctx->ev_done[b], ctx->aux_stream));
+    }
+    RML_HIP(hipEventRecord(ctx->ev_join, ctx->aux_stream));
+    RML_HIP(hipStreamWaitEvent(f.caller, ctx->ev_join, 0));
+    return RML_OK;
+}
+}  // namespace
+
+// predict.py:98-119 for a recording whose arena differs from the training arena (calc_proj_zoom, predict.py:34-54, is not 1):
+// slices or max-projections at the source grid, common.process_samples' zoom to the training geometry (common.py:141-148), the
+// classifier of predict.py:60 -- B frames per call, nothing through the host
+extern "C" int rml_project_zoom_svm(rml_ctx* ctx, const rml_svm* m, const void* V, int vdtype, int64_t B, int X, int Y, int Z,
+                                    int mode, const int32_t* ijk, const int32_t* out_shape, float scale_div, uint32_t mask,
+                                    double* dec_ovo, double* dec_ovr, double* proba,
+                                    int32_t* label_vote, int32_t* label_calib, void* stream) {
+    RML_REQUIRE(ctx && m && B >= 0, RML_ERR_INVALID, "rml_project_zoom_svm: bad arguments");
+    if (mode == RML_MODE_MAX_NAN) mode = RML_MODE_MAX;
+    RML_REQUIRE(mode == RML_MODE_MAX || mode == RML_MODE_SLICE || mode == RML_MODE_SUM, RML_ERR_INVALID, "rml_project_zoom_svm: unknown mode %d", mode);
+    rml_zoom_plan zp;
+    if (int rc = rml_zoom_plan_make(ctx, "rml_project_zoom_svm", vdtype, mode, X, Y, Z, 1, mode == RML_MODE_SLICE && !ijk, out_shape, mask, &zp)) return rc;
+    RML_REQUIRE(zp.Dout == m->D, RML_ERR_INVALID, "rml_project_zoom_svm: the zoomed planes give D=%lld, model has D=%lld",
+                (long long)zp.Dout, (long long)m->D);
+    if (B == 0) return RML_OK;
+    RML_REQUIRE(V != nullptr, RML_ERR_INVALID, "rml_project_zoom_svm: V is NULL");
+    RML_REQUIRE(B < (int64_t)1 << 31, RML_ERR_UNSUPPORTED, "rml_project_zoom_svm: B too large");
+    RML_REQUIRE(!(proba || label_calib) || m->has_calib, RML_ERR_STATE, "rml_project_zoom_svm: model has no calibrators");
+    RML_HIP(hipSetDevice(ctx->device));
+    hipStream_t caller = static_cast<hipStream_t>(stream);
+    rml_ctx_guard guard(ctx, caller);       // shared workspaces, aux stream and chunk events (the caller's stream joins at the end)
+    const FrontCall f{ctx, m, caller, V, vdtype, B, X, Y, Z, mode, ijk, /*derive=*/false, nullptr, scale_div, mask,
+                      DecisionOut{dec_ovo, dec_ovr, proba, label_vote, label_calib}, /*grid_ok=*/false};
+    return front_zoom(f, zp);
+}
+
 // libsvm's own Platt coefficients (SVC(probability=True): sk:svm/_base.py _probA / _probB, one pair per class pair):
 // uploaded once, at load time, so that rml_svm_pairwise_proba is an ordinary asynchronous launch
 extern "C" int rml_svm_set_platt(rml_ctx* ctx, rml_svm* m, const double* probA, const double* probB) {

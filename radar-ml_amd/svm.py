@@ -77,6 +77,12 @@ def _check_classes(n):
                                   "(csrc/svm_finish.h kMaxC)" % (n, MAX_CLASSES))
 
 
+def _check_zoomed_len(D, n_features, grid, shapes):
+    if D != n_features:
+        raise ValueError("proj_zoom takes the %dx%dx%d arena to planes %s: %d features, but the model is expecting %d"
+                         % (grid + (shapes, D, n_features)))
+
+
 class GpuSVC(_Base):
     """GPU twin of a fitted ``sklearn.svm.SVC`` (C-SVC, one-vs-one, RBF or linear kernel)."""
 
@@ -207,18 +213,23 @@ class GpuSVC(_Base):
         return ovo, ovr, vote, proba, lab
 
     def decide_volumes(self, volumes, mode="max", ijk=None, proj_mask=ProjMask(True, True, True), scale=True,
-                       want_proba=None, validate_ijk=True):
+                       want_proba=None, validate_ijk=True, proj_zoom=None):
         """Fused batched path: (B,X,Y,Z) volumes -> projection -> SVM, features never leave the GPU.
         Returns a dict of CUDA tensors (dec_ovo, dec_ovr, label_vote[, proba, label_calib]); mode='slice' without ``ijk``
         slices through the strongest derived target of every frame (common.py:49-80) and also returns it as ``ijk`` (B,3)
         where the one-pass kernel ran.  ``validate_ijk=False``: the caller vouches that a DEVICE ``ijk`` is within
-        [-size, size) -- the range check of a device tensor costs a synchronising read-back per call."""
+        [-size, size) -- the range check of a device tensor costs a synchronising read-back per call.
+        ``proj_zoom``: volumes from an arena that differs from the model's (predict.py:109-116) -- projections at the volumes'
+        own grid, zoomed on the device to the model's geometry (rml_project_zoom_svm); ValueError when the zoomed planes do not
+        give the model's feature count.  None or a unit zoom: the call above, unchanged."""
         torch = _torch()
         lib = _lib.load()
-        from .common import derive_targets, _slice_indices, process_volumes
+        from .common import derive_targets, _slice_indices, process_volumes, is_unit_zoom
         v, vdt = _as_device_volumes(volumes, self._dev)
         if v.ndim == 3:
             v = v.unsqueeze(0)
+        if not is_unit_zoom(proj_zoom, proj_mask):
+            return self._decide_volumes_zoom(v, vdt, mode, ijk, proj_mask, scale, want_proba, validate_ijk, proj_zoom)
         B, X, Y, Z = v.shape
         dev = v.device
         C_ = len(self.classes_)
@@ -269,6 +280,47 @@ class GpuSVC(_Base):
                 float(RADAR_MAX) if scale else 0.0, _mask_bits(proj_mask),
                 _lib.ptr(out["dec_ovo"]), _lib.ptr(out["dec_ovr"]), _lib.ptr(out.get("proba")),
                 _lib.ptr(out["label_vote"]), _lib.ptr(out.get("label_calib")), _lib.stream_ptr(dev)), "rml_project_svm")
+        return out
+
+    def _decide_volumes_zoom(self, v, vdt, mode, ijk, proj_mask, scale, want_proba, validate_ijk, proj_zoom):
+        """decide_volumes for a foreign arena: one call per batch, the rows of the volumes' own grid live for a chunk."""
+        torch = _torch()
+        lib = _lib.load()
+        from .common import _slice_indices, process_volumes, zoom_out_shapes, _zoomed_len, _shape_array
+        B, X, Y, Z = v.shape
+        dev = v.device
+        shapes = zoom_out_shapes(X, Y, Z, proj_zoom)
+        _check_zoomed_len(_zoomed_len(shapes, proj_mask), self.n_features_in_, (X, Y, Z), shapes)
+        C_ = len(self.classes_)
+        P = C_ * (C_ - 1) // 2
+        if want_proba is None:
+            want_proba = self.has_calibration
+        ijk_t = None
+        if mode == "slice" and ijk is not None:
+            ijk_t, T = _slice_indices(ijk, B, X, Y, Z, dev, validate=validate_ijk)
+            if T > 1:
+                # several targets per frame: zoomed rows first, then the SVM on the B*T rows (frame-major), as without a zoom
+                feat = process_volumes(v, mode="slice", ijk=ijk_t.reshape(B, T, 3), proj_mask=proj_mask, scale=scale, proj_zoom=proj_zoom)
+                ovo, ovr, vote, proba, lab = self._decide(feat, want_proba=want_proba)
+                out = {"dec_ovo": ovo, "dec_ovr": ovr, "label_vote": vote}
+                if want_proba:
+                    out["proba"], out["label_calib"] = proba, lab
+                return out
+        out = {
+            "dec_ovo": torch.empty((B, P), dtype=torch.float64, device=dev),
+            "dec_ovr": torch.empty((B,) if C_ == 2 else (B, C_), dtype=torch.float64, device=dev),
+            "label_vote": torch.empty((B,), dtype=torch.int32, device=dev),
+        }
+        if want_proba:
+            out["proba"] = torch.empty((B, C_), dtype=torch.float64, device=dev)
+            out["label_calib"] = torch.empty((B,), dtype=torch.int32, device=dev)
+        arr = _shape_array(shapes)
+        with torch.cuda.device(dev):
+            _lib.check(lib.rml_project_zoom_svm(
+                self._ctx, self._h, _lib.ptr(v), vdt, B, X, Y, Z, _lib.MODES[mode], _lib.ptr(ijk_t), C.cast(arr, C.c_void_p),
+                float(RADAR_MAX) if scale else 0.0, _mask_bits(proj_mask),
+                _lib.ptr(out["dec_ovo"]), _lib.ptr(out["dec_ovr"]), _lib.ptr(out.get("proba")),
+                _lib.ptr(out["label_vote"]), _lib.ptr(out.get("label_calib")), _lib.stream_ptr(dev)), "rml_project_zoom_svm")
         return out
 
     def kernel_matrix(self, X, path=None):
@@ -406,11 +458,19 @@ class GpuLinearClassifier(_Base):
         lab = self._run(self._rows(X))[1]
         return self.classes_.take(lab.cpu().numpy().astype(np.intp))
 
-    def decide_volumes(self, volumes, mode="max", ijk=None, proj_mask=ProjMask(True, True, True), scale=True):
+    def decide_volumes(self, volumes, mode="max", ijk=None, proj_mask=ProjMask(True, True, True), scale=True, proj_zoom=None):
         """Batched path for the reference's default (SGD) model: (B,X,Y,Z) volumes -> projection + feature rows
-        (one pass over the volumes) -> linear scores, labels and calibrated probabilities, all on the GPU."""
-        from .common import process_volumes
-        feat = process_volumes(volumes, mode=mode, ijk=ijk, proj_mask=proj_mask, scale=scale, device=self._dev)
+        (one pass over the volumes) -> linear scores, labels and calibrated probabilities, all on the GPU.
+        ``proj_zoom``: volumes from another arena, zoomed to the model's geometry on the device (process_volumes); ValueError when
+        the zoomed planes do not give the model's feature count."""
+        from .common import process_volumes, is_unit_zoom, zoom_out_shapes, _zoomed_len
+        if not is_unit_zoom(proj_zoom, proj_mask):
+            grid = tuple(int(s) for s in volumes.shape[-3:])
+            shapes = zoom_out_shapes(grid[0], grid[1], grid[2], proj_zoom)
+            _check_zoomed_len(_zoomed_len(shapes, proj_mask), self.n_features_in_, grid, shapes)
+            feat = process_volumes(volumes, mode=mode, ijk=ijk, proj_mask=proj_mask, scale=scale, device=self._dev, proj_zoom=proj_zoom)
+        else:
+            feat = process_volumes(volumes, mode=mode, ijk=ijk, proj_mask=proj_mask, scale=scale, device=self._dev)
         dec, lab, proba, labc = self._run(feat, want_proba=self.has_calibration)
         out = {"dec": dec, "label": lab}
         if proba is not None:
