@@ -119,7 +119,7 @@ int rml_ctx_device(const rml_ctx* ctx);
  *   RML_OPT_SMO_LDS_ROWS (default RML_SMO_LDS_ROWS_MAX = 2 768, the 160 KB of a CU at 59 bytes per row): rml_smo_solve keeps the state
  *     of a dual of at most this many rows in LDS; larger duals run the same code on the workspace.  0: every dual on the workspace.
  *   RML_OPT_SGD_RESIDENT_D (default RML_SGD_RESIDENT_D_MAX = 10 240, ten elements per thread of a 1 024-thread workgroup):
- *     rml_sgd_solve keeps the weights of a problem of at most this many features in registers; wider rows run the same code with
+ *     rml_sgd_solve and rml_sgd_online keep the weights of a problem of at most this many features in registers; wider rows run the same code with
  *     the weights on the workspace.  0: every problem on the workspace.  The results are the same bits either way.
  *   RML_OPT_CONV7 (default RML_CONV7_DEFAULT; bit 0: forward, bit 1: backward): which passes of the generator's output layer the callers
  *     of rml_conv7_tanh_* (nn_common.conv7_tanh) run on the hand-written kernels; a cleared bit sends that pass to the convolution library.
@@ -509,6 +509,58 @@ int rml_sgd_score(rml_ctx* ctx, const float* X, int64_t N, int64_t D, int64_t ld
                   const double* t, int n_classes, const rml_sgd_fit* fits, int64_t n_fits, const int32_t* test_rows,
                   const int32_t* test_y, int64_t n_test_total, double* dec, int32_t* labels, int32_t* correct, void* stream);
 int rml_sgd_shuffle(uint32_t seed, int64_t n, int32_t* perm_inout);
+
+/* ---- a chain of SGDClassifier.partial_fit calls on the device (train.py:409-416, 418-438) ------------------------------
+ * rml_sgd_online: n_steps partial_fit calls of ONE SGDClassifier of n_classes (2..8) classes on resident rows, each followed,
+ * where its step asks for it, by predict on the held-out rows, as ONE asynchronous call on `stream`: one persistent
+ * workgroup per class problem (k_sgd_online) that keeps the weights where rml_sgd_solve keeps them for all the steps, then
+ * k_sgd_online_finish for the labels and counts.  No device synchronisation, no environment variable; it uses the context's
+ * workspace and can be captured like rml_sgd_solve.
+ *   X, N, D, ld: as for rml_sgd_solve.  probs: HOST, K descriptors, K = n_classes (class order), or ONE when n_classes == 2
+ *   (class 1 positive): penalty, average, shuffle, alpha, l1_ratio, weight_pos / weight_neg, the output slot `out` (distinct),
+ *   warm, and t0 = est.t_ before the first step; penalty, average, t0 and warm are the same for all K.  n, seed, rows_off,
+ *   y_off, max_iter, tol and n_iter_no_change are ignored: a partial_fit call is exactly one epoch and cannot stop early.
+ *   steps: HOST, n_steps records.  Step s trains on the n rows at rows + off (DEVICE int32, n_rows_total entries in [0, N), in
+ *   the order the partial_fit call would see them) with the class indices at cls + off (DEVICE int32, same offsets): the
+ *   problem of class c has the label 1 where cls == c.  Steps may share or overlap ranges.  seed[k]: the shuffle seed of
+ *   problem k for this call (scikit-learn draws them per call).  score != 0: the held-out rows are scored after the step.
+ *   test_rows / test_y: DEVICE int32, n_test >= 0 held-out rows and their class indices (no step is scored when n_test == 0).
+ * Per step and problem: one epoch of _plain_sgd64 from the state the previous step left, with everything a fresh _plain_sgd
+ * call starts anew started anew: the index array 0 .. n-1 and ONE shuffle with the step's seed, wscale = 1, the cumulative L1
+ * penalty u and q = 0, average_a = 0, average_b = 1; the epoch ends with reset_wscale; t advances by n.  The arithmetic and the
+ * dot order are rml_sgd_solve's.  Between steps the intercepts follow the statements of _fit_binary / _fit_multiclass
+ * (sklearn/linear_model/_stochastic_gradient.py:753-768, 807-823) with what their aliasing does.  Per problem k the call
+ * keeps SI[k] (_standard_intercept), AI[k] (_average_intercept) and, per estimator, the flag A ("intercept_ is
+ * _average_intercept").  A step starts problem k from (SI[k], AI[k]) and yields (icpt, aicpt).  With average > 0,
+ * AI[k] = aicpt.  Then, for more than two classes: icpt goes to AI[k] if A was set before the step, else to SI[k] (the
+ * former overwrites the averaged intercept and leaves SI stale, as scikit-learn does), and A = average > 0 && average <= t - 1.
+ * For two classes: if average > 0 && average <= t - 1, A is set and SI stays; else SI[0] = icpt and A is cleared.  coef_ /
+ * intercept_ are the averaged arrays iff A, and a scored step uses exactly that view: dec[r][c] = coef_[c] . x_r +
+ * intercept_[c] in rml_sgd_score's dot order, the label the first maximum (dec > 0 for two classes).
+ *   In and out, DEVICE, per slot `out` < n_out as rml_sgd_solve leaves them: coef, avg_coef (D doubles at out * D; avg_coef only
+ *   where average > 0), intercept = SI, avg_intercept = AI, and avg_flag (ONE int32: A); read where warm != 0 (else the state
+ *   starts at zero and A clear).  The weights are written once, at the end of the call.  A call split in two (steps 0..j, then
+ *   j..n_steps with t0 = t, warm = 1 and the state and flag the first left) gives the bits of the one call.
+ *   Out, DEVICE: t (per slot: t0 + the rows of the steps run), status (per slot: 1 all steps run, 2 non-finite weights, -1),
+ *   fail_step (ONE int32: the first step at which a problem went non-finite, else -1), correct (n_steps int32: the held-out
+ *   rows labelled as test_y says after step s; -1 for a step that was not scored), labels (n_test int32) and dec (n_test x
+ *   n_dec doubles, n_dec = 1 for two classes) of the last scored step.
+ * A row index outside [0, N), in any step or in test_rows, is found before anything is written: status -1 in every
+ * problem's slot, every other output untouched.  If a problem's weights go non-finite at step s (scikit-learn raises
+ * there): its status is 2, fail_step = s, correct[s ..] = -1, labels / dec are those of the last scored step before s; the
+ * other problems stop at the first step boundary after s at which they see it (they never wait for each other), so their
+ * weights are then those of some step >= s: the estimator is to be discarded, as after scikit-learn's exception. */
+typedef struct rml_sgd_step {
+    int64_t off;                /* into `rows` and `cls` */
+    int32_t n;                  /* rows of this partial_fit call, 1 .. RML_SGD_MAX_ROWS */
+    int32_t score;              /* != 0: predict on the held-out rows after this step */
+    uint32_t seed[8];           /* the shuffle seed of each class problem for this call */
+} rml_sgd_step;
+int rml_sgd_online(rml_ctx* ctx, const float* X, int64_t N, int64_t D, int64_t ld, const rml_sgd_problem* probs, int n_classes,
+                   const rml_sgd_step* steps, int64_t n_steps, const int32_t* rows, const int32_t* cls, int64_t n_rows_total,
+                   const int32_t* test_rows, const int32_t* test_y, int64_t n_test, int64_t n_out, double* coef, double* avg_coef,
+                   double* intercept, double* avg_intercept, double* t, int32_t* avg_flag, int32_t* status, int32_t* fail_step,
+                   int32_t* correct, int32_t* labels, double* dec, void* stream);
 
 /* ---- the host-side steps of SVC(probability=True).fit -------------------------------------------------------------------
  * libsvm's svm_train with probability = 1 runs, per class pair, svm_binary_svc_probability (scikit-learn 1.7.2,

@@ -16,7 +16,8 @@ from .predict import classifier, classify_batch, calc_proj_zoom
 from .synth import synth_volumes
 from .augment import DataGenerator, augment_planes, rotation_params
 from .train import (GridSearchSVC, find_best_svm_estimator, fit_svc, GridSearchSGD, find_best_sgd_svm_estimator, fit_sgd,
-                    partial_fit_sgd)
+                    partial_fit_sgd, partial_fit_sgd_steps, balance_classes, balance_indices, sgd_fit, svc_fit, calibrate_prefit,
+                    evaluate_model)
 
 __all__ = [
     "RadarMLError", "ProjMask", "ProjZoom", "DerivedTarget", "RADAR_MAX", "RADAR_MIN",
@@ -26,6 +27,7 @@ __all__ = [
     "classifier", "classify_batch", "calc_proj_zoom", "synth_volumes",
     "DataGenerator", "augment_planes", "rotation_params", "GridSearchSVC", "find_best_svm_estimator", "fit_svc",
     "GridSearchSGD", "find_best_sgd_svm_estimator", "fit_sgd", "partial_fit_sgd",
+    "partial_fit_sgd_steps", "balance_classes", "balance_indices", "sgd_fit", "svc_fit", "calibrate_prefit", "evaluate_model",
     "define_classifier", "train_classifier", "define_discriminator", "fold_batchnorm", "folded_packs",
 ]
 

@@ -82,6 +82,9 @@ SIGNATURES = {
                               c_void_p, c_void_p, c_int, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
                               c_void_p]),
     "rml_sgd_shuffle": (c_int, [c_uint32, c_int64, c_void_p]),
+    "rml_sgd_online": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int, c_void_p, c_int64, c_void_p, c_void_p, c_int64,
+                               c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                               c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "rml_libsvm_shuffle": (c_int, [c_uint32, c_int64, c_void_p]),
     "rml_platt_fit": (c_int, [c_void_p, c_void_p, c_int64, C.POINTER(c_double), C.POINTER(c_double), C.POINTER(c_int)]),
     "rml_project_svm": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_int, c_int, c_void_p, c_float,

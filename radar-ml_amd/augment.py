@@ -149,15 +149,15 @@ class DataGenerator(object):
                         pickle.dump({'x_batch': x[lo:hi], 'y_batch': y[lo:hi]}, fp)
             epoch += 1
 
-    def augment_dataset(self, x, y):
+    def augment_dataset(self, x, y, return_samples=False):
         """One pass of ``flow`` over the whole data set (what an epoch of train.py:506-515 appends to the training set) as ONE
         batched device job: the draws are made for every sample first, in the order the reference makes them batch by batch
         (its ``np.random.uniform`` stream simply continues across batches; its noise generator is a fresh, unseeded
         ``Generator(PCG64())`` per batch, here one per call), then every (projection, kind, shape) group is one ``rml_augment``
         launch and the results stay on the GPU.  Returns ``(tuples of CUDA float32 planes, labels as numpy)``; feed the planes
-        to ``process_samples`` / the SVM front doors without a host round trip."""
+        to ``process_samples`` / the SVM front doors without a host round trip.  With ``return_samples`` a third value says which sample
+        of ``x`` every tuple was made from (the online loop of train.py:425-438 forms its batches by it)."""
         weights = self._class_weights(y)
         jobs, labels = self._draw_jobs(x, y, weights)
-        if not jobs:
-            return [], np.array(labels)
-        return self._run_jobs(x, jobs, to_host=False), np.array(labels)
+        out = (self._run_jobs(x, jobs, to_host=False) if jobs else [], np.array(labels))
+        return out + (np.array([j[1] for j in jobs], dtype=np.int64),) if return_samples else out

@@ -1,5 +1,6 @@
-// Binary logistic-regression fits of SGDClassifier solved on the device, one workgroup per fit (rml_sgd_solve), and the held-out
-// rows scored from the solutions (rml_sgd_score).
+// Binary logistic-regression fits of SGDClassifier solved on the device, one workgroup per fit (rml_sgd_solve), the held-out
+// rows scored from the solutions (rml_sgd_score), and a chain of partial_fit calls of one estimator with the weights resident for
+// all its steps (rml_sgd_online).
 //
 // Reference arithmetic replaced (sk: = scikit-learn 1.7.2, the reference's dependency):
 //   sk:linear_model/_sgd_fast.pyx.tp:275-603    _plain_sgd64 (the epoch loop, the 'optimal' schedule, the stopping rule)
@@ -27,6 +28,7 @@
 // k_sgd<EPT, ..> with EPT = 1, 2, 4, 10 keeps the state (w, and q / the averaged weights where the problem has them) in
 // registers, EPT elements per thread, and the current and next row beside it: D up to 10 240.  k_sgd<0, ..> is the same code
 // with the state in a slice of the context's workspace and the row re-read from memory, for any D (RML_OPT_SGD_RESIDENT_D).
+// k_sgd_online<EPT, ..> runs the same epoch (sgd_epoch) once per partial_fit step of train.py:409-438.
 #include "rml_internal.h"
 #include <math.h>
 #include <string.h>
@@ -125,6 +127,133 @@ __device__ inline double block_sum(double s, double (*red)[kWaves], int& buf, in
     return tot;
 }
 
+// what _plain_sgd64 carries from sample to sample; k_sgd and k_sgd_online run the same epoch on it
+template <int EPT>
+struct SgdState {
+    Own<EPT> w, q, aw;
+    double intercept, avg_intercept, wscale, average_a, average_b, u, t;
+};
+
+// WeightVector.reset_wscale (sk:_weight_vector.pyx.tp:191-201)
+template <int EPT, bool AVG>
+__device__ __forceinline__ void sgd_reset_wscale(SgdState<EPT>& S, int nk, int tid, int64_t D) {
+#pragma unroll
+    for (int k = 0; k < nk; ++k) {
+        if (tid + (int64_t)k * kThreads < D) {
+            if (AVG) {
+                double a = S.aw.get(k);
+                a += S.average_a * S.w.get(k);
+                a *= 1.0 / S.average_b;
+                S.aw.set(k, a);
+            }
+            S.w.set(k, S.w.get(k) * S.wscale);
+        }
+    }
+    if (AVG) { S.average_a = 0.0; S.average_b = 1.0; }
+    S.wscale = 1.0;
+}
+
+template <int EPT>
+__device__ __forceinline__ void sgd_load_row(Row<EPT>& r, const float* __restrict__ X, int64_t row, int64_t ld, int64_t D, int tid) {
+    if constexpr (EPT > 0) {
+        const float* __restrict__ xr = X + row * ld;
+#pragma unroll
+        for (int k = 0; k < EPT; ++k) {
+            const int64_t e = tid + (int64_t)k * kThreads;
+            r.v[k] = e < D ? xr[e] : 0.0f;
+        }
+    }
+}
+
+// One epoch of _plain_sgd64 (sk:_sgd_fast.pyx.tp:470-552) over the n rows rows[perm[0]], rows[perm[1]], ..; returns the epoch's summed
+// loss.  The label of a row is lab[.] itself (pos < 0: 0 / 1), or lab[.] == pos (class indices, the problem of class pos).
+template <int EPT, bool L1, bool AVG>
+__device__ __forceinline__ double sgd_epoch(SgdState<EPT>& S, const SgdDev& P, const int32_t* __restrict__ rows,
+                                            const int32_t* __restrict__ lab, int pos_class, int n, const int32_t* perm,
+                                            const float* __restrict__ X, int64_t D, int64_t ld, int nk, double l1_ratio,
+                                            double (*red)[kWaves], int& buf, int tid, int lane, int wave) {
+    const double alpha = P.alpha, optimal_init = P.optimal_init, average = (double)P.average;
+    double sumloss = 0;
+    Row<EPT> xn;
+    sgd_load_row(xn, X, rows[perm[0]], ld, D, tid);
+    for (int i = 0; i < n; ++i) {
+        const int pos = perm[i];
+        const double y = pos_class < 0 ? (double)lab[pos] : (lab[pos] == pos_class ? 1.0 : 0.0);
+        const float* __restrict__ xrow = X + (int64_t)rows[pos] * ld;
+        Row<EPT> x = xn;
+        if (i + 1 < n) sgd_load_row(xn, X, rows[perm[i + 1]], ld, D, tid);     // the next row travels while this one is reduced
+        auto xval = [&](int k, int64_t e) -> double {
+            if constexpr (EPT > 0) return (double)x.v[k]; else return (double)xrow[e];
+        };
+
+        // p = w.dot(x) + intercept, in the order of the header
+        double s = 0;
+#pragma unroll
+        for (int k = 0; k < nk; ++k) {
+            const int64_t e = tid + (int64_t)k * kThreads;
+            if (e < D) s += S.w.get(k) * xval(k, e);
+        }
+        double p = block_sum(s, red, buf, lane, wave);
+        p *= S.wscale;
+        p = p + S.intercept;
+        const double eta = 1.0 / (alpha * (optimal_init + S.t - 1));
+        sumloss += half_binomial_loss(y, p);
+        const double class_weight = y > 0.0 ? P.weight_pos : P.weight_neg;
+        double dloss = half_binomial_grad(y, p);
+        if (dloss < -kMaxDloss) dloss = -kMaxDloss;
+        else if (dloss > kMaxDloss) dloss = kMaxDloss;
+        double update = -eta * dloss;
+        update *= class_weight * 1.0;
+        if (P.penalty >= RML_SGD_L2) {                          // not for the pure L1 penalty (sk:513-516)
+            const double c = 1.0 - ((1.0 - l1_ratio) * eta * alpha);
+            S.wscale *= c > 0 ? c : 0;
+            if (S.wscale < 1e-9) sgd_reset_wscale<EPT, AVG>(S, nk, tid, D);
+        }
+        if (update != 0.0) S.intercept += update * 1.0;
+        const bool averaging = AVG && 0 < average && average <= S.t;
+        const double num_iter = S.t - average + 1;
+        if (L1) S.u += (l1_ratio * eta * alpha);
+        const double c_add = update / S.wscale, c_avg = -update / S.wscale;
+        // w.add, w.add_average and l1penalty, element by element in that order
+#pragma unroll
+        for (int k = 0; k < nk; ++k) {
+            const int64_t e = tid + (int64_t)k * kThreads;
+            if (e < D) {
+                const double val = xval(k, e);
+                double wk = S.w.get(k);
+                if (update != 0.0) wk += val * c_add;
+                if (AVG && averaging) S.aw.set(k, S.aw.get(k) + S.average_a * val * c_avg);
+                if (L1) {
+                    const double z = wk;
+                    const double qk = S.q.get(k);
+                    if (S.wscale * z > 0.0) { const double v = wk - ((S.u + qk) / S.wscale); wk = v > 0.0 ? v : 0.0; }
+                    else if (S.wscale * z < 0.0) { const double v = wk + ((S.u - qk) / S.wscale); wk = v < 0.0 ? v : 0.0; }
+                    S.q.set(k, qk + S.wscale * (wk - z));
+                }
+                S.w.set(k, wk);
+            }
+        }
+        if (AVG && averaging) {
+            const double mu = 1.0 / num_iter;
+            if (num_iter > 1) S.average_b /= (1.0 - mu);
+            S.average_a += mu * S.average_b * S.wscale;
+            S.avg_intercept += ((S.intercept - S.avg_intercept) / num_iter);
+        }
+        S.t += 1;
+    }
+    return sumloss;
+}
+
+// floating-point under-/overflow check on the stored (unscaled) weights, sk:554-557: this thread's share
+template <int EPT>
+__device__ __forceinline__ int sgd_nonfinite(const SgdState<EPT>& S, int nk, int tid, int64_t D) {
+    int nonfinite = !isfinite(S.intercept);
+#pragma unroll
+    for (int k = 0; k < nk; ++k)
+        if (tid + (int64_t)k * kThreads < D) nonfinite |= !isfinite(S.w.get(k));
+    return nonfinite;
+}
+
 template <int EPT, bool L1, bool AVG>
 __global__ __launch_bounds__(kThreads) void k_sgd(const SgdDev* __restrict__ probs, const int32_t* __restrict__ order,
                                                   const float* __restrict__ X, int64_t N, int64_t D, int64_t ld,
@@ -155,137 +284,34 @@ __global__ __launch_bounds__(kThreads) void k_sgd(const SgdDev* __restrict__ pro
         return;
     }
 
-    Own<EPT> w, q, aw;
-    w.bind(P.ws, tid); q.bind(P.ws + D, tid); aw.bind(P.ws + 2 * D, tid);
+    SgdState<EPT> S;
+    S.w.bind(P.ws, tid); S.q.bind(P.ws + D, tid); S.aw.bind(P.ws + 2 * D, tid);
 #pragma unroll
     for (int k = 0; k < nk; ++k) {
         const int64_t e = tid + (int64_t)k * kThreads;
         const bool in = e < D;
         if (EPT || in) {
-            w.set(k, P.warm && in ? P.coef[e] : 0.0);
-            if (L1) q.set(k, 0.0);
-            if (AVG) aw.set(k, P.warm && in ? P.avg_coef[e] : 0.0);
+            S.w.set(k, P.warm && in ? P.coef[e] : 0.0);
+            if (L1) S.q.set(k, 0.0);
+            if (AVG) S.aw.set(k, P.warm && in ? P.avg_coef[e] : 0.0);
         }
     }
-    double intercept = P.warm ? intercept_out[P.out] : 0.0;
-    double avg_intercept = P.warm && AVG ? avg_intercept_out[P.out] : 0.0;
-    double wscale = 1.0, average_a = 0.0, average_b = 1.0, u = 0.0, t = P.t0;
-    const double alpha = P.alpha;
+    S.intercept = P.warm ? intercept_out[P.out] : 0.0;
+    S.avg_intercept = P.warm && AVG ? avg_intercept_out[P.out] : 0.0;
+    S.wscale = 1.0; S.average_a = 0.0; S.average_b = 1.0; S.u = 0.0; S.t = P.t0;
     const double l1_ratio = P.penalty == RML_SGD_L2 ? 0.0 : (P.penalty == RML_SGD_L1 ? 1.0 : P.l1_ratio);
-    const double optimal_init = P.optimal_init;
-    const double average = (double)P.average;
     double best_loss = INFINITY;
     int no_improvement = 0, buf = 0, status = 1, epochs = 0;
 
-    // WeightVector.reset_wscale (sk:_weight_vector.pyx.tp:191-201)
-    auto reset_wscale = [&]() {
-#pragma unroll
-        for (int k = 0; k < nk; ++k) {
-            if (tid + (int64_t)k * kThreads < D) {
-                if (AVG) {
-                    double a = aw.get(k);
-                    a += average_a * w.get(k);
-                    a *= 1.0 / average_b;
-                    aw.set(k, a);
-                }
-                w.set(k, w.get(k) * wscale);
-            }
-        }
-        if (AVG) { average_a = 0.0; average_b = 1.0; }
-        wscale = 1.0;
-    };
-    auto load_row = [&](Row<EPT>& r, int64_t row) {
-        if constexpr (EPT > 0) {
-            const float* __restrict__ xr = X + row * ld;
-#pragma unroll
-            for (int k = 0; k < EPT; ++k) {
-                const int64_t e = tid + (int64_t)k * kThreads;
-                r.v[k] = e < D ? xr[e] : 0.0f;
-            }
-        }
-    };
-
     for (int epoch = 0; epoch < P.max_iter; ++epoch) {
-        double sumloss = 0;
         if (P.shuffle) {
             if (tid == 0) fisher_yates(P.seed, n, perm);           // every read of the last epoch lies before its last barrier
             __syncthreads();
         }
-        Row<EPT> xn;
-        load_row(xn, P.rows[perm[0]]);
-        for (int i = 0; i < n; ++i) {
-            const int pos = perm[i];
-            const double y = (double)P.y[pos];
-            const float* __restrict__ xrow = X + (int64_t)P.rows[pos] * ld;
-            Row<EPT> x = xn;
-            if (i + 1 < n) load_row(xn, P.rows[perm[i + 1]]);       // the next row travels while this one is reduced
-            auto xval = [&](int k, int64_t e) -> double {
-                if constexpr (EPT > 0) return (double)x.v[k]; else return (double)xrow[e];
-            };
-
-            // p = w.dot(x) + intercept, in the order of the header
-            double s = 0;
-#pragma unroll
-            for (int k = 0; k < nk; ++k) {
-                const int64_t e = tid + (int64_t)k * kThreads;
-                if (e < D) s += w.get(k) * xval(k, e);
-            }
-            double p = block_sum(s, red, buf, lane, wave);
-            p *= wscale;
-            p = p + intercept;
-            const double eta = 1.0 / (alpha * (optimal_init + t - 1));
-            sumloss += half_binomial_loss(y, p);
-            const double class_weight = y > 0.0 ? P.weight_pos : P.weight_neg;
-            double dloss = half_binomial_grad(y, p);
-            if (dloss < -kMaxDloss) dloss = -kMaxDloss;
-            else if (dloss > kMaxDloss) dloss = kMaxDloss;
-            double update = -eta * dloss;
-            update *= class_weight * 1.0;
-            if (P.penalty >= RML_SGD_L2) {                          // not for the pure L1 penalty (sk:513-516)
-                const double c = 1.0 - ((1.0 - l1_ratio) * eta * alpha);
-                wscale *= c > 0 ? c : 0;
-                if (wscale < 1e-9) reset_wscale();
-            }
-            if (update != 0.0) intercept += update * 1.0;
-            const bool averaging = AVG && 0 < average && average <= t;
-            const double num_iter = t - average + 1;
-            if (L1) u += (l1_ratio * eta * alpha);
-            const double c_add = update / wscale, c_avg = -update / wscale;
-            // w.add, w.add_average and l1penalty, element by element in that order
-#pragma unroll
-            for (int k = 0; k < nk; ++k) {
-                const int64_t e = tid + (int64_t)k * kThreads;
-                if (e < D) {
-                    const double val = xval(k, e);
-                    double wk = w.get(k);
-                    if (update != 0.0) wk += val * c_add;
-                    if (AVG && averaging) aw.set(k, aw.get(k) + average_a * val * c_avg);
-                    if (L1) {
-                        const double z = wk;
-                        const double qk = q.get(k);
-                        if (wscale * z > 0.0) { const double v = wk - ((u + qk) / wscale); wk = v > 0.0 ? v : 0.0; }
-                        else if (wscale * z < 0.0) { const double v = wk + ((u - qk) / wscale); wk = v < 0.0 ? v : 0.0; }
-                        q.set(k, qk + wscale * (wk - z));
-                    }
-                    w.set(k, wk);
-                }
-            }
-            if (AVG && averaging) {
-                const double mu = 1.0 / num_iter;
-                if (num_iter > 1) average_b /= (1.0 - mu);
-                average_a += mu * average_b * wscale;
-                avg_intercept += ((intercept - avg_intercept) / num_iter);
-            }
-            t += 1;
-        }
+        const double sumloss = sgd_epoch<EPT, L1, AVG>(S, P, P.rows, P.y, -1, n, perm, X, D, ld, nk, l1_ratio, red, buf, tid, lane, wave);
         epochs = epoch + 1;
 
-        // floating-point under-/overflow check on the stored (unscaled) weights, sk:554-557
-        int nonfinite = !isfinite(intercept);
-#pragma unroll
-        for (int k = 0; k < nk; ++k)
-            if (tid + (int64_t)k * kThreads < D) nonfinite |= !isfinite(w.get(k));
-        if (nonfinite) flag[1] = 1;
+        if (sgd_nonfinite(S, nk, tid, D)) flag[1] = 1;
         __syncthreads();
         if (flag[1]) { status = 2; break; }
         if (P.tol > -INFINITY && sumloss > best_loss - P.tol * (double)(unsigned)n) ++no_improvement;
@@ -294,18 +320,18 @@ __global__ __launch_bounds__(kThreads) void k_sgd(const SgdDev* __restrict__ pro
         if (no_improvement >= P.n_iter_no_change) { status = 0; break; }
     }
 
-    if (status != 2) reset_wscale();                // (sklearn raises instead; the outputs are then whatever the epoch left)
+    if (status != 2) sgd_reset_wscale<EPT, AVG>(S, nk, tid, D);     // (sklearn raises instead; the outputs are then whatever the epoch left)
 #pragma unroll
     for (int k = 0; k < nk; ++k) {
         const int64_t e = tid + (int64_t)k * kThreads;
         if (e < D) {
-            P.coef[e] = w.get(k);
-            if (AVG) P.avg_coef[e] = aw.get(k);
+            P.coef[e] = S.w.get(k);
+            if (AVG) P.avg_coef[e] = S.aw.get(k);
         }
     }
     if (tid == 0) {
-        intercept_out[P.out] = intercept;
-        if (AVG) avg_intercept_out[P.out] = avg_intercept;
+        intercept_out[P.out] = S.intercept;
+        if (AVG) avg_intercept_out[P.out] = S.avg_intercept;
         iter_out[P.out] = epochs;
         t_out[P.out] = P.t0 + (double)((int64_t)epochs * n);
         status_out[P.out] = status;
@@ -357,6 +383,220 @@ __global__ __launch_bounds__(kThreads) void k_sgd_score(const FitDev* __restrict
         F.labels[r] = label;
         if (label == F.test_y[r]) atomicAdd(&correct[blockIdx.x], 1);
     }
+}
+
+// ---- a chain of partial_fit calls of one estimator: rml_sgd_online --------------------------------------------------------------
+struct StepDev {                                    // one partial_fit call
+    int64_t off;                                    // its rows and class indices in the two lists
+    int32_t n;
+    int32_t slot;                                   // which block of the decision workspace a scored step fills, else -1
+    int32_t next_scored;                            // the next scored step after this one, or the step count
+    uint32_t seed[kMaxClasses];                     // the shuffle seed of every class problem
+};
+constexpr int32_t kNoFail = 0x7f7f7f7f;             // the failure word as hipMemsetAsync leaves it: no step has failed
+
+// One workgroup per class problem, alive for all the steps: the weights stay where k_sgd keeps them, every step is one epoch of
+// sgd_epoch from what the last step left, followed by the intercept statements of _fit_binary / _fit_multiclass (SI, AI, A: see
+// include/radarml.h) and, for a scored step, this class's decision value of every held-out row.  The workgroups exchange nothing
+// but the failure word: a problem whose weights go non-finite at step s lowers it to s with an integer atomic, and the others read
+// it (one lane, an agent-scope atomic load) before every step and stop before a step later than it.
+template <int EPT, bool L1, bool AVG>
+__global__ __launch_bounds__(kThreads) void k_sgd_online(const SgdDev* __restrict__ probs, const StepDev* __restrict__ steps, int n_steps,
+                                                         const int32_t* __restrict__ rows, const int32_t* __restrict__ cls, int n_classes,
+                                                         const float* __restrict__ X, int64_t N, int64_t D, int64_t ld,
+                                                         const int32_t* __restrict__ test_rows, int n_test,
+                                                         double* __restrict__ intercept_out, double* __restrict__ avg_intercept_out,
+                                                         double* __restrict__ t_out, int32_t* __restrict__ status_out,
+                                                         const int32_t* __restrict__ avg_flag, int32_t* fail,
+                                                         int32_t* __restrict__ avg_flag_out, double* __restrict__ decws) {
+    __shared__ int32_t perm[kMaxRows];
+    __shared__ double red[2][kWaves];
+    __shared__ int flag[2];
+    __shared__ int32_t seen;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int kp = blockIdx.x;
+    const SgdDev P = probs[kp];
+    const int pos_class = n_classes == 2 ? 1 : kp;
+    const int n_dec = n_classes == 2 ? 1 : n_classes;
+    const int nk = EPT ? EPT : (int)((D + kThreads - 1) / kThreads);
+
+    // ---- every row index of every step and of the held-out rows checked before anything is written ----
+    if (tid < 2) flag[tid] = 0;
+    __syncthreads();
+    int bad = 0;
+    for (int s = 0; s < n_steps; ++s) {
+        const int64_t off = steps[s].off;
+        const int n = steps[s].n;
+        for (int i = tid; i < n; i += kThreads) {
+            const int64_t r = rows[off + i];
+            if (r < 0 || r >= N) bad = 1;
+        }
+    }
+    for (int i = tid; i < n_test; i += kThreads) {
+        const int64_t r = test_rows[i];
+        if (r < 0 || r >= N) bad = 1;
+    }
+    if (bad) flag[0] = 1;
+    __syncthreads();
+    if (flag[0]) {
+        if (tid == 0) status_out[P.out] = -1;
+        return;
+    }
+
+    SgdState<EPT> S;
+    S.w.bind(P.ws, tid); S.q.bind(P.ws + D, tid); S.aw.bind(P.ws + 2 * D, tid);
+#pragma unroll
+    for (int k = 0; k < nk; ++k) {
+        const int64_t e = tid + (int64_t)k * kThreads;
+        const bool in = e < D;
+        if (EPT || in) {
+            S.w.set(k, P.warm && in ? P.coef[e] : 0.0);
+            if (AVG) S.aw.set(k, P.warm && in ? P.avg_coef[e] : 0.0);
+        }
+    }
+    double SI = P.warm ? intercept_out[P.out] : 0.0;
+    double AI = P.warm && AVG ? avg_intercept_out[P.out] : 0.0;
+    bool A = P.warm && AVG && *avg_flag != 0;
+    S.t = P.t0;
+    const double l1_ratio = P.penalty == RML_SGD_L2 ? 0.0 : (P.penalty == RML_SGD_L1 ? 1.0 : P.l1_ratio);
+    int buf = 0, status = 1;
+
+    for (int s = 0; s < n_steps; ++s) {
+        const int64_t off = steps[s].off;
+        const int n = steps[s].n, slot = steps[s].slot;
+        if (tid == 0) seen = __hip_atomic_load(fail, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        for (int i = tid; i < n; i += kThreads) perm[i] = i;       // a fresh _plain_sgd call: the index array 0 .. n-1
+        __syncthreads();                                            // (every read of the last step lies before its last barrier)
+        if (seen < s) break;                                        // another problem of the estimator failed at an earlier step
+        if (P.shuffle) {
+            if (tid == 0) fisher_yates(steps[s].seed[kp], n, perm);
+            __syncthreads();
+        }
+        if (L1) {
+#pragma unroll
+            for (int k = 0; k < nk; ++k)
+                if (EPT || tid + (int64_t)k * kThreads < D) S.q.set(k, 0.0);
+        }
+        S.intercept = SI; S.avg_intercept = AI;
+        S.wscale = 1.0; S.average_a = 0.0; S.average_b = 1.0; S.u = 0.0;
+        sgd_epoch<EPT, L1, AVG>(S, P, rows + off, cls + off, pos_class, n, perm, X, D, ld, nk, l1_ratio, red, buf, tid, lane, wave);
+
+        if (sgd_nonfinite(S, nk, tid, D)) flag[1] = 1;
+        __syncthreads();
+        if (flag[1]) {
+            status = 2;
+            if (tid == 0) atomicMin(fail, s);
+            break;
+        }
+        sgd_reset_wscale<EPT, AVG>(S, nk, tid, D);
+
+        // _fit_binary / _fit_multiclass after the solver, on SI, AI and A
+        if (AVG) AI = S.avg_intercept;
+        const bool now = AVG && (double)P.average <= S.t - 1.0;
+        if (n_classes > 2) {
+            if (A) AI = S.intercept; else SI = S.intercept;
+            A = now;
+        } else if (now) {
+            A = true;
+        } else {
+            SI = S.intercept;
+            A = false;
+        }
+
+        if (slot >= 0 && n_test > 0) {                              // coef_[class] . x + intercept_[class] of every held-out row
+            const double icpt = A ? AI : SI;
+            double* __restrict__ out = decws + (int64_t)slot * n_test * n_dec + kp;
+            Row<EPT> xn;
+            sgd_load_row(xn, X, test_rows[0], ld, D, tid);
+            for (int r = 0; r < n_test; ++r) {
+                const float* __restrict__ xrow = X + (int64_t)test_rows[r] * ld;
+                Row<EPT> x = xn;
+                if (r + 1 < n_test) sgd_load_row(xn, X, test_rows[r + 1], ld, D, tid);
+                double sum = 0;
+#pragma unroll
+                for (int k = 0; k < nk; ++k) {
+                    const int64_t e = tid + (int64_t)k * kThreads;
+                    if (e < D) {
+                        double xv;
+                        if constexpr (EPT > 0) xv = (double)x.v[k]; else xv = (double)xrow[e];
+                        double c = S.w.get(k);
+                        if constexpr (AVG) c = A ? S.aw.get(k) : c;
+                        sum += c * xv;
+                    }
+                }
+                double d = block_sum(sum, red, buf, lane, wave);
+                d = d + icpt;
+                if (tid == 0) out[(int64_t)r * n_dec] = d;
+            }
+        }
+    }
+
+    // the weights go to memory once (after a failure: whatever the failed epoch left, as rml_sgd_solve)
+#pragma unroll
+    for (int k = 0; k < nk; ++k) {
+        const int64_t e = tid + (int64_t)k * kThreads;
+        if (e < D) {
+            P.coef[e] = S.w.get(k);
+            if (AVG) P.avg_coef[e] = S.aw.get(k);
+        }
+    }
+    if (tid == 0) {
+        intercept_out[P.out] = SI;
+        if (AVG) avg_intercept_out[P.out] = AI;
+        t_out[P.out] = S.t;
+        status_out[P.out] = status;
+        if (kp == 0) *avg_flag_out = A ? 1 : 0;     // k_sgd_online_finish hands it on: a late workgroup may still read avg_flag
+    }
+}
+
+// After k_sgd_online, one workgroup per step: the labels of a scored step from the decision values the class workgroups left, and
+// the count of correct ones (an integer sum through LDS); -1 for a step that was not scored or not reached.  The last scored step
+// also leaves its labels and decision values in the call's outputs.
+constexpr int kFinishThreads = 256;
+__global__ __launch_bounds__(kFinishThreads) void k_sgd_online_finish(const StepDev* __restrict__ steps, int n_steps, int n_classes,
+                                                                      const int32_t* __restrict__ test_y, int n_test,
+                                                                      const double* __restrict__ decws, const int32_t* __restrict__ status0,
+                                                                      const int32_t* __restrict__ fail, const int32_t* __restrict__ avg_flag_new,
+                                                                      int32_t* __restrict__ avg_flag, int32_t* __restrict__ fail_step,
+                                                                      int32_t* __restrict__ correct, int32_t* __restrict__ labels,
+                                                                      double* __restrict__ dec) {
+    __shared__ int32_t count;
+    if (*status0 == -1) return;                                     // a row outside the matrix: every output stays as it was
+    const int s = blockIdx.x, tid = threadIdx.x;
+    const int32_t failed = *fail;
+    const int reached = failed < n_steps ? failed : n_steps;        // the steps 0 .. reached-1 were run by every problem
+    if (s == 0 && tid == 0) {
+        *fail_step = failed < n_steps ? failed : -1;
+        *avg_flag = *avg_flag_new;
+    }
+    const StepDev st = steps[s];
+    if (st.slot < 0 || s >= reached) {
+        if (tid == 0) correct[s] = -1;
+        return;
+    }
+    if (tid == 0) count = 0;
+    __syncthreads();
+    const int n_dec = n_classes == 2 ? 1 : n_classes;
+    const bool last = st.next_scored >= reached;
+    const double* __restrict__ dv = decws + (int64_t)st.slot * n_test * n_dec;
+    int mine = 0;
+    for (int r = tid; r < n_test; r += kFinishThreads) {
+        int best = 0;
+        double bestv = dv[(int64_t)r * n_dec];
+        for (int c = 1; c < n_dec; ++c) {
+            const double d = dv[(int64_t)r * n_dec + c];
+            if (d > bestv) { bestv = d; best = c; }
+        }
+        const int label = n_classes == 2 ? (bestv > 0 ? 1 : 0) : best;
+        mine += label == test_y[r];
+        if (last) {
+            labels[r] = label;
+            for (int c = 0; c < n_dec; ++c) dec[(int64_t)r * n_dec + c] = dv[(int64_t)r * n_dec + c];
+        }
+    }
+    if (mine) atomicAdd(&count, mine);
+    __syncthreads();
+    if (tid == 0) correct[s] = count;
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------------------
@@ -432,6 +672,23 @@ sgd_kernel pick(int ept, bool l1, bool avg) {
         case 4: return pick_flags<4>(l1, avg);
         case 10: return pick_flags<10>(l1, avg);
         default: return pick_flags<0>(l1, avg);
+    }
+}
+
+typedef void (*sgd_online_kernel)(const SgdDev*, const StepDev*, int, const int32_t*, const int32_t*, int, const float*, int64_t, int64_t,
+                                  int64_t, const int32_t*, int, double*, double*, double*, int32_t*, const int32_t*, int32_t*, int32_t*, double*);
+template <int EPT>
+sgd_online_kernel pick_online_flags(bool l1, bool avg) {
+    return l1 ? (avg ? k_sgd_online<EPT, true, true> : k_sgd_online<EPT, true, false>)
+              : (avg ? k_sgd_online<EPT, false, true> : k_sgd_online<EPT, false, false>);
+}
+sgd_online_kernel pick_online(int ept, bool l1, bool avg) {
+    switch (ept) {
+        case 1: return pick_online_flags<1>(l1, avg);
+        case 2: return pick_online_flags<2>(l1, avg);
+        case 4: return pick_online_flags<4>(l1, avg);
+        case 10: return pick_online_flags<10>(l1, avg);
+        default: return pick_online_flags<0>(l1, avg);
     }
 }
 
@@ -555,5 +812,97 @@ extern "C" int rml_sgd_score(rml_ctx* ctx, const float* X, int64_t N, int64_t D,
                            intercept, avg_intercept, t, correct);
         RML_HIP(hipGetLastError());
     }
+    return RML_OK;
+}
+
+extern "C" int rml_sgd_online(rml_ctx* ctx, const float* X, int64_t N, int64_t D, int64_t ld, const rml_sgd_problem* probs, int n_classes,
+                              const rml_sgd_step* steps, int64_t n_steps, const int32_t* rows, const int32_t* cls, int64_t n_rows_total,
+                              const int32_t* test_rows, const int32_t* test_y, int64_t n_test, int64_t n_out, double* coef, double* avg_coef,
+                              double* intercept, double* avg_intercept, double* t, int32_t* avg_flag, int32_t* status, int32_t* fail_step,
+                              int32_t* correct, int32_t* labels, double* dec, void* stream) {
+    RML_REQUIRE(ctx && (steps || n_steps == 0), RML_ERR_INVALID, "rml_sgd_online: NULL argument");
+    if (n_steps == 0) return RML_OK;
+    RML_REQUIRE(X && probs && rows && cls && coef && avg_coef && intercept && avg_intercept && t && avg_flag && status && fail_step && correct,
+                RML_ERR_INVALID, "rml_sgd_online: NULL argument");
+    RML_REQUIRE(n_classes >= 2 && n_classes <= kMaxClasses, RML_ERR_INVALID, "rml_sgd_online: n_classes=%d outside [2, %d]", n_classes,
+                kMaxClasses);
+    RML_REQUIRE(n_steps > 0 && n_steps < ((int64_t)1 << 24) && n_test >= 0 && n_test < ((int64_t)1 << 24), RML_ERR_INVALID,
+                "rml_sgd_online: bad counts");
+    RML_REQUIRE(n_test == 0 || (test_rows && test_y && labels && dec), RML_ERR_INVALID, "rml_sgd_online: NULL argument");
+    const int K = n_classes == 2 ? 1 : n_classes;
+    // the descriptors checked as rml_sgd_solve checks them, with the fields a partial_fit call does not have set to what it is
+    rml_sgd_problem pr[kMaxClasses];
+    for (int k = 0; k < K; ++k) {
+        pr[k] = probs[k];
+        pr[k].n = 1; pr[k].rows_off = 0; pr[k].y_off = 0; pr[k].max_iter = 1; pr[k].n_iter_no_change = 1; pr[k].tol = -INFINITY;
+    }
+    int rc = check_problems("rml_sgd_online", N, D, ld, pr, K, 1, 1, n_out);
+    if (rc) return rc;
+    for (int k = 1; k < K; ++k) {
+        RML_REQUIRE(pr[k].penalty == pr[0].penalty && pr[k].average == pr[0].average && pr[k].t0 == pr[0].t0 && pr[k].warm == pr[0].warm,
+                    RML_ERR_INVALID, "rml_sgd_online: problem %d: the class problems of one estimator share penalty, average, t0 and warm", k);
+        for (int j = 0; j < k; ++j)
+            RML_REQUIRE(pr[k].out != pr[j].out, RML_ERR_INVALID, "rml_sgd_online: problems %d and %d share output slot %lld", j, k,
+                        (long long)pr[k].out);
+    }
+    int64_t n_scored = 0;
+    for (int64_t s = 0; s < n_steps; ++s) {
+        const rml_sgd_step& st = steps[s];
+        RML_REQUIRE(st.n >= 1 && st.n <= kMaxRows, RML_ERR_INVALID, "rml_sgd_online: step %lld: n=%d outside [1, %d]", (long long)s, st.n,
+                    kMaxRows);
+        RML_REQUIRE(st.off >= 0 && st.off + st.n <= n_rows_total, RML_ERR_INVALID, "rml_sgd_online: step %lld: rows [%lld, +%d) outside the "
+                    "%lld given", (long long)s, (long long)st.off, st.n, (long long)n_rows_total);
+        if (st.score && n_test > 0) ++n_scored;
+    }
+    RML_HIP(hipSetDevice(ctx->device));
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    rml_ctx_guard guard(ctx, st);
+    const int ept = ept_of(D, ctx->opt.sgd_resident_d);
+    const int n_dec = n_classes == 2 ? 1 : n_classes;
+    // workspace: the failure word and the new flag (one 16-byte block, set before every call) | descriptors | steps |
+    // the state of the workspace variant | the decision values of every scored step
+    const size_t word_bytes = 16, dev_bytes = align16((size_t)K * sizeof(SgdDev)), step_bytes = align16((size_t)n_steps * sizeof(StepDev));
+    const size_t state = ept ? 0 : align16((size_t)D * 3 * sizeof(double));
+    const size_t dec_bytes = align16((size_t)n_scored * (size_t)n_test * n_dec * sizeof(double));
+    void* ws = nullptr;
+    rc = rml_ws_reserve(ctx, word_bytes + dev_bytes + step_bytes + state * (size_t)K + dec_bytes, &ws, st);
+    if (rc) return rc;
+    unsigned char* wsb = static_cast<unsigned char*>(ws);
+    void* stage = nullptr;
+    rc = rml_stage_reserve(ctx, dev_bytes + step_bytes, &stage);
+    if (rc) return rc;
+    SgdDev* dev = static_cast<SgdDev*>(stage);
+    for (int k = 0; k < K; ++k) {
+        dev[k] = to_dev(pr[k], D, nullptr, nullptr, coef, avg_coef);
+        if (!ept) dev[k].ws = reinterpret_cast<double*>(wsb + word_bytes + dev_bytes + step_bytes + state * (size_t)k);
+    }
+    StepDev* sd = reinterpret_cast<StepDev*>(static_cast<unsigned char*>(stage) + dev_bytes);
+    int32_t slot = 0;
+    for (int64_t s = 0; s < n_steps; ++s) {
+        sd[s].off = steps[s].off;
+        sd[s].n = steps[s].n;
+        sd[s].slot = steps[s].score && n_test > 0 ? slot++ : -1;
+        for (int k = 0; k < kMaxClasses; ++k) sd[s].seed[k] = steps[s].seed[k];
+    }
+    int32_t next = (int32_t)n_steps;
+    for (int64_t s = n_steps - 1; s >= 0; --s) {
+        sd[s].next_scored = next;
+        if (sd[s].slot >= 0) next = (int32_t)s;
+    }
+    RML_HIP(hipMemsetAsync(wsb, 0x7f, word_bytes, st));
+    rc = rml_stage_upload(ctx, wsb + word_bytes, dev_bytes + step_bytes, st);
+    if (rc) return rc;
+    int32_t* fail = reinterpret_cast<int32_t*>(wsb);
+    int32_t* flag_new = fail + 1;
+    const SgdDev* dprobs = reinterpret_cast<const SgdDev*>(wsb + word_bytes);
+    const StepDev* dsteps = reinterpret_cast<const StepDev*>(wsb + word_bytes + dev_bytes);
+    double* decws = reinterpret_cast<double*>(wsb + word_bytes + dev_bytes + step_bytes + state * (size_t)K);
+    hipLaunchKernelGGL(pick_online(ept, pr[0].penalty != RML_SGD_L2, pr[0].average > 0), dim3((unsigned)K), dim3(kThreads), 0, st, dprobs, dsteps,
+                       (int)n_steps, rows, cls, n_classes, X, N, D, ld, test_rows, (int)n_test, intercept, avg_intercept, t, status, avg_flag,
+                       fail, flag_new, decws);
+    RML_HIP(hipGetLastError());
+    hipLaunchKernelGGL(k_sgd_online_finish, dim3((unsigned)n_steps), dim3(kFinishThreads), 0, st, dsteps, (int)n_steps, n_classes, test_y,
+                       (int)n_test, decws, status + pr[0].out, fail, flag_new, avg_flag, fail_step, correct, labels, dec);
+    RML_HIP(hipGetLastError());
     return RML_OK;
 }

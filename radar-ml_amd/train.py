@@ -1027,25 +1027,7 @@ def partial_fit_sgd(estimator, X, y, classes=None, device=None):
     X32 = _rows(X)
     y = _check_y(X32, y)
     est = estimator
-    if not hasattr(est, "classes_"):
-        if est.class_weight == "balanced":
-            raise ValueError("class_weight 'balanced' is not supported for partial_fit. In order to use 'balanced' weights, use "
-                             "compute_class_weight('balanced', classes=classes, y=y).")
-        if classes is None:
-            raise ValueError("classes must be passed on the first call to partial_fit.")
-        est.classes_ = np.unique(np.asarray(classes))
-        if not 2 <= len(est.classes_) <= 8:
-            raise ValueError("%s takes 2..8 classes, got %d" % (who, len(est.classes_)))
-        est.n_features_in_ = X32.shape[1]
-    elif classes is not None and not np.array_equal(est.classes_, np.unique(np.asarray(classes))):
-        raise ValueError("`classes=%r` is not the same as on last call to partial_fit, was: %r" % (classes, est.classes_))
-    if getattr(est, "coef_", None) is None:
-        est._allocate_parameter_mem(n_classes=len(est.classes_), n_features=X32.shape[1], input_dtype=np.float64)
-    elif X32.shape[1] != est.coef_.shape[-1]:
-        raise ValueError("Number of features %d does not match previous data %d." % (X32.shape[1], est.coef_.shape[-1]))
-    est._loss_function_ = est._get_loss_function(est.loss)
-    if not hasattr(est, "t_"):
-        est.t_ = 1.0
+    _sgd_partial_prepare(est, X32.shape[1], classes, who)
     return _sgd_run(est, y, 1, lambda plan: _sgd(X32, plan, device), who)
 
 
@@ -1231,3 +1213,508 @@ def find_best_sgd_svm_estimator(X, y, cv, random_seed, device=None):
     logger.info('\n Best hyperparameters:')
     logger.info(grid_search.best_params_)
     return grid_search.best_estimator_
+
+
+# ---- the online loop of train.py:409-438: a chain of partial_fit calls resident on the device (rml_sgd_online) -----------------
+# rml_sgd_step of include/radarml.h
+SGD_STEP = np.dtype([("off", "<i8"), ("n", "<i4"), ("score", "<i4"), ("seed", "<u4", (8,))])
+RANDOM_SEED = 1234                      # train.py:32
+
+
+def sgd_online_device(Xd, plan, device=None, check=True, fill=None):
+    """``rml_sgd_online`` on the DEVICE rows ``Xd`` (as ``sgd_device`` takes them) for ``plan``: a dict of ``problems`` (K SGD_PROBLEM
+    records of one estimator, class order; K = 1 for two classes), ``n_classes``, ``steps`` (SGD_STEP records), ``rows`` / ``cls``
+    (int32: the steps' rows and their class indices), ``test_rows`` / ``test_y`` (int32, optional), ``init`` (host ``coef`` /
+    ``avg_coef`` (K, D), ``intercept`` / ``avg_intercept`` (K): the state of problem k, stored at its slot), ``avg_flag`` and
+    optionally ``n_out`` (output slots, default K).  Returns host arrays per PROBLEM ``coef``, ``avg_coef``, ``intercept``,
+    ``avg_intercept``, ``t``, ``status``, and ``avg_flag``, ``fail_step``, ``correct`` (per step), ``labels`` / ``dec`` (of the last
+    scored step).  Two uploads, one call, two copies back: the only wait is for those.  A row outside the matrix raises
+    RadarMLError (``check=False``: status -1 is returned).  ``fill``: what the outputs without an initial value hold before the
+    call (default 0)."""
+    import torch
+    lib = _lib.load()
+    dev = _lib.device_of(device if device is not None else Xd.device)
+    ctx = _lib.context(dev)
+    probs = np.ascontiguousarray(plan["problems"], dtype=SGD_PROBLEM)
+    steps = np.ascontiguousarray(plan["steps"], dtype=SGD_STEP)
+    if Xd.dtype != torch.float32 or Xd.dim() != 2 or Xd.stride(1) != 1 or Xd.stride(0) < Xd.shape[1]:
+        raise ValueError("sgd_online_device: the rows are an (N, D) float32 tensor with unit column stride")
+    N, D, ld = int(Xd.shape[0]), int(Xd.shape[1]), int(Xd.stride(0))
+    C = int(plan["n_classes"])
+    K, n_dec, S = len(probs), (1 if C == 2 else C), len(steps)
+    if K != n_dec:
+        raise ValueError("sgd_online_device: %d problems for %d classes" % (K, C))
+    n_out = int(plan.get("n_out", K))
+    out = probs["out"].astype(np.int64)
+    if ((out < 0) | (out >= n_out)).any():
+        raise ValueError("sgd_online_device: an output slot outside [0, %d)" % n_out)
+    i32 = lambda a: np.ascontiguousarray(a, dtype=np.int32).ravel()
+    rows, cls = i32(plan["rows"]), i32(plan["cls"])
+    te_rows, te_y = i32(plan.get("test_rows", [])), i32(plan.get("test_y", []))
+    n_test = len(te_rows)
+    init = plan["init"]
+    fill = 0 if fill is None else fill
+    # one float64 and one int32 block hold every in / out array: [coef | avg_coef | intercept | avg_intercept | t | dec] and
+    # [status | avg_flag | fail_step | correct | labels | rows | cls | test_rows | test_y]
+    f_off = np.cumsum([0, n_out * D, n_out * D, n_out, n_out, n_out, max(n_test * n_dec, 1)])
+    hf = np.full(int(f_off[-1]), float(fill))
+    for name, j, width in (("coef", 0, D), ("avg_coef", 1, D), ("intercept", 2, 1), ("avg_intercept", 3, 1)):
+        hf[f_off[j]:f_off[j + 1]].reshape(n_out, width)[out] = np.asarray(init[name], dtype=np.float64).reshape(K, width)
+    i_off = np.cumsum([0, n_out, 1, 1, max(S, 1), max(n_test, 1), max(len(rows), 1), max(len(cls), 1), max(n_test, 1), max(n_test, 1)])
+    hi = np.full(int(i_off[-1]), int(fill), dtype=np.int32)
+    hi[i_off[1]] = int(bool(plan.get("avg_flag", False)))
+    for j, a in ((5, rows), (6, cls), (7, te_rows), (8, te_y)):
+        hi[i_off[j]:i_off[j] + len(a)] = a
+    with torch.cuda.device(dev):
+        df, di = torch.from_numpy(hf).to(dev), torch.from_numpy(hi).to(dev)
+        fp = lambda j: _lib.ptr(df[int(f_off[j]):])
+        ip = lambda j: _lib.ptr(di[int(i_off[j]):])
+        _lib.check(lib.rml_sgd_online(ctx, _lib.ptr(Xd), N, D, ld, probs.ctypes.data, C, steps.ctypes.data, S, ip(5), ip(6), len(rows),
+                                      ip(7), ip(8), n_test, n_out, fp(0), fp(1), fp(2), fp(3), fp(4), ip(1), ip(0), ip(2), ip(3), ip(4), fp(5),
+                                      _lib.stream_ptr(dev)), "rml_sgd_online")
+        rf, ri = df.cpu().numpy(), di[:int(i_off[5])].cpu().numpy()
+    f = lambda j, width: rf[f_off[j]:f_off[j + 1]].reshape(n_out, width)[out]
+    res = {"coef": f(0, D), "avg_coef": f(1, D), "intercept": f(2, 1)[:, 0], "avg_intercept": f(3, 1)[:, 0], "t": f(4, 1)[:, 0],
+           "status": ri[:n_out][out], "avg_flag": bool(ri[i_off[1]]), "fail_step": int(ri[i_off[2]]), "correct": ri[i_off[3]:i_off[3] + S],
+           "labels": ri[i_off[4]:i_off[4] + n_test], "dec": rf[f_off[5]:f_off[5] + n_test * n_dec].reshape(n_test, n_dec)}
+    if check and (res["status"] < 0).any():
+        raise _lib.RadarMLError("rml_sgd_online: a step or the held-out list names a row outside the matrix")
+    return res
+
+
+def _sgd_online(X, plan, device=None):
+    """The rows ``X`` (float32 host rows, uploaded ONCE, or a CUDA tensor taken where it is) and the whole chain of partial_fit steps
+    of ``plan`` in one ``rml_sgd_online`` call (``sgd_online_device``).
+
+    All device work of ``partial_fit_sgd_steps`` goes through this function (tests replace it to run the logic without a GPU)."""
+    import torch
+    dev = _lib.device_of(device if device is not None or not isinstance(X, torch.Tensor) else X.device)
+    with torch.cuda.device(dev):
+        Xd = X.to(dev) if isinstance(X, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(X, dtype=np.float32)).to(dev)
+        return sgd_online_device(Xd, plan, dev)
+
+
+def _sgd_partial_prepare(est, n_features, classes, who):
+    """What ``SGDClassifier.partial_fit`` does to the estimator before its solver runs (sk:583-631)."""
+    if est.class_weight == "balanced" and not hasattr(est, "classes_"):
+        raise ValueError("class_weight 'balanced' is not supported for partial_fit. In order to use 'balanced' weights, use "
+                         "compute_class_weight('balanced', classes=classes, y=y).")
+    if not hasattr(est, "classes_"):
+        if classes is None:
+            raise ValueError("classes must be passed on the first call to partial_fit.")
+        est.classes_ = np.unique(np.asarray(classes))
+        if not 2 <= len(est.classes_) <= 8:
+            raise ValueError("%s takes 2..8 classes, got %d" % (who, len(est.classes_)))
+        est.n_features_in_ = n_features
+    elif classes is not None and not np.array_equal(est.classes_, np.unique(np.asarray(classes))):
+        raise ValueError("`classes=%r` is not the same as on last call to partial_fit, was: %r" % (classes, est.classes_))
+    if getattr(est, "coef_", None) is None:
+        est._allocate_parameter_mem(n_classes=len(est.classes_), n_features=n_features, input_dtype=np.float64)
+    elif n_features != est.coef_.shape[-1]:
+        raise ValueError("Number of features %d does not match previous data %d." % (n_features, est.coef_.shape[-1]))
+    est._loss_function_ = est._get_loss_function(est.loss)
+    if not hasattr(est, "t_"):
+        est.t_ = 1.0
+
+
+def partial_fit_sgd_steps(estimator, X, y, steps, classes=None, test=None, score_every=1, device=None):
+    """The chain ``for rows in steps: estimator.partial_fit(X[rows], y[rows], classes)`` of train.py:409-416 and 425-438 on the GPU
+    as ONE ``rml_sgd_online`` call: the rows go up at most once, the weights never leave the chip between the steps, and the only
+    wait is for the results.  ``X``: host rows or a CUDA float32 tensor; ``y``: the labels of all its rows; ``steps``: a sequence of
+    row-index arrays (1 .. 8 192 rows each), one partial_fit call each, in the order the call would see its rows.
+    ``test=(row indices, labels)``: held-out rows of ``X`` that are predicted after every ``score_every``-th step (the steps
+    ``score_every - 1``, ``2 score_every - 1``, ..).  Returns ``(estimator, accuracies)``: the estimator as the chain of
+    ``partial_fit_sgd`` calls leaves it (a genuine ``SGDClassifier``: ``t_``, ``n_iter_ == 1``, the four weight arrays, ``coef_`` /
+    ``intercept_`` aliased as scikit-learn aliases them) and per step the accuracy on the held-out rows (NaN where the step was
+    not scored).  The estimator, its restrictions and its errors are ``partial_fit_sgd``'s; where scikit-learn would raise its
+    overflow ``ValueError`` in some step, this raises it after the call and leaves the estimator as it was before the call."""
+    from sklearn.utils.class_weight import compute_class_weight
+    who = "partial_fit_sgd_steps"
+    est = estimator
+    _sgd_prepare(est, who)
+    try:
+        import torch
+        on_device = isinstance(X, torch.Tensor) and X.is_cuda
+    except ImportError:   # pragma: no cover - torch is part of the image
+        on_device = False
+    if on_device:
+        if X.dim() != 2 or X.dtype != torch.float32:
+            raise ValueError("%s: device rows are an (N, D) float32 tensor" % who)
+        rows_of = X
+    else:
+        rows_of = _rows(X)
+    y = _check_y(rows_of, y)
+    N, D = int(rows_of.shape[0]), int(rows_of.shape[1])
+    if est.class_weight == "balanced":
+        raise ValueError("class_weight 'balanced' is not supported for partial_fit. In order to use 'balanced' weights, use "
+                         "compute_class_weight('balanced', classes=classes, y=y).")
+    _sgd_partial_prepare(est, D, classes, who)
+    prm = _sgd_params(est.get_params(), who)
+    steps = [np.asarray(s, dtype=np.int64).ravel() for s in steps]
+    if not steps:
+        return est, np.zeros(0)
+    for s, rr in enumerate(steps):
+        if len(rr) < 1:
+            raise ValueError("%s: step %d has no rows" % (who, s))
+        _sgd_check_rows(who, len(rr))
+        if rr.min() < 0 or rr.max() >= N:
+            raise IndexError("%s: step %d names a row outside the %d rows" % (who, s, N))
+    classes_ = est.classes_
+    nc = len(classes_)
+
+    def class_index(lab, strict):
+        idx = np.searchsorted(classes_, lab)
+        miss = (idx >= nc) | (classes_[np.minimum(idx, nc - 1)] != lab)
+        if strict and miss.any():
+            raise ValueError("%s: y holds labels outside classes_ %r" % (who, classes_))
+        return np.where(miss, -1, idx).astype(np.int32)
+
+    used = np.unique(np.concatenate(steps))
+    yi = np.full(N, -1, dtype=np.int32)
+    yi[used] = class_index(y[used], True)
+    est._expanded_class_weight = compute_class_weight(est.class_weight, classes=classes_, y=y[steps[-1]])
+    positives = [1] if nc == 2 else list(range(nc))
+    K = len(positives)
+    avg = prm["average"] > 0
+    score_every = int(score_every)
+    if score_every < 1:
+        raise ValueError("%s: score_every must be >= 1" % who)
+    if test is not None:
+        te_rows = np.asarray(test[0], dtype=np.int64).ravel()
+        te_y = class_index(np.asarray(test[1]).ravel(), False)
+        if len(te_rows) != len(te_y) or len(te_rows) < 1:
+            raise ValueError("%s: test is (row indices, labels) of equal, non-zero length" % who)
+    else:
+        te_rows, te_y = np.zeros(0, np.int64), np.zeros(0, np.int32)
+    # the shuffle seeds, drawn per call as scikit-learn draws them (the same every call for an integer random_state)
+    fixed = _sgd_seeds(est.random_state, nc) if isinstance(est.random_state, (int, np.integer)) else None
+    rec = np.zeros(len(steps), dtype=SGD_STEP)
+    off, offs = 0, {}
+    row_parts = []
+    for s, rr in enumerate(steps):
+        key = rr.tobytes()
+        if key not in offs:                     # identical steps (the online_learn chain) share one range of the list
+            offs[key] = off
+            row_parts.append(rr)
+            off += len(rr)
+        rec[s]["off"], rec[s]["n"] = offs[key], len(rr)
+        rec[s]["score"] = int(test is not None and (s + 1) % score_every == 0)
+        rec[s]["seed"][:K] = fixed if fixed is not None else _sgd_seeds(est.random_state, nc)
+    rows = np.concatenate(row_parts)
+
+    def state(c):                       # _prepare_fit_binary (sk:348-365): views of the estimator's arrays
+        j = 0 if nc == 2 else c
+        if avg:
+            return est._standard_coef.reshape(K, -1)[j], est._standard_intercept, est._average_coef.reshape(K, -1)[j], est._average_intercept, j
+        return est.coef_.reshape(K, -1)[j], est.intercept_, None, None, j
+
+    init = {"coef": np.zeros((K, D)), "avg_coef": np.zeros((K, D)), "intercept": np.zeros(K), "avg_intercept": np.zeros(K)}
+    problems = []
+    for k, c in enumerate(positives):
+        coef, icpt, acoef, aicpt, j = state(c)
+        init["coef"][k], init["intercept"][k] = coef, icpt[j]
+        if avg:
+            init["avg_coef"][k], init["avg_intercept"][k] = acoef, aicpt[j]
+        wpos = est._expanded_class_weight[c]
+        wneg = est._expanded_class_weight[0] if nc == 2 else 1.0
+        problems.append(_sgd_problem(prm, 1, 0, 0, 0, k, wpos, wneg, t0=float(est.t_), warm=1, max_iter=1))
+    plan = {"problems": np.array(problems, dtype=SGD_PROBLEM), "n_classes": nc, "steps": rec, "rows": rows.astype(np.int32),
+            "cls": yi[rows], "test_rows": te_rows.astype(np.int32), "test_y": te_y, "init": init,
+            "avg_flag": bool(avg and est.intercept_ is est._average_intercept)}
+    out = _sgd_online(rows_of, plan, device)
+    if (out["status"] == 2).any():
+        raise ValueError(_SGD_OVERFLOW % 1)
+    for k, c in enumerate(positives):
+        coef, icpt, acoef, aicpt, j = state(c)
+        coef[:] = out["coef"][k]
+        if avg:
+            acoef[:] = out["avg_coef"][k]
+            aicpt[j] = out["avg_intercept"][k]
+    SI = np.array(out["intercept"], dtype=np.float64)
+    est.t_ = float(out["t"].max())
+    est.n_iter_ = 1
+    if avg:
+        # the standard intercept in an array of its own, as _fit_binary / _fit_multiclass leave it once averaging has begun
+        if est._standard_intercept is est._average_intercept:
+            est._standard_intercept = SI
+        else:
+            est._standard_intercept[:] = SI
+        if out["avg_flag"]:
+            est.coef_ = est._average_coef.reshape(1, -1) if nc == 2 else est._average_coef
+            est.intercept_ = est._average_intercept
+        else:
+            est.coef_ = est._standard_coef.reshape(1, -1) if nc == 2 else est._standard_coef
+            est.intercept_ = est._standard_intercept
+    else:
+        est.coef_ = est.coef_.reshape(K, -1)
+        if nc == 2:
+            est.intercept_ = np.atleast_1d(SI[0])
+        else:
+            est.intercept_[:] = SI
+    acc = np.full(len(steps), np.nan)
+    scored = out["correct"] >= 0
+    if len(te_rows):
+        acc[scored] = out["correct"][scored].astype(np.float64) / len(te_rows)
+    return est, acc
+
+
+def balance_indices(labels):
+    """The index form of ``balance_classes``: the positions it takes its balanced set from, in its order, or None where the
+    labels are balanced already (it then returns its input)."""
+    import collections
+    from sklearn import utils
+    labels = np.asarray(labels)
+    mc = collections.Counter(labels.tolist()).most_common()
+    if len(set(c for _, c in mc)) == 1:
+        return None
+    majority = mc[0][1]
+    # utils.resample(a, ...) is a[random_state.randint(0, len(a), n_samples)]: drawing on the index array takes the same rows
+    return np.concatenate([utils.resample(np.nonzero(labels == c)[0], replace=True, n_samples=majority, random_state=RANDOM_SEED)
+                           for c, _ in mc])
+
+
+def balance_classes(labels, data):
+    """Balance classes (train.py:230-274): every class upsampled with replacement to the size of the most frequent one, the classes
+    in ``Counter.most_common`` order, the draws those of ``utils.resample(..., random_state=RANDOM_SEED)`` on the host.  ``data``:
+    host rows (NumPy indexing) or a CUDA tensor (one gather).  Already-balanced input is returned as it is."""
+    idx = balance_indices(labels)
+    if idx is None:
+        return labels, data
+    labels = np.asarray(labels)
+    try:
+        import torch
+        if isinstance(data, torch.Tensor):
+            return labels[idx], data[torch.as_tensor(idx, dtype=torch.long, device=data.device)]
+    except ImportError:   # pragma: no cover - torch is part of the image
+        pass
+    return labels[idx], np.asarray(data)[idx]
+
+
+def _feature_rows(samples, proj_mask, device=None):
+    """``common.process_samples`` at zoom 1 for a list of projection tuples whose planes are host arrays or CUDA tensors (the output
+    of ``DataGenerator.augment_dataset``), to DEVICE rows: the host planes go up in one copy per projection, the device planes are
+    taken where they are, and ``rml_assemble_features`` writes the rows."""
+    import torch
+    from . import common
+    lib = _lib.load()
+    dev = _lib.device_of(device)
+    samples = list(samples)
+    n = len(samples)
+    if n == 0:
+        raise ValueError("no samples")
+    with torch.cuda.device(dev):
+        planes = []
+        for i in range(3):
+            if not proj_mask[i]:
+                planes.append(None)
+                continue
+            shp = tuple(int(v) for v in samples[0][i].shape)
+            if len(shp) != 2 or any(tuple(int(v) for v in s[i].shape) != shp for s in samples):
+                raise ValueError("setting an array element with a sequence: ragged projection shapes")
+            out = torch.empty((n,) + shp, dtype=torch.float32, device=dev)
+            host = [j for j, s in enumerate(samples) if not isinstance(s[i], torch.Tensor)]
+            there = [j for j, s in enumerate(samples) if isinstance(s[i], torch.Tensor)]
+            if host:
+                out[torch.as_tensor(host, device=dev)] = torch.from_numpy(np.stack([np.asarray(samples[j][i], dtype=np.float32)
+                                                                                   for j in host])).to(dev)
+            if there:
+                out[torch.as_tensor(there, device=dev)] = torch.stack([samples[j][i].to(device=dev, dtype=torch.float32) for j in there])
+            planes.append(out)
+        X = planes[0].shape[1] if planes[0] is not None else (planes[2].shape[1] if planes[2] is not None else 1)
+        Z = planes[0].shape[2] if planes[0] is not None else (planes[1].shape[2] if planes[1] is not None else 1)
+        Y = planes[1].shape[1] if planes[1] is not None else (planes[2].shape[2] if planes[2] is not None else 1)
+        for i, want in enumerate([(X, Z), (Y, Z), (X, Y)]):
+            if planes[i] is not None and tuple(planes[i].shape[1:]) != want:
+                raise ValueError("projection shapes are inconsistent: got %s for plane %d, expected %s" % (tuple(planes[i].shape[1:]), i, want))
+        bits = common._mask_bits(proj_mask)
+        D = int(lib.rml_feature_len(X, Y, Z, bits))
+        feat = torch.empty((n, D), dtype=torch.float32, device=dev)
+        _lib.check(lib.rml_assemble_features(_lib.context(dev), _lib.ptr(planes[0]), _lib.ptr(planes[1]), _lib.ptr(planes[2]), n, X, Y, Z,
+                                             0.0, bits, _lib.ptr(feat), D, _lib.stream_ptr(dev)), "rml_assemble_features")
+    return feat
+
+
+def _online_learn_steps(n):
+    """train.py:414: the partial_fit calls of --online_learn over a training set of n rows."""
+    return int(max(np.ceil(10**6 / n), 1000))
+
+
+def _augment_steps(sample_of, labels, n_samples, batch_size):
+    """The partial_fit calls of one augment epoch (train.py:427-438): per slice of ``batch_size`` samples the augmented rows whose
+    sample lies in it, balanced as ``balance_classes`` balances the batch.  ``len(xc) / batch_size`` batches, as train.py:437 counts."""
+    steps = []
+    for b in range(int(np.ceil(n_samples / batch_size))):
+        jobs = np.nonzero(np.asarray(sample_of) // batch_size == b)[0]
+        if len(jobs) == 0:
+            continue
+        idx = balance_indices(labels[jobs])
+        steps.append(jobs if idx is None else jobs[idx])
+    return steps
+
+
+def sgd_fit(train, test, proj_mask, online_learn, svm_model, epochs, folds=5, batch_size=32, device=None):
+    """Fit SVM using SGD on data set (train.py:324-440, the same arguments) with every fit on the GPU.
+
+    The features are made once and balanced; then either the grid search (``find_best_sgd_svm_estimator``) or, for
+    ``online_learn``, the pickled classifier ``svm_model`` (a path or an open file) and its ``max(ceil(1e6 / n), 1000)`` identical
+    partial fits in ONE ``partial_fit_sgd_steps`` call.  Then per augment epoch: one ``DataGenerator.augment_dataset`` call (the
+    draws in the reference's order, batch by batch), one feature pass to device rows, per batch the balanced row list of the
+    augmented samples that come from it, and one ``partial_fit_sgd_steps`` call that predicts ``X_test`` after every step -- one wait
+    per epoch; the per-batch accuracies are logged at debug level afterwards.
+
+    Returns:
+        estimator: Estimator that was chosen by grid search.
+    """
+    import pickle
+    from sklearn import model_selection
+    from .augment import DataGenerator
+    from .svm import from_sklearn
+    X_train, y_train = train
+    X_test, y_test = test
+    y_train, y_test = np.asarray(y_train), np.asarray(y_test)
+    if epochs:
+        xc = list(X_train)
+        yc = y_train.copy()
+    logger.info('Generating feature vectors.')
+    Xd_test = _feature_rows(X_test, proj_mask, device)
+    Xd = _feature_rows(X_train, proj_mask, device)
+    logger.info(f'Feature vector length: {Xd.shape[1]}')
+    logger.info('Balancing classes.')
+    y_bal, Xd = balance_classes(y_train, Xd)
+    if not online_learn:
+        logger.info('Running best fit with new data.')
+        skf = model_selection.StratifiedKFold(n_splits=folds)
+        Xh = Xd.cpu().numpy()
+        clf = find_best_sgd_svm_estimator(Xh, y_bal, list(skf.split(Xh, y_bal)), RANDOM_SEED, device=device)
+    else:
+        logger.info('Running partial fit with new data.')
+        if hasattr(svm_model, "read"):
+            clf = pickle.load(svm_model)
+        else:
+            with open(svm_model, 'rb') as fp:
+                clf = pickle.load(fp)
+        everything = np.arange(len(y_bal))
+        clf, _ = partial_fit_sgd_steps(clf, Xd, y_bal, [everything] * _online_learn_steps(len(y_bal)), device=device)
+    if epochs:
+        logger.info(f'Running partial fit with augmented data (epochs: {epochs}).')
+        if logger.isEnabledFor(logging.DEBUG):
+            y_predicted = from_sklearn(clf).predict(Xd_test)
+            logger.debug(f'Un-augmented accuracy: {float(np.mean(y_predicted == y_test))}.')
+        data_gen = DataGenerator(rotation_range=5.0, zoom_range=0.2, noise_sd=0.1, balance=True, device=device)
+        classes = np.unique(y_bal)
+        for e in range(epochs):
+            logger.debug(f'Augment epoch: {e}.')
+            tuples, labels, sample_of = data_gen.augment_dataset(xc, yc, return_samples=True)
+            Xe = _feature_rows(list(tuples) + list(X_test), proj_mask, device)
+            steps = _augment_steps(sample_of, labels, len(xc), batch_size)
+            held_out = (np.arange(len(labels), len(labels) + len(y_test)), y_test)
+            clf, acc = partial_fit_sgd_steps(clf, Xe, np.concatenate((labels, y_test)), steps, classes=classes, test=held_out,
+                                             device=device)
+            for batch, a in enumerate(acc):
+                logger.debug(f'Augment batch: {batch}.')
+                logger.debug(f'Augmented accuracy: {a}.')
+    return clf
+
+
+def svc_fit(train, proj_mask, epochs, folds=5, batch_size=32, solver="host", refit_solver="host", device=None):
+    """Fit SVM using SVC on data set (train.py:442-545): the training set augmented ``epochs`` times on the GPU (one
+    ``DataGenerator.augment_dataset`` call per epoch; ``batch_size`` only sliced the reference's loop, the draws are the same
+    stream), the 1e-6 scale check, the features to device rows, ``balance_classes`` and ``find_best_svm_estimator``
+    (``solver`` / ``refit_solver`` as there).
+
+    Returns:
+        estimator: Estimator that was chosen by grid search.
+    """
+    import torch
+    from sklearn import model_selection
+    from .augment import DataGenerator
+    X_train, y_train = train
+    X_train = list(X_train)
+    y_train = np.asarray(y_train)
+    if epochs:
+        data_gen = DataGenerator(rotation_range=15.0, zoom_range=0.3, noise_sd=0.2, device=device)
+        logger.info('Augmenting data set.')
+        logger.info(f'Original number of training samples: {y_train.shape[0]}')
+        xc, yc = list(X_train), y_train.copy()
+        y_parts = [y_train]
+        for e in range(epochs):
+            logger.debug(f'epoch: {e}')
+            tuples, labels = data_gen.augment_dataset(xc, yc)
+            X_train.extend(tuples)
+            y_parts.append(labels)
+        # Sanity check if augmentation introduced a scaling problem.
+        top = max(float(p.max()) if isinstance(p, torch.Tensor) else float(np.max(p)) for t in X_train for p in t)
+        assert abs(top - 1.0) < 1e-6, 'scale error'
+        y_train = np.concatenate(y_parts).astype(np.int8)
+        logger.info(f'Augmented number of training samples: {y_train.shape[0]}')
+    logger.info('Generating feature vectors from radar projections.')
+    Xd = _feature_rows(X_train, proj_mask, device)
+    logger.info(f'Feature vector length: {Xd.shape[1]}')
+    logger.info('Balancing classes.')
+    y_train, Xd = balance_classes(y_train, Xd)
+    skf = model_selection.StratifiedKFold(n_splits=folds)
+    logger.info('Finding best classifier.')
+    Xh = Xd.cpu().numpy()
+    return find_best_svm_estimator(Xh, y_train, list(skf.split(Xh, y_train)), RANDOM_SEED, solver=solver, refit_solver=refit_solver)
+
+
+def calibrate_prefit(clf, X_val, y_val):
+    """``CalibratedClassifierCV(clf, cv='prefit').fit(X_val, y_val)`` (train.py:722-724) for a fitted SVC or SGDClassifier: the
+    decision values of the validation rows come from the GPU twin (``from_sklearn(clf).decision_function``), the two-parameter
+    sigmoid fits from scikit-learn's own ``_fit_calibrator`` on the host (some hundred values per class), and the result is a
+    genuine ``CalibratedClassifierCV`` that pickles and that ``from_sklearn`` takes."""
+    from sklearn.calibration import CalibratedClassifierCV, _fit_calibrator
+    from .svm import from_sklearn
+    y_val = np.asarray(y_val)
+    predictions = np.asarray(from_sklearn(clf).decision_function(X_val), dtype=np.float64)
+    if predictions.ndim == 1:
+        predictions = predictions.reshape(-1, 1)
+    if len(predictions) != len(y_val):
+        raise ValueError("Found input variables with inconsistent numbers of samples: [%d, %d]" % (len(predictions), len(y_val)))
+    cal = CalibratedClassifierCV(estimator=clf, cv="prefit")
+    cal.classes_ = clf.classes_
+    cal.calibrated_classifiers_ = [_fit_calibrator(clf, predictions, y_val, cal.classes_, cal.method, None)]
+    if hasattr(clf, "n_features_in_"):
+        cal.n_features_in_ = clf.n_features_in_
+    return cal
+
+
+def evaluate_model(model, X_test, y_test, target_names, cm_name=None):
+    """Generate model confusion matrix and classification report (train.py:215-228): the labels come from the GPU model
+    (``from_sklearn(model)`` unless it is one already), accuracy, confusion matrix and report from ``sklearn.metrics``; the
+    figure of train.py:293-322 is drawn and saved only when ``cm_name`` is given.  Returns (accuracy, confusion matrix, report)."""
+    from sklearn import metrics
+    from .svm import from_sklearn, _Base
+    gpu = model if isinstance(model, _Base) else from_sklearn(model)
+    y_pred = gpu.predict(X_test)
+    acc = metrics.accuracy_score(y_test, y_pred)
+    logger.info(f'Accuracy: {acc}')
+    cm = metrics.confusion_matrix(y_test, y_pred)
+    logger.info(f'Confusion matrix:\n{cm}')
+    if cm_name is not None:
+        import itertools
+        import matplotlib
+        matplotlib.use("Agg", force=False)
+        import matplotlib.pyplot as plt
+        figure = plt.figure(figsize=(8, 8))
+        ax = plt.gca()
+        im = ax.imshow(cm, interpolation='nearest', cmap=plt.cm.Blues)
+        plt.title('Confusion matrix')
+        plt.colorbar(im, fraction=0.046, pad=0.04)
+        tick_marks = np.arange(len(target_names))
+        plt.xticks(tick_marks, target_names, rotation=45)
+        plt.yticks(tick_marks, target_names)
+        norm = np.around(cm.astype('float') / cm.sum(axis=1)[:, np.newaxis], decimals=2)
+        threshold = norm.max() / 2.
+        for i, j in itertools.product(range(norm.shape[0]), range(norm.shape[1])):
+            plt.text(j, i, norm[i, j], horizontalalignment='center', color='white' if norm[i, j] > threshold else 'black')
+        plt.tight_layout()
+        plt.ylabel('True label')
+        plt.xlabel('Predicted label')
+        logger.info(f'Saving confusion matrix plot to: {cm_name}')
+        figure.savefig(cm_name)
+        figure.clf()
+        plt.close(figure)
+    cls_report = metrics.classification_report(y_test, y_pred, target_names=target_names)
+    logger.info(f'Classification report:\n{cls_report}')
+    return acc, cm, cls_report
