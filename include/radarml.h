@@ -651,6 +651,18 @@ int rml_dnn_preprocess_rows(rml_ctx* ctx, const float* rows, int64_t ld, const u
 int rml_dnn_preprocess_volumes(rml_ctx* ctx, const void* V, int vdtype, int64_t B, int X, int Y, int Z, int mode, const int32_t* ijk,
                                uint8_t* codes, int64_t ldq, int32_t* flags, float* rows, int64_t ld, int out_h, int out_w,
                                uint16_t* xz, uint16_t* yz, uint16_t* xy, void* stream);
+/* Target slices -> trunk inputs in ONE launch.  The reference's samples are the three planes of the radar image through one
+ * target's voxel: yz = V[i,:,:], xz = V[:,j,:], xy = V[:,:,k] (predict.py:98-107, ground_truth_samples.py:413-419), and its live loop
+ * classifies every target of every scan that way (predict.py:93-119).  V: B volumes (X, Y, Z), float32 (4-byte aligned) or uint8
+ * (16-byte aligned); ijk: B * T * 3 int32, frame-major (row b * T + t is target t of frame b), negative indices wrap like Python's,
+ * the range is the caller's responsibility (as for rml_project_slices).  The (X + Y) * Z + X * Y voxels of a slice go straight from
+ * the volume into the kernel's LDS image -- float16 images for uint8 volumes, float32 images for float32 volumes (any finite value:
+ * no on-grid test) -- and through the passes of rml_dnn_preprocess_rows: the planes are those of rml_dnn_preprocess_rows on the rows
+ * of rml_project_slices, bit for bit.  Outputs: (B * T, out_h, out_w) bf16, 8-byte aligned.  No scratch, no row flags, no second
+ * stream, no synchronisation; the only allocation is the cached table of a new (grid, output size) pair.  Shapes: those of
+ * rml_dnn_preprocess_supported, others RML_ERR_UNSUPPORTED; T < 1: RML_ERR_INVALID; B == 0: RML_OK. */
+int rml_dnn_preprocess_slices(rml_ctx* ctx, const void* V, int vdtype, int64_t B, int X, int Y, int Z, const int32_t* ijk, int T,
+                              int out_h, int out_w, uint16_t* xz, uint16_t* yz, uint16_t* xy, void* stream);
 /* ---- dnn.py convolutional trunk (dnn.py:45-52,68-76), fused ----------------------------------------------
  * Per branch Conv2D(1->64,3x3,s2,'same',relu) -> Conv2D(64->32,3x3,s2,'same',relu); the three branches concatenated
  * on channels and flattened NHWC: feat[b][(h*(W/4)+w)*96 + branch*32 + n], bf16.  Inputs (B,H,W) already scaled to

@@ -102,6 +102,8 @@ SIGNATURES = {
                                         c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "rml_dnn_preprocess_volumes": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int64,
                                            c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "rml_dnn_preprocess_slices": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int,
+                                          c_void_p, c_void_p, c_void_p, c_void_p]),
     "rml_dnn_trunk": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p,
                               c_void_p, c_void_p, c_void_p]),
     "rml_dnn_trunk_kblock": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p,

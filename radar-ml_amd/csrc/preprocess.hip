@@ -22,85 +22,24 @@
 //    slots: conflict-free; (p - 127.5) / 127.5 is applied to the result (the weights of a window sum to 1);
 //  * vertical pass: a thread produces four adjacent outputs of a row from four ds_read_b128 (the row's weights from a 16-byte record
 //    in LDS) with v_pk_fma_f32 and stores them as one 8-byte piece -- consecutive threads write consecutive bytes.
+// The plan, the device tables, the LDS layout and the two passes live in preprocess_shared.h: k_pre3s (preprocess_slice.hip) stages
+// target slices straight from the volumes into the same image and runs the same passes.
 // Where its time goes, and what was tried on top (matrix-core horizontal pass, projection-by-projection intermediate):
 // tools/exp/README.md, round 4.
 #include "rml_internal.h"
 #include "resize_tables.h"
+#include "preprocess_shared.h"
 #include <type_traits>
 #include <array>
 #include <map>
 #include <mutex>
 
+using namespace rmlpre;         // the plan, the tables, the LDS layout and the two passes: shared with preprocess_slice.hip
+
 namespace {
 
 using rmlresize::AxisTable;
 using rmlresize::precompute;
-
-constexpr int PU = 5;       // 16-element units of a row a thread holds (rows up to 20 480 elements)
-constexpr int VT = 4;       // taps of the vertical pass (Pillow's bicubic window when the height does not shrink)
-
-struct PreArgs {
-    const float* rows; int64_t ld;          // float32 feature rows (k_pre3<false>)
-    const uint8_t* codes; int64_t ldq;      // biased uint8 code rows, byte = code ^ 0x80 (k_pre3<true>)
-    const int32_t* flags;                   // per row: != 0 -> the code row is valid (nullptr: every row)
-    const int32_t* skip_if_set;             // k_pre3<false>: the whole launch is a no-op when *skip_if_set != 0
-    int64_t B;
-    int X, Y, Z, OH, OW;
-    int SZ, TW;                             // LDS row strides in elements: [xz | yz] image, intermediate
-    const int* hz_a0; const float* hz_w;    // Z -> OW: aligned window start per output column, [OW][WZ] weights
-    const int* hy_a0; const float* hy_w;    // Y -> OW: window start, [OW][WY] weights (unshifted)
-    const float* vw; const int* vfirst;     // [2][OH][VT] weights, [2][OH] first rows: table 0 = X -> OH (xz, xy), 1 = Y -> OH (yz)
-    uint16_t* out[3];                       // bf16 (B, OH, OW) per projection
-};
-
-typedef float f32x4u __attribute__((ext_vector_type(4), aligned(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-
-__device__ __forceinline__ uint32_t pk_bf16(float lo, float hi) {     // v_cvt_pk_bf16_f32 (round to nearest even)
-    bf16x2 b = __builtin_convertvector(f32x2{lo, hi}, bf16x2);
-    return *reinterpret_cast<uint32_t*>(&b);
-}
-// LDS-only barrier: __syncthreads() would also wait for the prefetch of the next sample (vmcnt)
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
-// the reference's (p - 127.5) / 127.5 (dnn.py:202-205), applied to the horizontal pass's result: the weights of a window sum to 1
-__device__ __forceinline__ float unit_range(float p) { return fmaf(p, 1.0f / 127.5f, -1.0f); }
-
-// four consecutive image values (8- / 16-byte aligned) as floats
-__device__ __forceinline__ float4 quad(const _Float16* s) {
-    const f16x4 v = *reinterpret_cast<const f16x4*>(s);
-    return make_float4((float)v.x, (float)v.y, (float)v.z, (float)v.w);
-}
-__device__ __forceinline__ float4 quad(const float* s) { return *reinterpret_cast<const float4*>(s); }
-
-template <int WIN, typename T>
-__device__ __forceinline__ float window_dot(const T* s, const float (&w)[WIN]) {
-    float ax = 0.0f, ay = 0.0f, az = 0.0f, aw = 0.0f;
-#pragma unroll
-    for (int q = 0; q < WIN / 4; ++q) {
-        const float4 v = quad(s + 4 * q);
-        ax = fmaf(v.x, w[4 * q], ax);
-        ay = fmaf(v.y, w[4 * q + 1], ay);
-        az = fmaf(v.z, w[4 * q + 2], az);
-        aw = fmaf(v.w, w[4 * q + 3], aw);
-    }
-    return (ax + ay) + (az + aw);
-}
-// the same on an unaligned window, element by element (the small xy image, kept linear)
-template <int WIN, typename T>
-__device__ __forceinline__ float window_dot1(const T* s, const float (&w)[WIN]) {
-    float a0 = 0.0f, a1 = 0.0f;
-#pragma unroll
-    for (int t = 0; t + 1 < WIN; t += 2) {
-        a0 = fmaf((float)s[t], w[t], a0);
-        a1 = fmaf((float)s[t + 1], w[t + 1], a1);
-    }
-    if (WIN & 1) a0 = fmaf((float)s[WIN - 1], w[WIN - 1], a0);
-    return a0 + a1;
-}
 
 // One sample per workgroup iteration.  CODES: code rows in, raw codes as float16 in LDS (integers 0..255 are exact in float16: half
 // the LDS bytes of the float path, ds_read_b64 windows, v_fma_mix_f32 taps); !CODES: float32 rows in (the rows whose flag is NOT
@@ -111,38 +50,12 @@ __global__ __launch_bounds__(256) void k_pre3(PreArgs a) {
     if (!CODES && a.skip_if_set && *a.skip_if_set) return;
     extern __shared__ __align__(16) unsigned char smem[];
     const int tid = threadIdx.x;
-    const int X = a.X, Y = a.Y, Z = a.Z, OH = a.OH, OW = a.OW, SZ = a.SZ, TW = a.TW;
+    const int X = a.X, Y = a.Y, Z = a.Z, SZ = a.SZ;
     const int R1 = X + Y, XY = X * Y, D = R1 * Z + XY;
-    const int nimg = R1 * SZ + 16 + ((XY + 15) & ~15) + 32;     // image elements: [R1][SZ] + 16 pad, then xy linear + pad
-    float* tmp = reinterpret_cast<float*>(smem);    // [R1 + X + 3][TW]: xz, yz, xy rows after the horizontal pass, 3 pad rows
-    float* vw_s = tmp + (R1 + X + 3) * TW;          // [2][OH][VT]
-    int* vf_s = reinterpret_cast<int*>(vw_s + 2 * OH * VT);     // [2][OH]
-    T* inA = reinterpret_cast<T*>(vf_s + ((2 * OH + 3) & ~3));  // [R1][SZ] + 16: xz rows, then yz rows
-    T* inB = inA + R1 * SZ + 16;                    // [XY] linear + pad
-    // every pad (row tails, the elements behind each image, the pad rows of the intermediate) is read under a zero weight and must
-    // be finite: zeroed once, never written again
-    for (int i = tid; i < (R1 + X + 3) * TW; i += 256) tmp[i] = 0.0f;
-    for (int i = tid; i < nimg; i += 256) inA[i] = (T)0.0f;
-    for (int i = tid; i < 2 * OH * VT; i += 256) vw_s[i] = a.vw[i];
-    for (int i = tid; i < 2 * OH; i += 256) vf_s[i] = a.vfirst[i];
-
-    // horizontal pass: thread (g, xx) with its window weights in registers
-    const int G = 256 / OW;
-    const int hg = tid / OW, hx = tid - hg * OW;
-    const bool hact = hg < G;
-    float wz[WZ], wy[WY];
-    int az = 0, ay = 0;
-#pragma unroll
-    for (int t = 0; t < WZ; ++t) wz[t] = 0.0f;
-#pragma unroll
-    for (int t = 0; t < WY; ++t) wy[t] = 0.0f;
-    if (hact) {
-        az = a.hz_a0[hx]; ay = a.hy_a0[hx];
-#pragma unroll
-        for (int t = 0; t < WZ; ++t) wz[t] = a.hz_w[hx * WZ + t];
-#pragma unroll
-        for (int t = 0; t < WY; ++t) wy[t] = a.hy_w[hx * WY + t];
-    }
+    const PreLds<T> l = pre_lds_init<T>(smem, a, tid);
+    T* inA = l.inA;
+    PreWin<WZ, WY> h;
+    pre_win_load(h, a, tid);
 
     // staging map of this thread (fixed for the launch): 16-element units of the row [xz | yz | xy]; a unit of the first two planes
     // lies inside one image row (Z % 16 == 0), xy is kept linear
@@ -173,18 +86,7 @@ __global__ __launch_bounds__(256) void k_pre3(PreArgs a) {
             for (int u = 0; u < PU; ++u)
                 if (u < nu && dst[u] >= 0) {
                     const uint4 w4 = pa[u];
-                    const uint32_t ws[4] = {w4.x ^ 0x80808080u, w4.y ^ 0x80808080u, w4.z ^ 0x80808080u, w4.w ^ 0x80808080u};
-                    f16x8* d = reinterpret_cast<f16x8*>(inA + dst[u]);
-#pragma unroll
-                    for (int h = 0; h < 2; ++h) {
-                        const uint32_t w0 = ws[2 * h], w1 = ws[2 * h + 1];
-                        f16x8 v;
-                        v[0] = (_Float16)(float)(w0 & 0xFFu); v[1] = (_Float16)(float)((w0 >> 8) & 0xFFu);
-                        v[2] = (_Float16)(float)((w0 >> 16) & 0xFFu); v[3] = (_Float16)(float)(w0 >> 24);
-                        v[4] = (_Float16)(float)(w1 & 0xFFu); v[5] = (_Float16)(float)((w1 >> 8) & 0xFFu);
-                        v[6] = (_Float16)(float)((w1 >> 16) & 0xFFu); v[7] = (_Float16)(float)(w1 >> 24);
-                        d[h] = v;
-                    }
+                    stage_codes16(inA + dst[u], make_uint4(w4.x ^ 0x80808080u, w4.y ^ 0x80808080u, w4.z ^ 0x80808080u, w4.w ^ 0x80808080u));
                 }
         } else {
             // the float rows are the rare case (projections off the code grid): loaded here, no prefetch
@@ -208,11 +110,6 @@ __global__ __launch_bounds__(256) void k_pre3(PreArgs a) {
         }
     };
 
-    const int OW4 = OW >> 2;
-    const int per = OH * OW4;                       // 8-byte output pieces per projection
-    const int vdq = 256 / OW4, vdr = 256 - vdq * OW4;
-    const int64_t opl = (int64_t)OH * OW;
-
     int64_t b = blockIdx.x;
     if (CODES && b < a.B) issue(b);
     __syncthreads();                                // LDS initialised (this one may wait for the loads: once)
@@ -223,48 +120,9 @@ __global__ __launch_bounds__(256) void k_pre3(PreArgs a) {
         if (CODES && b + gridDim.x < a.B) issue(b + gridDim.x);
         if (!mine) continue;
         lds_barrier();
-
-        if (hact) {
-            // rows of [xz | yz] (length Z) and of xy (length Y) -> column hx of the intermediate, scaled to [-1, 1]
-            float* tc = tmp + hx;
-            int y = hg;
-            for (; y + G < R1; y += 2 * G) {        // two rows at a time: independent chains
-                const float r0 = window_dot<WZ, T>(inA + y * SZ + az, wz);
-                const float r1 = window_dot<WZ, T>(inA + (y + G) * SZ + az, wz);
-                tc[y * TW] = unit_range(r0);
-                tc[(y + G) * TW] = unit_range(r1);
-            }
-            if (y < R1) tc[y * TW] = unit_range(window_dot<WZ, T>(inA + y * SZ + az, wz));
-            tc += R1 * TW;
-            for (y = hg; y < X; y += G) tc[y * TW] = unit_range(window_dot1<WY, T>(inB + y * Y + ay, wy));
-        }
+        pre_horizontal<T, WZ, WY>(l, h, a);
         lds_barrier();
-
-#pragma unroll 1
-        for (int p = 0; p < 3; ++p) {
-            const float* tp = tmp + (p == 0 ? 0 : (p == 1 ? X : R1)) * TW;
-            const float* wv = vw_s + (p == 1 ? OH * VT : 0);
-            const int* fv = vf_s + (p == 1 ? OH : 0);
-            uint2* o8 = reinterpret_cast<uint2*>(a.out[p] + b * opl);
-            int yy = tid / OW4, c4 = tid - yy * OW4;
-            for (int r = tid; r < per; r += 256) {
-                const float4 w = *reinterpret_cast<const float4*>(wv + yy * VT);
-                const float* s = tp + fv[yy] * TW + 4 * c4;
-                const float4 v0 = *reinterpret_cast<const float4*>(s);
-                const float4 v1 = *reinterpret_cast<const float4*>(s + TW);
-                const float4 v2 = *reinterpret_cast<const float4*>(s + 2 * TW);
-                const float4 v3 = *reinterpret_cast<const float4*>(s + 3 * TW);
-                // two outputs per instruction (v_pk_mul_f32 / v_pk_fma_f32): the pairs (x, y) and (z, w) of the four outputs
-                const f32x2 w0 = {w.x, w.x}, w1 = {w.y, w.y}, w2 = {w.z, w.z}, w3 = {w.w, w.w};
-                f32x2 lo = f32x2{v0.x, v0.y} * w0, hi = f32x2{v0.z, v0.w} * w0;
-                lo = __builtin_elementwise_fma(f32x2{v1.x, v1.y}, w1, lo); hi = __builtin_elementwise_fma(f32x2{v1.z, v1.w}, w1, hi);
-                lo = __builtin_elementwise_fma(f32x2{v2.x, v2.y}, w2, lo); hi = __builtin_elementwise_fma(f32x2{v2.z, v2.w}, w2, hi);
-                lo = __builtin_elementwise_fma(f32x2{v3.x, v3.y}, w3, lo); hi = __builtin_elementwise_fma(f32x2{v3.z, v3.w}, w3, hi);
-                o8[r] = make_uint2(pk_bf16(lo.x, lo.y), pk_bf16(hi.x, hi.y));
-                yy += vdq; c4 += vdr;
-                if (c4 >= OW4) { c4 -= OW4; ++yy; }
-            }
-        }
+        pre_vertical<T>(l, a, b, tid);
         lds_barrier();                              // the images and the intermediate are free for the next sample
     }
 }
@@ -299,32 +157,6 @@ int odd_slots(int n, int per_slot) {        // row stride in elements: whole 16-
     int s = (n + per_slot - 1) / per_slot;
     if (!(s & 1)) ++s;
     return per_slot * s;
-}
-
-struct Plan {
-    bool ok = false;
-    int wz = 0, wy = 0, TW = 0;
-    int SZ[2] = {0, 0};         // image row stride: float32 images, float16 images
-    size_t lds[2] = {0, 0};
-    std::vector<int> hz_a0, hy_a0, vfirst;
-    std::vector<float> hz_w, hy_w, vw;
-};
-
-Plan build_plan(int X, int Y, int Z, int OH, int OW);
-
-// the plan of a (grid, output size) pair is a pure function of the five numbers: built once per process, not once per call
-// (four Pillow coefficient tables and their window tables: ~10^4 double operations at the Walabot grid)
-Plan make_plan(int X, int Y, int Z, int OH, int OW) {
-    static std::mutex mu;
-    static std::map<std::array<int, 5>, Plan> cache;
-    const std::array<int, 5> key{X, Y, Z, OH, OW};
-    std::lock_guard<std::mutex> lk(mu);
-    auto it = cache.find(key);
-    if (it == cache.end()) {
-        if (cache.size() >= 64) cache.clear();          // a bound, not a policy: callers use a handful of shapes
-        it = cache.emplace(key, build_plan(X, Y, Z, OH, OW)).first;
-    }
-    return it->second;                                  // a copy, made under the lock (a few KB of tables)
 }
 
 Plan build_plan(int X, int Y, int Z, int OH, int OW) {
@@ -366,8 +198,42 @@ Plan build_plan(int X, int Y, int Z, int OH, int OW) {
     return p;
 }
 
-// device copy of a plan's tables, cached in the context per (X, Y, Z, OH, OW)
-int pre_tables(rml_ctx* ctx, int X, int Y, int Z, int OH, int OW, const Plan& p, PreArgs& a) {
+template <bool CODES, int WZ, int WY>
+void launch_pre3(const PreArgs& a, size_t lds, int num_cu, hipStream_t st) {
+    RML_MAX_DYN_LDS(160 * 1024, &k_pre3<CODES, WZ, WY>);
+    int per_cu = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_pre3<CODES, WZ, WY>, 256, lds) != hipSuccess || per_cu < 1) {
+        (void)hipGetLastError();
+        per_cu = 1;
+    }
+    const int64_t slots = (int64_t)per_cu * num_cu;
+    hipLaunchKernelGGL((k_pre3<CODES, WZ, WY>), dim3((unsigned)(a.B < slots ? a.B : slots)), dim3(256), lds, st, a);
+}
+
+template <bool CODES>
+void launch_pre3_w(const Plan& p, const PreArgs& a, int num_cu, hipStream_t st) {
+    const size_t lds = p.lds[CODES ? 1 : 0];
+    if (p.wz == 16 && p.wy == 5) launch_pre3<CODES, 16, 5>(a, lds, num_cu, st);
+    else if (p.wz == 8 && p.wy == 5) launch_pre3<CODES, 8, 5>(a, lds, num_cu, st);
+    else launch_pre3<CODES, 16, 12>(a, lds, num_cu, st);
+}
+
+}  // namespace
+
+Plan rmlpre::make_plan(int X, int Y, int Z, int OH, int OW) {
+    static std::mutex mu;
+    static std::map<std::array<int, 5>, Plan> cache;
+    const std::array<int, 5> key{X, Y, Z, OH, OW};
+    std::lock_guard<std::mutex> lk(mu);
+    auto it = cache.find(key);
+    if (it == cache.end()) {
+        if (cache.size() >= 64) cache.clear();          // a bound, not a policy: callers use a handful of shapes
+        it = cache.emplace(key, build_plan(X, Y, Z, OH, OW)).first;
+    }
+    return it->second;                                  // a copy, made under the lock (a few KB of tables)
+}
+
+int rmlpre::pre_tables(rml_ctx* ctx, int X, int Y, int Z, int OH, int OW, const Plan& p, PreArgs& a) {
     std::lock_guard<std::recursive_mutex> lock(ctx->mu);
     for (int pass = 0; pass < 2; ++pass) {
         for (const auto& e : ctx->pre_tabs)
@@ -398,28 +264,6 @@ int pre_tables(rml_ctx* ctx, int X, int Y, int Z, int OH, int OW, const Plan& p,
     }
     return RML_ERR_INVALID;
 }
-
-template <bool CODES, int WZ, int WY>
-void launch_pre3(const PreArgs& a, size_t lds, int num_cu, hipStream_t st) {
-    RML_MAX_DYN_LDS(160 * 1024, &k_pre3<CODES, WZ, WY>);
-    int per_cu = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_pre3<CODES, WZ, WY>, 256, lds) != hipSuccess || per_cu < 1) {
-        (void)hipGetLastError();
-        per_cu = 1;
-    }
-    const int64_t slots = (int64_t)per_cu * num_cu;
-    hipLaunchKernelGGL((k_pre3<CODES, WZ, WY>), dim3((unsigned)(a.B < slots ? a.B : slots)), dim3(256), lds, st, a);
-}
-
-template <bool CODES>
-void launch_pre3_w(const Plan& p, const PreArgs& a, int num_cu, hipStream_t st) {
-    const size_t lds = p.lds[CODES ? 1 : 0];
-    if (p.wz == 16 && p.wy == 5) launch_pre3<CODES, 16, 5>(a, lds, num_cu, st);
-    else if (p.wz == 8 && p.wy == 5) launch_pre3<CODES, 8, 5>(a, lds, num_cu, st);
-    else launch_pre3<CODES, 16, 12>(a, lds, num_cu, st);
-}
-
-}  // namespace
 
 extern "C" int rml_dnn_preprocess_supported(int X, int Y, int Z, int out_h, int out_w) {
     const Plan p = make_plan(X, Y, Z, out_h, out_w);

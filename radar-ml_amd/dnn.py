@@ -607,7 +607,7 @@ class Classifier(_module_base()):
 
     # ---- volumes -> probabilities --------------------------------------------------------------------------
     def predict_volumes(self, volumes, rescale=(80, 80), mode="max", batch_size=16384, overlap=False, trunk_events=None,
-                        exact_resize=False, label_guard=LABEL_GUARD):
+                        exact_resize=False, label_guard=LABEL_GUARD, ijk=None, num_targets=1, return_ijk=False):
         """The whole inference path of BASELINE configs[3] on the GPU: (N,X,Y,Z) volumes (float32 or uint8) ->
         projections as uint8 code rows (csrc/project*.hip) -> [-1,1] scaling + bicubic resize of the three projections in one
         launch, bf16 out (csrc/preprocess.hip: Pillow's windows and weights in float32) -> fused conv trunk (csrc/dnn.hip) ->
@@ -630,19 +630,38 @@ class Classifier(_module_base()):
         seen.  Guarded outputs are not batching-invariant bit for bit (a row near the gap may be re-scored under one batching and
         not under another; both values are within the bf16 tolerance); ``label_guard=None`` results are.  ``self.last_guard``: what
         the guard did (the keys: dnn_guard.py).
+
+        ``mode="slice"``: what the model was trained on -- the three planes of the image through a target's voxel, yz = V[i,:,:],
+        xz = V[:,j,:], xy = V[:,:,k] (predict.py:98-107), for every target of every frame (predict.py:93-119).  ``ijk``: (N,3) or
+        (N,T,3) indices (negative ones wrap like Python's); None: the ``num_targets`` strongest derived targets of every frame
+        (``common.derive_targets``).  The result has N*T rows, frame-major (row b*T+t is target t of frame b); ``return_ijk=True``
+        returns ``(proba, ijk)`` with the (N,T,3) int32 indices the rows were sliced at.  (N,T,3) and derived targets go from the
+        volumes into the preprocessing kernel's LDS image in one launch (csrc/preprocess_slice.hip); the margin guard re-scores
+        row r from frame r // T at ijk[r] (:meth:`rescore_exact`).  The other modes ignore the three arguments.
         """
         import torch
         if not isinstance(volumes, torch.Tensor):
             volumes = torch.as_tensor(volumes)
         n = int(volumes.shape[0])
         dev = volumes.device if volumes.is_cuda else next(self.parameters()).device
+        sliced = mode == "slice"
+        T = 1
+        if sliced:
+            from . import nn_common
+            ijk, T = nn_common.slice_targets_arg(ijk, n, num_targets)
         if n == 0:
-            return torch.zeros((0, self.n_classes), device=dev)
+            res = torch.zeros((0, self.n_classes), device=dev)
+            return (res, torch.zeros((0, T, 3), dtype=torch.int32, device=dev)) if (sliced and return_ijk) else res
         if dev.type != "cuda":
             raise RuntimeError("predict_volumes runs on the GPU: move the model to a CUDA device (there is no CPU path)")
         bs = int(min(batch_size, n))
         plan = [(s0, min(n, s0 + bs)) for s0 in range(0, n, bs)]         # the passes: frames [s0, s1) each
-        out = torch.empty((n, self.n_classes), dtype=torch.float32, device=dev)
+        out = torch.empty((n * T, self.n_classes), dtype=torch.float32, device=dev)
+        if sliced:
+            with torch.no_grad(), torch.cuda.device(dev):
+                used = self._chain_slices(volumes, plan, out, rescale, exact_resize, trunk_events, ijk, T)
+                res = self._guard(out, label_guard, lambda idx, prec: self.rescore_exact(volumes, rescale, mode, prec, rows=idx, ijk=used))
+            return (res, used) if return_ijk else res
         with torch.no_grad(), torch.cuda.device(dev):
             if overlap and len(plan) > 1 and volumes.is_cuda:
                 self._chain_two_streams(volumes, plan, out, rescale, mode, trunk_events)
@@ -670,6 +689,28 @@ class Classifier(_module_base()):
                 feat = common.process_volumes(v, mode=mode, scale=False)
                 xs = nn_common.preprocess_features(feat, dims, rescale, out_dtype="bfloat16")
             out[s0:s1] = self._forward_timed(xs, trunk_events)
+
+    def _chain_slices(self, volumes, plan, out, rescale, exact_resize, trunk_events, ijk, T):
+        """:meth:`_chain_serial` on target slices: ``T`` rows per frame, ``ijk`` (N,3) / (N,T,3) or None (derived targets).  Returns the
+        (N,T,3) int32 CUDA indices the rows were sliced at.  Grids and rescales the fused preprocessing does not take, and
+        ``exact_resize``: float32 slice rows (``process_volumes``) and the Pillow-exact resize, the same rows."""
+        import torch
+        from . import common, nn_common
+        dims = tuple(int(v) for v in volumes.shape[1:])
+        dev = out.device
+        fused = not exact_resize and nn_common.preprocess_supported(dims, rescale)
+        used = []
+        for s0, s1 in plan:
+            v = volumes[s0:s1] if volumes.is_cuda else volumes[s0:s1].to(dev)
+            idx = None if ijk is None else ijk[s0:s1]
+            if fused:
+                xs, got = nn_common.preprocess_volumes(v, rescale, mode="slice", ijk=idx, num_targets=T, return_ijk=True)
+            else:
+                feat, got = common.process_volumes(v, mode="slice", ijk=idx, num_targets=T, scale=False, return_ijk=True)
+                xs = nn_common.preprocess_features(feat, dims, rescale, out_dtype="bfloat16")
+            out[s0 * T:s1 * T] = self._forward_timed(xs, trunk_events)
+            used.append(got)
+        return used[0] if len(used) == 1 else torch.cat(used)
 
     def _chain_two_streams(self, volumes, plan, out, rescale, mode, trunk_events):
         """The ``overlap`` chain: the projection of pass b+2 on a second stream beside the resize of pass b+1, the trunk (a whole CU's
@@ -844,7 +885,7 @@ class Classifier(_module_base()):
     # not by RESCORE_BYTES of volumes)
     RESCORE_BLOCK = 16384
 
-    def rescore_exact(self, volumes, rescale=(80, 80), mode="max", precision="float64", rows=None):
+    def rescore_exact(self, volumes, rescale=(80, 80), mode="max", precision="float64", rows=None, ijk=None):
         """(n,X,Y,Z) volumes -> (n, n_classes) probabilities through the reference's chain without a rounding the reference does
         not have: projection (exact), (p - 127.5) / 127.5 and Pillow's bicubic resize in float64 rounded to float32 planes as
         Pillow stores them (csrc/resize.hip, bit-identical), then the layers in ``precision`` (:meth:`forward_exact`: "x3",
@@ -852,7 +893,11 @@ class Classifier(_module_base()):
         tensor -- score ``volumes[rows]`` (in that order), a pass of at most RESCORE_BYTES of volumes at a time.  A sparse ``rows``
         gathers its frames (:func:`rescore_route`: in one library call per pass where that takes them); when at least half of the
         frames are wanted the passes project whole contiguous blocks of frames instead (no 480 KB-per-frame gather) and pick the
-        40 KB feature rows."""
+        40 KB feature rows.
+
+        ``mode="slice"``: ``ijk`` (n,3) or (n,T,3) -- the result has n*T rows, frame-major, and ``rows`` indexes THOSE: row r is scored
+        from frame r // T at ijk[r] (``nn_common.slice_row_targets``), through ``process_volumes(mode="slice", ijk=...)`` (exact), the
+        Pillow-exact resize and :meth:`forward_exact`."""
         import torch
         from . import common, nn_common
         N = int(volumes.shape[0])
@@ -860,6 +905,8 @@ class Classifier(_module_base()):
         step = max(64, min(16384, self.RESCORE_BYTES // max(1, dims[0] * dims[1] * dims[2] * volumes.element_size())))
         host = not volumes.is_cuda
         dev = next(self.parameters()).device
+        if mode == "slice":
+            return self._rescore_slices(volumes, rescale, precision, rows, ijk, step)
 
         def score(v, pick=None):
             if host:
@@ -883,6 +930,43 @@ class Classifier(_module_base()):
                 outs = [score(volumes[s:s + step]) for s in range(0, N, step)]
             else:
                 outs = self._rescore_gather(volumes, rows, step, score)
+        return torch.cat(outs) if len(outs) != 1 else outs[0]
+
+    def _rescore_slices(self, volumes, rescale, precision, rows, ijk, step):
+        """:meth:`rescore_exact` on target slices.  All rows: blocks of frames with their (T,3) indices, no volume duplicated; an index
+        tensor: the frames of ``step`` rows gathered (a frame once per wanted target of it: the guard asks for a handful of rows)."""
+        import torch
+        from . import common, nn_common
+        if ijk is None:
+            raise ValueError("rescore_exact: mode='slice' needs ijk")
+        N = int(volumes.shape[0])
+        dims = tuple(int(v) for v in volumes.shape[1:])
+        host = not volumes.is_cuda
+        dev = next(self.parameters()).device
+        ijk, T = nn_common.slice_targets_arg(ijk, N)
+        ijk = ijk.reshape(N, T, 3)
+        if rows is not None and 2 * int(rows.numel()) >= N * T:
+            # at least half of the rows are wanted (a model without margins): every row by blocks of frames, no gather, and pick
+            return self._rescore_slices(volumes, rescale, precision, None, ijk, step)[rows.to(dev)]
+
+        def score(v, idx):
+            feat = common.process_volumes(v.to(dev) if host else v, mode="slice", ijk=idx, scale=False)
+            xs = nn_common.preprocess_features(feat, dims, rescale, out_dtype="float32")
+            return self.forward_exact(*xs, precision=precision)
+
+        with torch.no_grad():
+            if rows is None:
+                fstep = max(1, step // T)
+                outs = [score(volumes[s:s + fstep], ijk[s:s + fstep]) for s in range(0, N, fstep)]
+            else:
+                flat = ijk.reshape(N * T, 3)
+                outs = []
+                for s in range(0, int(rows.numel()), step):
+                    r = rows[s:s + step]
+                    frames, _ = nn_common.slice_row_targets(r, T)
+                    outs.append(score(volumes[frames.cpu() if host else frames.to(volumes.device)], flat[r.to(flat.device)]))
+            if not outs:
+                return torch.zeros((0, self.n_classes), dtype=torch.float64 if precision == "float64" else torch.float32, device=dev)
         return torch.cat(outs) if len(outs) != 1 else outs[0]
 
     @staticmethod

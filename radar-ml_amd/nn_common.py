@@ -148,12 +148,73 @@ def preprocess_rows(grid, rescale, feat=None, codes=None, flags=None):
     return outs
 
 
-def preprocess_volumes(volumes, rescale, mode="max", ijk=None):
+def slice_row_targets(rows, T):
+    """Rows of a frame-major (B*T) slice batch -> (frames, targets): row ``r`` is target ``r % T`` of frame ``r // T``
+    (``process_volumes(mode='slice', ijk=(B,T,3))``, ``rml_dnn_preprocess_slices``).  ``rows``: integers in any order, repeats allowed
+    (a list, a NumPy array or a torch tensor; the result has its kind and order)."""
+    T = int(T)
+    if T < 1:
+        raise ValueError("slice_row_targets: T >= 1 expected")
+    if hasattr(rows, "div"):                          # torch
+        return rows.div(T, rounding_mode="floor"), rows.remainder(T)
+    r = np.asarray(rows)
+    if r.size and r.dtype.kind not in "iu":
+        raise TypeError("slice_row_targets: integer rows expected")
+    return r // T, r % T
+
+
+def slice_targets_arg(ijk, n, num_targets=1):
+    """The ``ijk`` / ``num_targets`` arguments of a slice call on ``n`` frames -> (ijk as a tensor that can be cut per pass or None,
+    T targets per frame): (n,3) -> T = 1, (n,T,3) -> T, None -> ``num_targets`` derived targets.  The range of the indices is checked
+    where they are used (``common._slice_indices``)."""
+    torch = _torch()
+    if ijk is None:
+        T = int(num_targets)
+    else:
+        if not isinstance(ijk, torch.Tensor):
+            ijk = torch.as_tensor(np.asarray(ijk))
+        if ijk.ndim == 1 and n == 1:
+            ijk = ijk.reshape(1, 3)
+        if ijk.ndim not in (2, 3) or ijk.shape[-1] != 3 or int(ijk.shape[0]) != n:
+            raise ValueError("ijk must be (N,3) or (N,T,3) with one row (or T rows) per frame")
+        T = 1 if ijk.ndim == 2 else int(ijk.shape[1])
+    if T < 1:
+        raise ValueError("at least one target per frame expected")
+    return ijk, T
+
+
+def preprocess_slices(volumes, ijk_t, T, rescale):
+    """The trunk's three bf16 inputs (B*T, H, W) of the target slices yz = V[i,:,:], xz = V[:,j,:], xy = V[:,:,k] (predict.py:98-107)
+    in ONE launch, straight from the volumes (csrc/preprocess_slice.hip, ``rml_dnn_preprocess_slices``): ``volumes`` a contiguous CUDA
+    (B, X, Y, Z) tensor, float32 or uint8, ``ijk_t`` the (B*T, 3) int32 CUDA indices of ``common._slice_indices`` (frame-major, in
+    range or negative as Python's).  The planes are those of :func:`preprocess_rows` on the sliced rows, bit for bit."""
+    torch = _torch()
+    from . import _lib
+    lib = _lib.load()
+    B, X, Y, Z = (int(t) for t in volumes.shape)
+    dev = volumes.device
+    oh, ow = int(rescale[1]), int(rescale[0])
+    vdt = _lib.VOL_U8 if volumes.dtype == torch.uint8 else _lib.VOL_F32
+    outs = [torch.empty((B * int(T), oh, ow), dtype=torch.bfloat16, device=dev) for _ in range(3)]
+    with torch.cuda.device(dev):
+        _lib.check(lib.rml_dnn_preprocess_slices(_lib.context(dev), _lib.ptr(volumes), vdt, B, X, Y, Z, _lib.ptr(ijk_t), int(T), oh, ow,
+                                                 _lib.ptr(outs[0]), _lib.ptr(outs[1]), _lib.ptr(outs[2]), _lib.stream_ptr(dev)),
+                   "rml_dnn_preprocess_slices")
+    return outs
+
+
+def preprocess_volumes(volumes, rescale, mode="max", ijk=None, num_targets=1, return_ijk=False):
     """(N, X, Y, Z) volumes (float32 or uint8, CUDA) -> the trunk's three bf16 inputs (N, H, W): projection into uint8 code rows
     (no float rows through HBM when the projections are integers 0..255 -- radar magnitudes, common.py:30-31; rows that are not
     take a device-predicated float pass), then the fused scaling + bicubic resize (``rml_dnn_preprocess_volumes``).  Finite
     projections assumed on the float pass (its aligned windows touch neighbouring rows under zero weights: 0 * NaN is NaN where
-    Pillow would not have read): ``Classifier.predict_volumes`` sends mode "max_nan" through the Pillow-exact resize instead."""
+    Pillow would not have read): ``Classifier.predict_volumes`` sends mode "max_nan" through the Pillow-exact resize instead.
+
+    mode='slice': ``ijk`` as (N,3) or -- several targets per frame, the reference's ``for target in targets`` (predict.py:93-119) --
+    (N,T,3): N*T rows, frame-major (row b*T+t).  ``ijk=None``: the ``num_targets`` strongest derived targets of every frame
+    (``common.derive_targets``).  (N,T,3) and derived targets go straight from the volumes into the kernel's LDS image
+    (:func:`preprocess_slices`: one launch); an (N,3) call keeps the code-row route above.  ``return_ijk=True`` appends the (N,T,3)
+    int32 indices the rows were sliced at."""
     torch = _torch()
     from . import _lib, common
     lib = _lib.load()
@@ -163,11 +224,14 @@ def preprocess_volumes(volumes, rescale, mode="max", ijk=None):
     m = _lib.MODES[mode]
     ijk_t = None
     if m == _lib.MODE_SLICE:
-        if ijk is None:
-            raise ValueError("preprocess_volumes: mode='slice' needs ijk")
-        ijk_t, T = common._slice_indices(ijk, n, X, Y, Z, dev)
-        if T != 1:
-            raise ValueError("preprocess_volumes: one (i,j,k) per frame")
+        derived = ijk is None
+        if derived:
+            ijk = common.derive_targets(v, int(num_targets))
+        per_frame = not derived and (ijk.ndim if hasattr(ijk, "ndim") else np.ndim(ijk)) != 3
+        ijk_t, T = common._slice_indices(ijk, n, X, Y, Z, dev, validate=not derived)
+        if not per_frame:
+            outs = preprocess_slices(v, ijk_t, T, rescale)
+            return (outs, ijk_t.reshape(n, T, 3)) if return_ijk else outs
     D = common.feature_len(X, Y, Z)
     ldq = (D + 127) // 128 * 128
     oh, ow = int(rescale[1]), int(rescale[0])
@@ -179,6 +243,8 @@ def preprocess_volumes(volumes, rescale, mode="max", ijk=None):
         _lib.check(lib.rml_dnn_preprocess_volumes(_lib.context(dev), _lib.ptr(v), vdt, n, X, Y, Z, m, _lib.ptr(ijk_t), _lib.ptr(codes), ldq,
                                                   _lib.ptr(flags), _lib.ptr(rows), D, oh, ow, _lib.ptr(outs[0]), _lib.ptr(outs[1]),
                                                   _lib.ptr(outs[2]), _lib.stream_ptr(dev)), "rml_dnn_preprocess_volumes")
+    if return_ijk:
+        return outs, (ijk_t.reshape(n, 1, 3) if ijk_t is not None else None)
     return outs
 
 

@@ -32,3 +32,15 @@ def classify_batch(proba, class_names, min_proba=0.7):
     p = proba[np.arange(proba.shape[0]), j]
     names = [class_names[jj] if pp >= min_proba else 'Unknown' for jj, pp in zip(j, p)]
     return names, p
+
+
+def classify_targets(model, class_names, volumes, ijk=None, num_targets=1, min_proba=0.7):
+    """The per-target body of the reference's live loop (predict.py:93-119) for a neural classifier: every target of every scan
+    is classified from the three planes of the image through its voxel.  ``model``: a ``dnn.Classifier`` or an
+    ``sgan.Discriminator`` on the GPU; ``volumes`` (B,X,Y,Z); ``ijk`` (B,3) or (B,T,3) target indices, None: the ``num_targets``
+    strongest derived targets of every frame.  Returns ``(names, proba)`` of the B*T targets, frame-major (row b*T+t), as
+    :func:`classify_batch` gives them: 'Unknown' below ``min_proba``."""
+    proba = model.predict_volumes(volumes, mode="slice", ijk=ijk, num_targets=num_targets)
+    if hasattr(proba, "detach"):
+        proba = proba.detach().float().cpu().numpy()
+    return classify_batch(proba, class_names, min_proba)

@@ -238,13 +238,18 @@ class Discriminator(_nn().Module):
         with torch.no_grad():
             return self.dense_tail_fused(self.features_fused(xz, yz, xy))
 
-    def predict_volumes(self, volumes, rescale=RESCALE, mode="max", ijk=None, batch_size=8192, exact_resize=False, return_numpy=True):
+    def predict_volumes(self, volumes, rescale=RESCALE, mode="max", ijk=None, batch_size=8192, exact_resize=False, return_numpy=True,
+                        num_targets=1, return_ijk=False):
         """Radar volumes -> class probabilities on the GPU: (N, X, Y, Z) volumes (float32 or uint8; numpy or torch, host or device)
         -> projections -> ``(p - 127.5) / 127.5`` and the bicubic resize of sgan.py:636-681 to ``rescale`` (Pillow's (width, height))
         -> fused trunk -> LeakyReLU tail.  Grids the fused preprocessing kernel takes (``nn_common.preprocess_supported``: at 128x128 the
         Walabot grid does, 64x64x128 does not) go from uint8 code rows to bf16 planes in one launch (Pillow's windows in float32: the planes are within one bf16 ulp
         of the exact ones); other grids, mode "max_nan" and ``exact_resize=True`` take float32 rows and the Pillow-bit-identical
-        resize.  ``mode="slice"`` needs ``ijk`` (N, 3).  ``batch_size``: frames per pass; a row's result does not depend on it.
+        resize.  ``mode="slice"``: the planes through a target's voxel (predict.py:98-107) at ``ijk`` (N,3) or -- every target of every
+        frame, predict.py:93-119 -- (N,T,3); ``ijk=None``: the ``num_targets`` strongest derived targets of every frame.  The result has
+        N*T rows, frame-major (row b*T+t), (N,T,3) and derived targets in one preprocessing launch straight from the volumes
+        (csrc/preprocess_slice.hip); ``return_ijk=True`` returns ``(proba, ijk)`` with the (N,T,3) int32 indices used (a CUDA tensor;
+        NumPy with ``return_numpy``).  ``batch_size``: frames per pass; a row's result does not depend on it.
         There is no margin guard: rows whose two largest probabilities are closer than the bf16 chain's error (a few 1e-3) can
         take the other label than float32 Keras would give."""
         import torch
@@ -258,12 +263,15 @@ class Discriminator(_nn().Module):
         oh, ow = int(rescale[1]), int(rescale[0])
         if not self.fused_supported(oh, ow):
             raise ValueError("predict_volumes: the fused SGAN trunk does not take %dx%d planes on this model" % (oh, ow))
-        if mode == "slice" and ijk is None:
-            raise ValueError("predict_volumes: mode='slice' needs ijk")
-        out = torch.empty((n, self.n_classes), dtype=torch.float32, device=dev)
+        sliced = mode == "slice"
+        T = 1
+        if sliced:
+            ijk, T = nn_common.slice_targets_arg(ijk, n, num_targets)
+        out = torch.empty((n * T, self.n_classes), dtype=torch.float32, device=dev)
         dims = tuple(int(v) for v in volumes.shape[1:])
         fused = not exact_resize and mode != "max_nan" and nn_common.preprocess_supported(dims, rescale)
         bs = max(1, int(batch_size))
+        used = []
         with torch.no_grad(), torch.cuda.device(dev):
             for s0 in range(0, n, bs):
                 s1 = min(n, s0 + bs)
@@ -272,12 +280,22 @@ class Discriminator(_nn().Module):
                     v = v.float()
                 idx = None if ijk is None else ijk[s0:s1]
                 if fused:
-                    xs = nn_common.preprocess_volumes(v, rescale, mode=mode, ijk=idx)
+                    xs = nn_common.preprocess_volumes(v, rescale, mode=mode, ijk=idx, num_targets=T, return_ijk=sliced)
+                    if sliced:
+                        xs, got = xs
                 else:
-                    feat = common.process_volumes(v, mode=mode, ijk=idx, scale=False)
+                    feat = common.process_volumes(v, mode=mode, ijk=idx, num_targets=T, scale=False, return_ijk=sliced)
+                    if sliced:
+                        feat, got = feat
                     xs = nn_common.preprocess_features(feat, dims, rescale, out_dtype="bfloat16")
-                out[s0:s1] = self.forward_fused(*xs)
-        return out.cpu().numpy() if return_numpy else out
+                if sliced:
+                    used.append(got)
+                out[s0 * T:s1 * T] = self.forward_fused(*xs)
+        res = out.cpu().numpy() if return_numpy else out
+        if sliced and return_ijk:
+            got = torch.cat(used) if used else torch.zeros((0, T, 3), dtype=torch.int32, device=dev)
+            return res, (got.cpu().numpy() if return_numpy else got)
+        return res
 
     # ---- Keras layout in / out -------------------------------------------------------------------------
     def _conv_bn_pairs(self):
