@@ -854,6 +854,35 @@ int rml_conv7_tanh_forward(rml_ctx* ctx, const void* x, int dtype, int64_t N, in
 int rml_conv7_tanh_backward(rml_ctx* ctx, const void* x, const float* y, const float* dy, int dtype, int64_t N, int H, int W, int C,
                             const float* weight, float* workspace, void* dx, float* dweight, float* dbias, void* stream);
 
+/* ---- SGAN generator at inference (sgan.py:57-122 through g_model.predict: sgan.py:450 in generate_fake_samples, sgan.py:462-488 in
+ * summarize_performance; csrc/gen_infer.hip) ----------------------------------------------------------------------------------------------
+ * rml_gen_up_forward: Conv2DTranspose(C -> C, 4x4, stride 2, 'same') + BatchNormalization (moving statistics) + ReLU (sgan.py:65-87) with
+ * the BatchNorm folded by the CALLER.  x: N x H x W x C (NHWC, dense) float16 (dtype 0) or bfloat16 (dtype 1) -> y: N x 2H x 2W x C of the
+ * same type.  Output pixel (2m+p, 2n+q), p, q in {0, 1}, reads the 2x2 input window at rows m-1+p+a and columns n-1+q+b (a, b in {0, 1};
+ * outside the plane: zero) through the kernel taps ky = 3-p-2a, kx = 3-q-2b (oy = 2 iy + ky - 1).  wt (DEVICE, of x's type):
+ * wt[p*2+q][co][(a*2+b)*C + ci] = K[ky][kx][co][ci] * s[co] with K the Keras kernel (4, 4, out, in) and s = gamma / sqrt(moving_variance +
+ * eps); bias[co] float32 = beta + (b - moving_mean) * s.  Four implicit GEMMs (K = 4C) on the matrix cores, float32 accumulation, bias and
+ * ReLU in float32 before the rounding.  No atomics; the sum order of an output element depends on nothing but (H, W): a sample has the
+ * same bits alone, at any position of any batch, and on a second call.  x, wt, bias and y 16-byte aligned.
+ * rml_gen_up_supported (HOST, no device): C = 128, H and W multiples of 8 in [8, 128]; anything else: 0, and rml_gen_up_forward returns
+ * RML_ERR_UNSUPPORTED without a launch.
+ * rml_sgan_generate: the whole generator, g_model.predict(z).  z [N][latent_dim] float32; per branch (xz, yz, xy) Dense + ReLU into the NHWC
+ * image [base][base][C] (Keras unit order: no permutation), n_up x rml_gen_up_forward ping-ponging through the workspace, then
+ * rml_conv7_tanh_forward into y_xz / y_yz / y_xy, each [N][S][S] float32, S = base * 2^n_up.  dense_w [3][latent_dim][base*base*C] float32
+ * (the Keras kernels), dense_b [3][base*base*C]; up_wt [3][n_up][4][C][4C] of `dtype` and up_bias [3][n_up][C] float32 as above; out_w
+ * [3][49][C] float32 and out_b [3] as rml_conv7_tanh_forward takes them.  The dense layer runs in float32 FMAs in a fixed order and rounds
+ * once.  N is cut into chunks so that the workspace stays bounded (128 MB of activations, one sample at least);
+ * workspace: rml_sgan_generate_workspace_bytes(N, base, n_up, C) bytes (0 for unsupported sizes; non-decreasing in N), 16-byte aligned.
+ * Asynchronous on `stream`, no device synchronisation.  Unsupported sizes (RML_ERR_UNSUPPORTED) and a workspace that is too small
+ * (RML_ERR_INVALID) are reported before anything is launched. */
+int rml_gen_up_supported(int H, int W, int C);
+int rml_gen_up_forward(rml_ctx* ctx, const void* x, int dtype, int64_t N, int H, int W, int C, const void* wt, const float* bias, void* y,
+                       void* stream);
+int64_t rml_sgan_generate_workspace_bytes(int64_t N, int base, int n_up, int C);
+int rml_sgan_generate(rml_ctx* ctx, const float* z, int64_t N, int latent_dim, int base, int n_up, int C, int dtype, const float* dense_w,
+                      const float* dense_b, const void* up_wt, const float* up_bias, const float* out_w, const float* out_b, float* y_xz,
+                      float* y_yz, float* y_xy, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* ---- Adam update of the SGAN discriminator (sgan.py:206, 214: Adam(lr=0.0002, beta_1=0.5) inside train_on_batch, sgan.py:525-532) ----
  * ONE pass over all parameters with the loss-scale bookkeeping of a half-precision step on the device (csrc/optim.hip).
  * table: DEVICE array of n_tensors + 1 records of rml_adam_entry_bytes() bytes each,

@@ -29,6 +29,7 @@ __all__ = [
     "GridSearchSGD", "find_best_sgd_svm_estimator", "fit_sgd", "partial_fit_sgd",
     "partial_fit_sgd_steps", "balance_classes", "balance_indices", "sgd_fit", "svc_fit", "calibrate_prefit", "evaluate_model",
     "define_classifier", "train_classifier", "define_discriminator", "fold_batchnorm", "folded_packs",
+    "define_generator", "fold_generator", "generator_packs", "generate_dataset",
 ]
 
 
@@ -39,6 +40,10 @@ def __getattr__(name):
         return dnn.define_classifier if name == "define_classifier" else dnn.train
     # the SGAN classifier (sgan.py): the model whose forward_fused / predict_volumes run csrc/sgan_infer.hip, and its folded weights
     if name in ("define_discriminator", "fold_batchnorm", "folded_packs"):
+        from . import sgan
+        return getattr(sgan, name)
+    # the SGAN generator: the model whose forward_fused / predict(fused=True) run csrc/gen_infer.hip, its folded weights, its data product
+    if name in ("define_generator", "fold_generator", "generator_packs", "generate_dataset"):
         from . import sgan
         return getattr(sgan, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

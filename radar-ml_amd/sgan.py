@@ -17,7 +17,10 @@ The generator side of the loop (sgan.py:57-122, 220-235, 439-543) is here too: :
 trained, every other discriminator weight is frozen for that step only), ``generate_fake_samples``, the
 ``generated_data_*.pickle`` product (``generated_samples`` / ``save_generated``) and the four-update loop :func:`train`.  On
 the GPU under half-precision autocast the transposed convolutions run through the library, BatchNorm + ReLU is the fused op of the
-discriminator (slope 0) and the 7x7 one-channel output layer is csrc/gen.hip (nn_common.conv7_tanh).
+discriminator (slope 0) and the 7x7 one-channel output layer is csrc/gen.hip (nn_common.conv7_tanh).  In inference mode
+(``g_model.predict``: the fake samples of every step, the data product) the whole generator can run on csrc/gen_infer.hip --
+``Generator.forward_fused``, ``predict(fused=True)``, :func:`generate_dataset`: the BatchNorm layers folded into the transposed
+convolutions (:func:`fold_generator`), each of which is four phase GEMMs on the matrix cores; every ``fused`` keyword defaults to False.
 """
 import logging
 import os
@@ -756,6 +759,7 @@ class Generator(_nn().Module):
             br.bns = nn.ModuleList([nn.BatchNorm2d(self.channels, eps=1e-3, momentum=0.01) for _ in range(self.n_up)])
             br.out = nn.Conv2d(self.channels, 1, 7, padding=3)
             self.branches.append(br)
+        self._packs = {}                            # name -> (key of the tensors it was made from, value): generator_packs
         for mod in self.modules():
             if isinstance(mod, (nn.Conv2d, nn.ConvTranspose2d, nn.Linear)):
                 nn.init.normal_(mod.weight, 0.0, 0.02)      # RandomNormal(stddev=0.02), sgan.py:60
@@ -793,11 +797,86 @@ class Generator(_nn().Module):
         adt = torch.get_autocast_dtype("cuda") if (z.is_cuda and torch.is_autocast_enabled("cuda")) else None
         return [self._branch(z, br, adt) for br in self.branches]
 
-    def predict(self, z, batch_size=256, return_numpy=True, amp_dtype=None):
+    # ---- inference on the fused HIP chain (csrc/gen_infer.hip + the forward of csrc/gen.hip) -------------------------------
+    def packs_key(self):
+        """What :func:`generator_packs` is cached on: the version counter and the storage of every parameter AND every BatchNorm
+        buffer.  An eager optimizer step, ``DeviceAdam`` (it increments the versions of what it wrote through raw pointers),
+        ``set_keras_weights``, ``load_state_dict`` and ``.to()`` change it; so does a training-mode forward, the fused one too: its
+        kernel advances the moving statistics through raw pointers, but ``nn_common._bn_side_effects`` then writes
+        ``num_batches_tracked`` and ``running_mean`` with ordinary in-place ops, and both are read here."""
+        return tuple((t._version, t.data_ptr()) for t in list(self.parameters()) + list(self.buffers()))
+
+    def generator_packs(self, dtype=None):
+        """:func:`generator_packs` of this model, cached until :meth:`packs_key` changes (one entry per dtype)."""
+        import torch
+        dtype = torch.bfloat16 if dtype is None else dtype
+        key = self.packs_key()
+        hit = self._packs.get(dtype)
+        if hit is None or hit[0] != key:
+            hit = self._packs[dtype] = (key, generator_packs(self, dtype, cached=False))
+        return hit[1]
+
+    def fused_supported(self):
+        """True when the fused inference chain takes this model's geometry: 128 channels, every transposed convolution on a plane
+        whose edge is a multiple of 8 in [8, 128] (``rml_gen_up_supported``), images of at most 256 x 256."""
+        from . import _lib
+        lib = _lib.load()
+        return (len(self.branches) == 3 and all(bool(lib.rml_gen_up_supported(self.base << l, self.base << l, self.channels)) for l in range(self.n_up))
+                and int(lib.rml_sgan_generate_workspace_bytes(1, self.base, self.n_up, self.channels)) > 0)
+
+    def forward_fused(self, z, dtype=None):
+        """``g_model.predict(z)`` on the fused HIP chain: three (n, 1, S, S) float32 CUDA tensors in [-1, 1] from (n, latent_dim)
+        latent points, in inference mode whatever ``self.training`` says (moving statistics; the BatchNorm layers folded into the
+        transposed convolutions, :func:`fold_generator`).  ``dtype``: the operand type of the matrix cores, bfloat16 (default) or
+        float16.  A sample's images do not depend on the batch around it.  Raises ValueError for a geometry the chain does not take
+        (there is no fall-back), for a model that is not on a GPU, and when ``z`` asks for a gradient."""
+        import torch
+        from . import _lib
+        dtype = torch.bfloat16 if dtype is None else dtype
+        par = next(self.parameters())
+        if par.device.type != "cuda":
+            raise ValueError("forward_fused runs on the GPU: move the generator to a CUDA device (there is no CPU path)")
+        if dtype not in (torch.bfloat16, torch.float16) or par.dtype != torch.float32:
+            raise ValueError("forward_fused: bfloat16 or float16 operands from a float32 model expected")
+        if isinstance(z, torch.Tensor) and z.requires_grad and torch.is_grad_enabled():
+            raise ValueError("forward_fused is inference only: it has no backward (z requires a gradient)")
+        if not self.fused_supported():
+            raise ValueError("the fused generator chain takes 128 channels and transposed convolutions on planes whose edge is a multiple "
+                             "of 8 in [8, 128]: got channels=%d, base=%d, n_up=%d" % (self.channels, self.base, self.n_up))
+        dev = par.device
+        with torch.no_grad():
+            zt = (z if isinstance(z, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(z))).to(device=dev, dtype=torch.float32)
+            if zt.ndim != 2 or zt.shape[1] != self.latent_dim:
+                raise ValueError("forward_fused: (n, %d) latent points expected, got %s" % (self.latent_dim, tuple(zt.shape)))
+            zt = zt.contiguous()
+            n, S = int(zt.shape[0]), self.size
+            outs = [torch.empty((n, 1, S, S), dtype=torch.float32, device=dev) for _ in range(3)]
+            if n == 0:
+                return outs
+            lib = _lib.load()
+            pk = self.generator_packs(dtype)
+            nbytes = int(lib.rml_sgan_generate_workspace_bytes(n, self.base, self.n_up, self.channels))
+            ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+            with torch.cuda.device(dev):
+                _lib.check(lib.rml_sgan_generate(_lib.context(dev), _lib.ptr(zt), n, self.latent_dim, self.base, self.n_up, self.channels,
+                                                 1 if dtype == torch.bfloat16 else 0, _lib.ptr(pk["dense_w"]), _lib.ptr(pk["dense_b"]),
+                                                 _lib.ptr(pk["up_wt"]), _lib.ptr(pk["up_bias"]), _lib.ptr(pk["out_w"]), _lib.ptr(pk["out_b"]),
+                                                 _lib.ptr(outs[0]), _lib.ptr(outs[1]), _lib.ptr(outs[2]), _lib.ptr(ws), nbytes,
+                                                 _lib.stream_ptr(dev)), "rml_sgan_generate")
+        return outs
+
+    def predict(self, z, batch_size=256, return_numpy=True, amp_dtype=None, fused=False):
         """``g_model.predict(z)`` (sgan.py:450): inference mode (moving statistics), a list of three (n, S, S, 1) float32 arrays
         in [-1, 1]; with ``return_numpy=False`` three (n, 1, S, S) float32 tensors on the model's device, which
-        ``DiscriminatorTrainer.train_on_batch_d`` takes without a host trip.  ``amp_dtype``: run the layers under autocast."""
+        ``DiscriminatorTrainer.train_on_batch_d`` takes without a host trip.  ``amp_dtype``: run the layers under autocast.
+        ``fused=True``: the images come from :meth:`forward_fused` (csrc/gen_infer.hip) with ``amp_dtype`` as the operand type,
+        bfloat16 when none is given; a model that chain does not take raises ValueError."""
         import torch
+        if fused:
+            cat = self.forward_fused(z, dtype=amp_dtype)
+            if not return_numpy:
+                return cat
+            return [c.permute(0, 2, 3, 1).contiguous().cpu().numpy() for c in cat]
         dev = next(self.parameters()).device
         dt = next(self.parameters()).dtype
         zt = z if isinstance(z, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(z))
@@ -873,8 +952,58 @@ def define_generator(latent_dim=100, device=None):
     return Generator(latent_dim=latent_dim).to(dev).to(memory_format=torch.channels_last)
 
 
+def fold_generator(model):
+    """The inference-mode generator with every BatchNorm folded into the transposed convolution in front of it (as
+    :func:`fold_batchnorm` does for the classifier), float64 on the model's device, in Keras layouts.  Per branch
+    ``[(dense kernel (latent, base*base*channels), bias), [(w' (4, 4, out, in), b')] x n_up, (output kernel (7, 7, channels, 1), bias)]``
+    with ``s = gamma / sqrt(moving_variance + eps)``, ``w'[ky, kx, co, ci] = K[ky, kx, co, ci] * s[co]`` and
+    ``b' = beta + (bias - moving_mean) * s``; a layer is then ``relu(conv_transpose(x, w') + b')``."""
+    def d(t):
+        return t.detach().double()
+    out = []
+    for br in model.branches:
+        ups = []
+        for up, bn in zip(br.ups, br.bns):
+            sc = d(bn.weight) / (d(bn.running_var) + float(bn.eps)).sqrt()
+            ups.append((d(up.weight).permute(2, 3, 1, 0) * sc.reshape(1, 1, -1, 1), d(bn.bias) + (d(up.bias) - d(bn.running_mean)) * sc))
+        out.append([(d(br.dense.weight).t(), d(br.dense.bias)), ups, (d(br.out.weight).permute(2, 3, 1, 0), d(br.out.bias))])
+    return out
+
+
+def pack_up_kernel(w):
+    """A folded transposed-convolution kernel (4, 4, out, in) in the layout of ``rml_gen_up_forward``: (4, out, 4 * in) with
+    ``wt[p*2+q, co, (a*2+b)*in + ci] = w[3-p-2a, 3-q-2b, co, ci]`` -- per output phase (p, q) the four taps its 2x2 input window
+    meets, window row a / column b major."""
+    import torch
+    return torch.stack([torch.cat([w[3 - p - 2 * a, 3 - q - 2 * b] for a in (0, 1) for b in (0, 1)], dim=1)
+                        for p in (0, 1) for q in (0, 1)])
+
+
+def generator_packs(model, dtype=None, cached=True):
+    """:func:`fold_generator` in the layouts of ``rml_sgan_generate``, computed in float64 and cast once, on the model's device (CPU
+    tensors for a CPU model): ``dense_w`` (3, latent, base*base*channels) and ``dense_b`` float32; ``up_wt`` (3, n_up, 4, channels,
+    4*channels) of ``dtype`` (bfloat16 unless given; :func:`pack_up_kernel`) and ``up_bias`` (3, n_up, channels) float32; ``out_w``
+    (3, 49, channels) and ``out_b`` (3,) float32.  With ``dtype=torch.float64`` every array stays float64 (what the tests' NumPy twin
+    reads).  ``cached``: kept on the model until one of its parameters or BatchNorm buffers is written (``Generator.packs_key``)."""
+    import torch
+    dtype = torch.bfloat16 if dtype is None else dtype
+    if cached:
+        return model.generator_packs(dtype)
+    f = fold_generator(model)
+    fdt = torch.float64 if dtype == torch.float64 else torch.float32
+    C, dev = model.channels, next(model.parameters()).device
+    up_wt = [torch.stack([pack_up_kernel(w) for w, _ in ups]) if ups else torch.zeros((0, 4, C, 4 * C), dtype=torch.float64, device=dev)
+             for _, ups, _ in f]
+    up_b = [torch.stack([b for _, b in ups]) if ups else torch.zeros((0, C), dtype=torch.float64, device=dev) for _, ups, _ in f]
+    return {"dense_w": torch.stack([dn[0] for dn, _, _ in f]).to(fdt).contiguous(),
+            "dense_b": torch.stack([dn[1] for dn, _, _ in f]).to(fdt).contiguous(),
+            "up_wt": torch.stack(up_wt).to(dtype).contiguous(), "up_bias": torch.stack(up_b).to(fdt).contiguous(),
+            "out_w": torch.stack([o[0].reshape(49, C) for _, _, o in f]).to(fdt).contiguous(),
+            "out_b": torch.stack([o[1].reshape(()) for _, _, o in f]).to(fdt).contiguous()}
+
+
 class GanTrainer:
-    """``define_gan`` + ``gan_model.train_on_batch`` (sgan.py:220-235, 534-537): the loss is ``d_loss(D(G(z)), y)``.
+    """``define_gan`` +``gan_model.train_on_batch`` (sgan.py:220-235, 534-537): the loss is ``d_loss(D(G(z)), y)``.
     ``define_gan`` freezes every discriminator layer except BatchNormalization, so this optimizer -- its own
     Adam(2e-4, beta1 0.5, eps 1e-7) -- updates all generator parameters and the discriminator's BatchNorm gammas and betas
     (1 600 values at the default size).  During the step the discriminator runs in training mode (batch statistics, moving
@@ -966,25 +1095,59 @@ def generate_latent_points(latent_dim, n, rng):
     return rng.standard_normal(size=(n, latent_dim))
 
 
-def generate_fake_samples(generator, latent_dim, n, rng, return_numpy=True, amp_dtype=None):
-    """sgan.py:445-454: ``generator.predict`` on n latent points, and their labels in [0, 0.3)."""
+def generate_fake_samples(generator, latent_dim, n, rng, return_numpy=True, amp_dtype=None, fused=False):
+    """sgan.py:445-454: ``generator.predict`` on n latent points, and their labels in [0, 0.3).  ``fused``: as ``Generator.predict``
+    (the draws from ``rng`` are the same numbers in the same order either way)."""
     z = generate_latent_points(latent_dim, n, rng)
-    images = generator.predict(z, return_numpy=return_numpy, amp_dtype=amp_dtype)
+    if fused:
+        images = generator.predict(z, return_numpy=return_numpy, amp_dtype=amp_dtype, fused=True)
+    else:
+        images = generator.predict(z, return_numpy=return_numpy, amp_dtype=amp_dtype)
     return images, smooth_negative_labels(np.zeros((n, 1)), rng)
 
 
-def generated_samples(generator, latent_dim, n, rng, sizes=(XZ_SIZE, YZ_SIZE, XY_SIZE)):
-    """The samples of ``summarize_performance`` (sgan.py:462-483): n fake images scaled to RADAR_MAX * (v + 1) / 2 and resized back
-    to the radar arena with Pillow's BICUBIC (csrc/resize.hip, bit-identical to Pillow); ``sizes`` in Pillow's (cols, rows) order.
-    Returns a list of (xz, yz, xy) float32 tuples."""
+def arena_planes(images, sizes=(XZ_SIZE, YZ_SIZE, XY_SIZE)):
+    """Three (n, 1, S, S) image tensors in [-1, 1] -> three (n, rows, cols) float32 numpy arrays at the radar arena
+    (sgan.py:466-481): RADAR_MAX * (v + 1) / 2, then Pillow's BICUBIC (csrc/resize.hip, bit-identical to Pillow); ``sizes`` in
+    Pillow's (cols, rows) order."""
     from .common import RADAR_MAX
     from .nn_common import resize_bicubic
-    fake, _ = generate_fake_samples(generator, latent_dim, n, rng, return_numpy=False)
     planes = []
-    for v, (cols, rows) in zip(fake, sizes):
+    for v, (cols, rows) in zip(images, sizes):
         p = (float(RADAR_MAX) * (v[:, 0] + 1.0) / 2.0).contiguous()
         planes.append(resize_bicubic(p, (int(rows), int(cols)), scale=False).cpu().numpy())
+    return planes
+
+
+def generated_samples(generator, latent_dim, n, rng, sizes=(XZ_SIZE, YZ_SIZE, XY_SIZE), fused=False):
+    """The samples of ``summarize_performance`` (sgan.py:462-483): n fake images scaled to RADAR_MAX * (v + 1) / 2 and resized back
+    to the radar arena with Pillow's BICUBIC (csrc/resize.hip, bit-identical to Pillow); ``sizes`` in Pillow's (cols, rows) order.
+    Returns a list of (xz, yz, xy) float32 tuples.  ``fused``: as ``Generator.predict``."""
+    if fused:
+        fake, _ = generate_fake_samples(generator, latent_dim, n, rng, return_numpy=False, fused=True)
+    else:
+        fake, _ = generate_fake_samples(generator, latent_dim, n, rng, return_numpy=False)
+    planes = arena_planes(fake, sizes)
     return [(planes[0][i], planes[1][i], planes[2][i]) for i in range(n)]
+
+
+def generate_dataset(generator, n, latent_dim=100, rng=None, sizes=(XZ_SIZE, YZ_SIZE, XY_SIZE), batch_size=4096, path=None, fused=True):
+    """The generator's data product (``generated_data_XXXX.pickle``, sgan.py:462-488) at any n, in batches of ``batch_size``: per
+    batch the latent points (``rng``, this module's unless given), the images (``Generator.predict``; ``fused``: on the HIP chain
+    of csrc/gen_infer.hip), RADAR_MAX * (v + 1) / 2 and the Pillow-exact resize back to the arena (:func:`arena_planes`).  Returns
+    the list of (xz, yz, xy) float32 tuples, or -- with ``path`` -- writes :func:`save_generated`'s pickle and returns the number of
+    samples in it."""
+    rng = _rng(rng)
+    bs = max(1, int(batch_size))
+    samples = []
+    for s in range(0, int(n), bs):
+        nb = min(bs, int(n) - s)
+        z = generate_latent_points(latent_dim, nb, rng)
+        planes = arena_planes(generator.predict(z, return_numpy=False, fused=bool(fused)), sizes)
+        samples += [(planes[0][i], planes[1][i], planes[2][i]) for i in range(nb)]
+    if path is not None:
+        return save_generated(path, samples)
+    return samples
 
 
 def save_generated(path, samples):
@@ -1053,12 +1216,13 @@ def select_supervised_samples(dataset, rng, n_samples=150, n_classes=3):
 
 
 def train(g_model, disc_trainer, gan, train_set, val_set, n_classes, w_classes=None, latent_dim=100, n_epochs=15, n_batch=32,
-          results_dir=None, seed=1234):
+          results_dir=None, seed=1234, fused_generate=False):
     """The training loop of sgan.py:504-543: per step the four updates c, d on real samples, d on fake samples, g; per epoch the
     classifier's accuracy on ``val_set``, ``generated_data_%04d.pickle`` and the models (``.npz`` of ``keras_weights()``).
     ``train_set`` = (X (N, H, W, 3), y, sup), ``val_set`` = (X, y, ...).  The data set is uploaded once and batches are gathered
-    on the device; every draw comes from one ``np.random.default_rng(seed)``.  Returns the per-step (c_loss, c_acc, dr_loss,
-    df_loss, g_loss)."""
+    on the device; every draw comes from one ``np.random.default_rng(seed)``.  ``fused_generate``: the fake samples of the third
+    update and of the epoch's data product come from ``Generator.forward_fused`` (csrc/gen_infer.hip; same draws).  Returns the
+    per-step (c_loss, c_acc, dr_loss, df_loss, g_loss)."""
     import torch
     rng = np.random.default_rng(seed)
     dev = disc_trainer.device
@@ -1083,7 +1247,8 @@ def train(g_model, disc_trainer, gan, train_set, val_set, n_classes, w_classes=N
         ix = rng.integers(0, X.shape[0], half_batch)
         y_real = smooth_positive_labels(np.ones((half_batch, 1)), rng)
         dr_l = disc_trainer.train_on_batch_d(gather(ix), y_real, class_weight=w_classes)
-        x_fake, y_fake = generate_fake_samples(g_model, latent_dim, half_batch, rng, return_numpy=False, amp_dtype=disc_trainer.amp_dtype)
+        x_fake, y_fake = generate_fake_samples(g_model, latent_dim, half_batch, rng, return_numpy=False, amp_dtype=disc_trainer.amp_dtype,
+                                               fused=bool(fused_generate))
         df_l = disc_trainer.train_on_batch_d(x_fake, y_fake)
         z = generate_latent_points(latent_dim, n_batch, rng)
         g_l = gan.train_on_batch_g(z, smooth_positive_labels(np.ones((n_batch, 1)), rng))
@@ -1097,7 +1262,7 @@ def train(g_model, disc_trainer, gan, train_set, val_set, n_classes, w_classes=N
                 f1 = os.path.join(results_dir, "generated_data_%04d.pickle" % (i + 1))
                 f2 = os.path.join(results_dir, "g_model_%04d.npz" % (i + 1))
                 f3 = os.path.join(results_dir, "c_model_%04d.npz" % (i + 1))
-                save_generated(f1, generated_samples(g_model, latent_dim, 100, rng))
+                save_generated(f1, generated_samples(g_model, latent_dim, 100, rng, fused=bool(fused_generate)))
                 save_model_npz(f2, g_model)
                 save_model_npz(f3, disc_trainer.model)
                 logger.info("Saved: %s, %s, and %s" % (f1, f2, f3))
