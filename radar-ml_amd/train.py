@@ -1,15 +1,22 @@
-"""SVC hyperparameter search of the reference's ``train.py`` (``find_best_svm_estimator``, train.py:462-491) on GPU kernel matrices.
+"""The training side of the reference's ``train.py`` on the GPU: its SVC and SGD fits, their grid searches, its online loop.
 
-The reference runs ``GridSearchCV(SVC(probability=True, class_weight='balanced'))`` over 5 linear and 25 RBF points with 5 folds;
-libsvm spends nearly all of that time computing kernel values one pair at a time.  ``GridSearchSVC`` computes the inner products of
-the training rows once on the GPU (``rml_gram``, csrc/gram.hip), writes every kernel matrix the grid needs from them, and fits
-libsvm's ``SVC(kernel='precomputed')`` on slices of those matrices -- the same fits, on the same kernel values to the last few ulps.
-The winner comes back as a genuine ``sklearn.svm.SVC`` with kernel ``rbf`` or ``linear``, so everything after the search in the
-reference (``CalibratedClassifierCV(cv='prefit')``, the pickle, predict.py, ``from_sklearn``) works on it unchanged.
+Every estimator that leaves this module is a genuine scikit-learn one (``SVC``, ``SGDClassifier``, ``CalibratedClassifierCV``), so
+what the reference does with it afterwards (the pickle, predict.py, ``from_sklearn``) works unchanged.  In file order:
+
+* Device hooks: ``_gram`` (``rml_gram``: every kernel matrix of a grid from one upload), ``_smo`` (``smo_device``: libsvm's duals and
+  their held-out scores, batched, on matrices that stay on the device), ``_sgd`` (``sgd_device``: scikit-learn's SGD problems, batched)
+  and ``_sgd_online`` (``sgd_online_device``: a chain of partial_fit steps in one call).  All device work of the rest of the module
+  goes through these four names, looked up in the module at call time (tests replace them with NumPy twins).
+* Fits: ``fit_svc`` (``SVC.fit``, Platt step included), ``fit_sgd`` / ``partial_fit_sgd`` and the chain ``partial_fit_sgd_steps``.
+* Searches: ``GridSearchSVC`` and ``GridSearchSGD`` on one ``GridSearchCV`` scaffold, inside the reference's ``find_best_*``.
+* Flows: ``sgd_fit`` / ``svc_fit`` of the reference (features, ``balance_classes``, augment epochs, search or online chain).
+* Calibration and evaluation: ``calibrate_prefit`` and ``evaluate_model``.
 """
 import logging
 import time
+from collections import namedtuple
 from concurrent.futures import ThreadPoolExecutor
+from types import SimpleNamespace
 
 import numpy as np
 
@@ -17,13 +24,15 @@ from . import _lib
 
 logger = logging.getLogger(__name__)
 
-_GRID_KEYS = ("C", "kernel", "gamma")
-# SVC constructor parameters that carry from the base estimator into every fit
-_CARRY = ("C", "probability", "class_weight", "random_state", "cache_size", "tol", "shrinking", "max_iter",
-          "decision_function_shape", "break_ties")
+RANDOM_SEED = 1234                      # train.py:32
 _NONFINITE = "Input contains NaN, infinity or a value too large for dtype('float64')."      # scikit-learn's message
 
 
+def _cat_i32(parts):
+    return np.concatenate(parts).astype(np.int32) if parts else np.zeros(0, np.int32)
+
+
+# ---- device hooks: the Gram pass and libsvm's duals on it (rml_gram, rml_smo_solve / rml_smo_score) --------------------------------
 def _gram_device(X, kernels, dev):
     """``rml_gram`` of the float32 host rows ``X`` for ``kernels``: a DEVICE (len(kernels), N, N) float64 tensor."""
     import torch
@@ -128,6 +137,194 @@ def _smo(X, kernels, plan, device=None):
     return out
 
 
+# ---- device hooks: scikit-learn's SGD problems, batched (rml_sgd_solve / rml_sgd_score) --------------------------------------------
+# rml_sgd_problem / rml_sgd_fit of include/radarml.h
+SGD_PROBLEM = np.dtype([("n", "<i4"), ("penalty", "<i4"), ("average", "<i4"), ("max_iter", "<i4"), ("n_iter_no_change", "<i4"),
+                        ("shuffle", "<i4"), ("seed", "<u4"), ("warm", "<i4"), ("rows_off", "<i8"), ("y_off", "<i8"), ("out", "<i8"),
+                        ("alpha", "<f8"), ("l1_ratio", "<f8"), ("tol", "<f8"), ("weight_pos", "<f8"), ("weight_neg", "<f8"), ("t0", "<f8")])
+SGD_FIT = np.dtype([("prob0", "<i4"), ("n_test", "<i4"), ("test_off", "<i8")])
+_SGD_PENALTY = {"l1": _lib.SGD_L1, "l2": _lib.SGD_L2, "elasticnet": _lib.SGD_ELASTICNET}
+
+
+def sgd_shuffle(seed, perm):
+    """``rml_sgd_shuffle``: one ``SequentialDataset.shuffle(seed)`` pass (Fisher-Yates on scikit-learn's xorshift generator) over the
+    int32 index array ``perm``; returns the permuted copy."""
+    perm = np.array(perm, dtype=np.int32)
+    _lib.check(_lib.load().rml_sgd_shuffle(int(seed), len(perm), perm.ctypes.data), "rml_sgd_shuffle")
+    return perm
+
+
+def _device_rows(who, Xd, device):
+    """(dev, ctx, N, D, ld) for the C calls of ``who`` on the DEVICE rows ``Xd``; ld is the row stride."""
+    import torch
+    dev = _lib.device_of(device if device is not None else Xd.device)
+    ctx = _lib.context(dev)
+    if Xd.dtype != torch.float32 or Xd.dim() != 2 or Xd.stride(1) != 1 or Xd.stride(0) < Xd.shape[1]:
+        raise ValueError("%s: the rows are an (N, D) float32 tensor with unit column stride" % who)
+    return dev, ctx, int(Xd.shape[0]), int(Xd.shape[1]), int(Xd.stride(0))
+
+
+def sgd_device(Xd, plan, device=None, check=True):
+    """``rml_sgd_solve`` + ``rml_sgd_score`` on the DEVICE rows ``Xd`` (an (N, D) float32 tensor with unit column stride; its row
+    stride is the ld of the C call) for ``plan``: a dict of
+    ``problems`` (SGD_PROBLEM records), ``rows`` / ``y`` (int32: the problems' rows and 0 / 1 labels), ``n_out`` (output slots),
+    ``fits`` (SGD_FIT records), ``test_rows`` / ``test_y`` (int32: held-out rows and their class indices), ``n_classes`` and, for
+    warm problems, ``init``: host arrays ``coef`` / ``avg_coef`` (n_out, D) and ``intercept`` / ``avg_intercept`` (n_out).
+    Returns host arrays ``intercept``, ``avg_intercept``, ``n_iter``, ``t``, ``status`` per slot, ``dec``, ``labels`` per held-out
+    row, ``correct`` per fit, ``solve_s`` / ``score_s`` (the wall time of the two batched calls), and ``coefs``: a function
+    slots -> host (coef, avg_coef) of those slots (the weights stay on the device until asked for).  A problem or a held-out row
+    that names a row outside the matrix raises RadarMLError (``check=False``: status -1 / label -1 are returned instead)."""
+    import torch
+    lib = _lib.load()
+    dev, ctx, N, D, ld = _device_rows("sgd_device", Xd, device)
+    probs = np.ascontiguousarray(plan["problems"], dtype=SGD_PROBLEM)
+    fits = np.ascontiguousarray(plan.get("fits", np.zeros(0, SGD_FIT)), dtype=SGD_FIT)
+    n_out = int(plan["n_out"])
+    C = int(plan.get("n_classes", 2))
+    n_dec = 1 if C == 2 else C
+    with torch.cuda.device(dev):
+        i32 = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(dev)
+        rows, y = i32(plan["rows"]), i32(plan["y"])
+        te_rows, te_y = i32(plan.get("test_rows", np.zeros(0, np.int32))), i32(plan.get("test_y", np.zeros(0, np.int32)))
+        n_test = int(te_rows.numel())
+        init = plan.get("init")
+        f64 = lambda a, shape: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64).reshape(shape)).to(dev)
+        if init is None:
+            coef = torch.zeros((max(n_out, 1), D), dtype=torch.float64, device=dev)
+            avg_coef = torch.zeros_like(coef)
+            icpt = torch.zeros(max(n_out, 1), dtype=torch.float64, device=dev)
+            avg_icpt = torch.zeros_like(icpt)
+        else:
+            coef, avg_coef = f64(init["coef"], (n_out, D)), f64(init["avg_coef"], (n_out, D))
+            icpt, avg_icpt = f64(init["intercept"], (n_out,)), f64(init["avg_intercept"], (n_out,))
+        n_iter = torch.zeros(max(n_out, 1), dtype=torch.int32, device=dev)
+        t = torch.zeros(max(n_out, 1), dtype=torch.float64, device=dev)
+        status = torch.zeros(max(n_out, 1), dtype=torch.int32, device=dev)
+        dec = torch.zeros(max(n_test * n_dec, 1), dtype=torch.float64, device=dev)
+        labels = torch.zeros(max(n_test, 1), dtype=torch.int32, device=dev)
+        correct = torch.zeros(max(len(fits), 1), dtype=torch.int32, device=dev)
+        st = _lib.stream_ptr(dev)
+        torch.cuda.synchronize(dev)
+        t0 = time.perf_counter()
+        _lib.check(lib.rml_sgd_solve(ctx, _lib.ptr(Xd), N, D, ld, probs.ctypes.data, len(probs), _lib.ptr(rows), int(rows.numel()),
+                                     _lib.ptr(y), int(y.numel()), n_out, _lib.ptr(coef), _lib.ptr(avg_coef), _lib.ptr(icpt),
+                                     _lib.ptr(avg_icpt), _lib.ptr(n_iter), _lib.ptr(t), _lib.ptr(status), st), "rml_sgd_solve")
+        torch.cuda.synchronize(dev)
+        t1 = time.perf_counter()
+        if len(fits):
+            _lib.check(lib.rml_sgd_score(ctx, _lib.ptr(Xd), N, D, ld, probs.ctypes.data, len(probs), n_out, _lib.ptr(coef),
+                                         _lib.ptr(avg_coef), _lib.ptr(icpt), _lib.ptr(avg_icpt), _lib.ptr(t), C, fits.ctypes.data,
+                                         len(fits), _lib.ptr(te_rows), _lib.ptr(te_y), n_test, _lib.ptr(dec), _lib.ptr(labels),
+                                         _lib.ptr(correct), st), "rml_sgd_score")
+        torch.cuda.synchronize(dev)
+        t2 = time.perf_counter()
+
+        def coefs(slots):
+            with torch.cuda.device(dev):
+                idx = torch.as_tensor(list(slots), dtype=torch.long, device=dev)
+                return coef[idx].cpu().numpy(), avg_coef[idx].cpu().numpy()
+
+        out = {"intercept": icpt.cpu().numpy()[:n_out], "avg_intercept": avg_icpt.cpu().numpy()[:n_out],
+               "n_iter": n_iter.cpu().numpy()[:n_out], "t": t.cpu().numpy()[:n_out], "status": status.cpu().numpy()[:n_out],
+               "dec": dec.cpu().numpy()[:n_test * n_dec].reshape(n_test, n_dec), "labels": labels.cpu().numpy()[:n_test],
+               "correct": correct.cpu().numpy()[:len(fits)], "solve_s": t1 - t0, "score_s": t2 - t1, "coefs": coefs}
+    if check and (out["status"][probs["out"]] < 0).any():
+        raise _lib.RadarMLError("rml_sgd_solve: a problem names a row outside the matrix")
+    if check and (out["labels"] < 0).any():
+        raise _lib.RadarMLError("rml_sgd_score: a held-out row outside the matrix")
+    return out
+
+
+def _sgd(X, plan, device=None):
+    """The float32 host rows ``X`` uploaded ONCE, every problem of ``plan`` solved on them in one ``rml_sgd_solve`` call and every
+    held-out row scored in one ``rml_sgd_score`` call (``sgd_device``).  Returns ``sgd_device``'s dict plus ``solve``: a function
+    plan -> ``sgd_device``'s dict of another plan on the same resident rows (the refit of a search's winner).
+
+    All device work of the SGD fits and of their search goes through this function (tests replace it to run the logic without a GPU)."""
+    import torch
+    dev = _lib.device_of(device)
+    with torch.cuda.device(dev):
+        Xd = torch.from_numpy(np.ascontiguousarray(X, dtype=np.float32)).to(dev)
+        out = sgd_device(Xd, plan, dev)
+    out["solve"] = lambda plan2: sgd_device(Xd, plan2, dev)
+    return out
+
+
+# ---- device hooks: a chain of partial_fit calls resident on the device (rml_sgd_online) --------------------------------------------
+# rml_sgd_step of include/radarml.h
+SGD_STEP = np.dtype([("off", "<i8"), ("n", "<i4"), ("score", "<i4"), ("seed", "<u4", (8,))])
+
+
+def sgd_online_device(Xd, plan, device=None, check=True, fill=None):
+    """``rml_sgd_online`` on the DEVICE rows ``Xd`` (as ``sgd_device`` takes them) for ``plan``: a dict of ``problems`` (K SGD_PROBLEM
+    records of one estimator, class order; K = 1 for two classes), ``n_classes``, ``steps`` (SGD_STEP records), ``rows`` / ``cls``
+    (int32: the steps' rows and their class indices), ``test_rows`` / ``test_y`` (int32, optional), ``init`` (host ``coef`` /
+    ``avg_coef`` (K, D), ``intercept`` / ``avg_intercept`` (K): the state of problem k, stored at its slot), ``avg_flag`` and
+    optionally ``n_out`` (output slots, default K).  Returns host arrays per PROBLEM ``coef``, ``avg_coef``, ``intercept``,
+    ``avg_intercept``, ``t``, ``status``, and ``avg_flag``, ``fail_step``, ``correct`` (per step), ``labels`` / ``dec`` (of the last
+    scored step).  Two uploads, one call, two copies back: the only wait is for those.  A row outside the matrix raises
+    RadarMLError (``check=False``: status -1 is returned).  ``fill``: what the outputs without an initial value hold before the
+    call (default 0)."""
+    import torch
+    lib = _lib.load()
+    dev, ctx, N, D, ld = _device_rows("sgd_online_device", Xd, device)
+    probs = np.ascontiguousarray(plan["problems"], dtype=SGD_PROBLEM)
+    steps = np.ascontiguousarray(plan["steps"], dtype=SGD_STEP)
+    C = int(plan["n_classes"])
+    K, n_dec, S = len(probs), (1 if C == 2 else C), len(steps)
+    if K != n_dec:
+        raise ValueError("sgd_online_device: %d problems for %d classes" % (K, C))
+    n_out = int(plan.get("n_out", K))
+    out = probs["out"].astype(np.int64)
+    if ((out < 0) | (out >= n_out)).any():
+        raise ValueError("sgd_online_device: an output slot outside [0, %d)" % n_out)
+    i32 = lambda a: np.ascontiguousarray(a, dtype=np.int32).ravel()
+    rows, cls = i32(plan["rows"]), i32(plan["cls"])
+    te_rows, te_y = i32(plan.get("test_rows", [])), i32(plan.get("test_y", []))
+    n_test = len(te_rows)
+    init = plan["init"]
+    fill = 0 if fill is None else fill
+    # one float64 and one int32 block hold every in / out array: [coef | avg_coef | intercept | avg_intercept | t | dec] and
+    # [status | avg_flag | fail_step | correct | labels | rows | cls | test_rows | test_y]
+    f_off = np.cumsum([0, n_out * D, n_out * D, n_out, n_out, n_out, max(n_test * n_dec, 1)])
+    hf = np.full(int(f_off[-1]), float(fill))
+    for name, j, width in (("coef", 0, D), ("avg_coef", 1, D), ("intercept", 2, 1), ("avg_intercept", 3, 1)):
+        hf[f_off[j]:f_off[j + 1]].reshape(n_out, width)[out] = np.asarray(init[name], dtype=np.float64).reshape(K, width)
+    i_off = np.cumsum([0, n_out, 1, 1, max(S, 1), max(n_test, 1), max(len(rows), 1), max(len(cls), 1), max(n_test, 1), max(n_test, 1)])
+    hi = np.full(int(i_off[-1]), int(fill), dtype=np.int32)
+    hi[i_off[1]] = int(bool(plan.get("avg_flag", False)))
+    for j, a in ((5, rows), (6, cls), (7, te_rows), (8, te_y)):
+        hi[i_off[j]:i_off[j] + len(a)] = a
+    with torch.cuda.device(dev):
+        df, di = torch.from_numpy(hf).to(dev), torch.from_numpy(hi).to(dev)
+        fp = lambda j: _lib.ptr(df[int(f_off[j]):])
+        ip = lambda j: _lib.ptr(di[int(i_off[j]):])
+        _lib.check(lib.rml_sgd_online(ctx, _lib.ptr(Xd), N, D, ld, probs.ctypes.data, C, steps.ctypes.data, S, ip(5), ip(6), len(rows),
+                                      ip(7), ip(8), n_test, n_out, fp(0), fp(1), fp(2), fp(3), fp(4), ip(1), ip(0), ip(2), ip(3), ip(4), fp(5),
+                                      _lib.stream_ptr(dev)), "rml_sgd_online")
+        rf, ri = df.cpu().numpy(), di[:int(i_off[5])].cpu().numpy()
+    f = lambda j, width: rf[f_off[j]:f_off[j + 1]].reshape(n_out, width)[out]
+    res = {"coef": f(0, D), "avg_coef": f(1, D), "intercept": f(2, 1)[:, 0], "avg_intercept": f(3, 1)[:, 0], "t": f(4, 1)[:, 0],
+           "status": ri[:n_out][out], "avg_flag": bool(ri[i_off[1]]), "fail_step": int(ri[i_off[2]]), "correct": ri[i_off[3]:i_off[3] + S],
+           "labels": ri[i_off[4]:i_off[4] + n_test], "dec": rf[f_off[5]:f_off[5] + n_test * n_dec].reshape(n_test, n_dec)}
+    if check and (res["status"] < 0).any():
+        raise _lib.RadarMLError("rml_sgd_online: a step or the held-out list names a row outside the matrix")
+    return res
+
+
+def _sgd_online(X, plan, device=None):
+    """The rows ``X`` (float32 host rows, uploaded ONCE, or a CUDA tensor taken where it is) and the whole chain of partial_fit steps
+    of ``plan`` in one ``rml_sgd_online`` call (``sgd_online_device``).
+
+    All device work of ``partial_fit_sgd_steps`` goes through this function (tests replace it to run the logic without a GPU)."""
+    import torch
+    dev = _lib.device_of(device if device is not None or not isinstance(X, torch.Tensor) else X.device)
+    with torch.cuda.device(dev):
+        Xd = X.to(dev) if isinstance(X, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(X, dtype=np.float32)).to(dev)
+        return sgd_online_device(Xd, plan, dev)
+
+
+# ---- argument checks shared by the fits and the searches (before any device work) -------------------------------------------------
 def _rows(X):
     """The training rows as a float32 host array, validated on the host with scikit-learn's messages."""
     try:
@@ -151,56 +348,28 @@ def _rows(X):
     return X32
 
 
-def _sklearn_gamma(gamma, X64):
-    """``SVC._gamma`` as ``SVC.fit`` computes it (sklearn/svm/_base.py)."""
-    if isinstance(gamma, str):
-        if gamma == "scale":
-            var = X64.var()
-            return 1.0 / (X64.shape[1] * var) if var != 0 else 1.0
-        if gamma == "auto":
-            return 1.0 / X64.shape[1]
-        raise ValueError("gamma %r" % gamma)
-    return gamma
+def _check_y(X32, y):
+    y = np.asarray(y)
+    if y.ndim != 1 or y.shape[0] != X32.shape[0]:
+        raise ValueError("Found input variables with inconsistent numbers of samples: [%d, %d]" % (X32.shape[0], len(y)))
+    return y
 
 
-def _masked_params(candidates):
-    """``param_*`` entries of ``cv_results_`` (GridSearchCV's layout: one masked array per parameter)."""
-    vals = {}
-    for i, p in enumerate(candidates):
-        for name, v in p.items():
-            vals.setdefault("param_%s" % name, {})[i] = v
-    out = {}
-    for key, d in vals.items():
-        arr = np.array(list(d.values()))
-        dtype = arr.dtype if arr.dtype.kind != "U" and arr.ndim == 1 else object
-        ma = np.ma.MaskedArray(np.empty(len(candidates), dtype=dtype), mask=True)
-        for i, v in d.items():
-            ma[i] = v
-        out[key] = ma
-    return out
+def _check_kernel(who, kernel, gamma, C):
+    if kernel not in ("linear", "rbf"):
+        raise NotImplementedError("%s: kernel %r (the HIP Gram pass computes 'linear' and 'rbf')" % (who, kernel))
+    if kernel == "rbf":
+        if isinstance(gamma, str):
+            raise NotImplementedError("%s: gamma=%r depends on each fold's rows; give numeric gammas" % (who, gamma))
+        if not np.isfinite(float(gamma)) or float(gamma) < 0:
+            raise ValueError("%s: gamma must be a finite non-negative number, got %r" % (who, gamma))
+    if not float(C) > 0:
+        raise ValueError("%s: C must be > 0, got %r" % (who, C))
 
 
-def _cv_results(candidates, n_splits, fit_t, score_t, scores):
-    """``cv_results_`` in GridSearchCV's layout from (candidate, split) arrays of fit times, score times and test scores."""
-    res = {}
-
-    def store(name, arr, splits_=False, rank=False):
-        if splits_:
-            for s in range(n_splits):
-                res["split%d_%s" % (s, name)] = arr[:, s]
-        mean = np.average(arr, axis=1)
-        res["mean_%s" % name] = mean
-        res["std_%s" % name] = np.sqrt(np.average((arr - mean[:, None]) ** 2, axis=1))
-        if rank:
-            from scipy.stats import rankdata
-            res["rank_%s" % name] = rankdata(-mean, method="min").astype(np.int32, copy=False)
-
-    store("fit_time", fit_t)
-    store("score_time", score_t)
-    res.update(_masked_params(candidates))
-    res["params"] = candidates
-    store("test_score", scores, splits_=True, rank=True)
-    return res
+def _kernel_key(kernel, gamma):
+    """The kernel of a checked (kernel, gamma) as ``_gram`` / ``_smo`` name it."""
+    return ("linear", None) if kernel == "linear" else ("rbf", float(gamma))
 
 
 # ---- SVC.fit as one batch of duals: libsvm's svm_train with its Platt cross-validation (sk: = sklearn/svm/src/libsvm/svm.cpp) ----
@@ -285,9 +454,8 @@ def _fit_plan(yi, nc, wC, seed, probability, shrinking, max_iter, tol, matrix=0)
                 held.append((p, te, n_test))
                 n_test += len(te)
         const_dec.append(dec0)
-    cat = lambda parts: np.concatenate(parts).astype(np.int32) if parts else np.zeros(0, np.int32)
-    plan = {"problems": np.array(problems, dtype=SMO_PROBLEM), "rows": cat(rows), "fits": np.array(fits, dtype=SMO_FIT),
-            "test_rows": cat(test_rows), "test_y": np.zeros(n_test, np.int32), "n_classes": 2}
+    plan = {"problems": np.array(problems, dtype=SMO_PROBLEM), "rows": _cat_i32(rows), "fits": np.array(fits, dtype=SMO_FIT),
+            "test_rows": _cat_i32(test_rows), "test_y": np.zeros(n_test, np.int32), "n_classes": 2}
     meta = {"pairs": pairs, "cls_rows": cls_rows, "rows": pair_rows, "const_dec": const_dec, "held": held}
     return plan, meta
 
@@ -367,6 +535,18 @@ def _fit_batch(params, y, run, matrix=0):
     return fitted
 
 
+def _sklearn_gamma(gamma, X64):
+    """``SVC._gamma`` as ``SVC.fit`` computes it (sklearn/svm/_base.py)."""
+    if isinstance(gamma, str):
+        if gamma == "scale":
+            var = X64.var()
+            return 1.0 / (X64.shape[1] * var) if var != 0 else 1.0
+        if gamma == "auto":
+            return 1.0 / X64.shape[1]
+        raise ValueError("gamma %r" % gamma)
+    return gamma
+
+
 def _adopt(est, fitted, X32, key):
     """Turn the ``linear`` / ``rbf`` estimator ``est`` into the fitted one from the fitted attributes of its precomputed-kernel twin
     on the rows ``X32``: the support vectors are the training rows, shape and gamma are those of a fit on the rows."""
@@ -377,18 +557,6 @@ def _adopt(est, fitted, X32, key):
     est.n_features_in_ = X32.shape[1]
     est._gamma = _sklearn_gamma(est.gamma, X64) if key[0] == "linear" else est.gamma
     return est
-
-
-def _check_kernel(who, kernel, gamma, C):
-    if kernel not in ("linear", "rbf"):
-        raise NotImplementedError("%s: kernel %r (the HIP Gram pass computes 'linear' and 'rbf')" % (who, kernel))
-    if kernel == "rbf":
-        if isinstance(gamma, str):
-            raise NotImplementedError("%s: gamma=%r depends on each fold's rows; give numeric gammas" % (who, gamma))
-        if not np.isfinite(float(gamma)) or float(gamma) < 0:
-            raise ValueError("%s: gamma must be a finite non-negative number, got %r" % (who, gamma))
-    if not float(C) > 0:
-        raise ValueError("%s: C must be > 0, got %r" % (who, C))
 
 
 def fit_svc(estimator, X, y, device=None):
@@ -404,421 +572,15 @@ def fit_svc(estimator, X, y, device=None):
     params = estimator.get_params()
     _check_kernel("fit_svc", params["kernel"], params["gamma"], params["C"])
     X32 = _rows(X)
-    y = np.asarray(y)
-    if y.ndim != 1 or y.shape[0] != X32.shape[0]:
-        raise ValueError("Found input variables with inconsistent numbers of samples: [%d, %d]" % (X32.shape[0], len(y)))
-    key = ("linear", None) if params["kernel"] == "linear" else ("rbf", float(params["gamma"]))
+    y = _check_y(X32, y)
+    key = _kernel_key(params["kernel"], params["gamma"])
     fitted = _fit_batch({k: params[k] for k in _FIT_CARRY}, y, lambda plan: _smo(X32, [key], plan, device))
     return _adopt(estimator, fitted, X32, key)
 
 
-class GridSearchSVC:
-    """``GridSearchCV(SVC(...), param_grid)`` for C, ``linear`` / ``rbf`` kernels and numeric gamma, on GPU kernel matrices.
-
-    The subset of ``GridSearchCV``'s surface that train.py uses: ``fit(X, y)``, ``best_estimator_``, ``best_params_``, ``best_score_``,
-    ``best_index_``, ``cv_results_``, ``n_splits_``, ``refit_time_``, ``scorer_`` (accuracy).  Fit order: rows validated; every distinct
-    kernel of the grid computed by ``rml_gram`` (grouped so that the host copies stay under ``max_gram_bytes``); the candidates in
-    ``ParameterGrid`` order x the splits fitted by libsvm on ``K[train, train]`` and scored on ``K[test, train]`` on a pool of
-    ``n_jobs`` threads (libsvm releases the GIL); the best point refitted on all rows.
-
-    ``solver="device"`` keeps the kernel matrices on the GPU and replaces the host fits and scores of the search: per group of
-    kernels, every candidate x split x class-pair dual is solved by ONE ``rml_smo_solve`` call (libsvm's SMO, one workgroup per
-    dual, the same iterates bit for bit) and every held-out row is scored by ONE ``rml_smo_score`` call; only the winner's matrix
-    is copied back, for the same host refit (``probability`` and libsvm's Platt step included).  ``tol``, ``shrinking``,
-    ``max_iter`` and ``class_weight`` of the base estimator are honoured (weighted C as scikit-learn forms it: ``compute_class_weight``
-    on the fold's labels, times C).  A split whose training rows miss a class is fitted on the host as before.  The batch has no
-    per-fit times: ``fit_time`` / ``score_time`` of a device fit are the batch's solve / score time divided evenly among its fits.
-    ``solver="host"`` (the default) is the search described above.
-
-    ``refit_solver="device"`` refits the winner on the GPU as well (``fit_svc``'s batch: the duals of libsvm's fit and of its Platt
-    cross-validation in one ``rml_smo_solve`` call, ``rml_platt_fit`` per class pair) -- after a device search on the matrix still
-    resident there, so that no kernel matrix is copied back at all.  The estimator is the same, bit for bit.
-    ``refit_solver="host"`` (the default) is libsvm's fit on the host copy of the winner's matrix."""
-
-    def __init__(self, estimator, param_grid, cv=5, n_jobs=4, refit=True, device=None, max_gram_bytes=8 << 30, scoring=None,
-                 verbose=0, solver="host", refit_solver="host"):
-        self.estimator = estimator
-        self.param_grid = param_grid
-        self.cv = cv
-        self.n_jobs = n_jobs
-        self.refit = refit
-        self.device = device
-        self.max_gram_bytes = max_gram_bytes
-        self.scoring = scoring
-        self.verbose = verbose
-        self.solver = solver
-        self.refit_solver = refit_solver
-
-    # ---- argument checks (before any work) ----
-    def _check(self):
-        from sklearn.model_selection import ParameterGrid
-        from sklearn.svm import SVC
-        if self.solver not in ("host", "device"):
-            raise ValueError("GridSearchSVC: solver must be 'host' or 'device', got %r" % (self.solver,))
-        if self.refit_solver not in ("host", "device"):
-            raise ValueError("GridSearchSVC: refit_solver must be 'host' or 'device', got %r" % (self.refit_solver,))
-        if type(self.estimator) is not SVC:
-            raise NotImplementedError("GridSearchSVC searches sklearn.svm.SVC, not %s" % type(self.estimator).__name__)
-        if self.scoring not in (None, "accuracy"):
-            raise NotImplementedError("GridSearchSVC scores by accuracy (SVC.score, GridSearchCV's default), not %r" % (self.scoring,))
-        if callable(self.refit) or not isinstance(self.refit, bool):
-            raise NotImplementedError("GridSearchSVC: refit must be True or False, not %r" % (self.refit,))
-        grids = [self.param_grid] if isinstance(self.param_grid, dict) else list(self.param_grid)
-        for g in grids:
-            bad = sorted(set(g) - set(_GRID_KEYS))
-            if bad:
-                raise NotImplementedError("GridSearchSVC searches %s, not %s" % (", ".join(_GRID_KEYS), ", ".join(bad)))
-        candidates = list(ParameterGrid(self.param_grid))
-        base = self.estimator.get_params()
-        for p in candidates:
-            kernel = p.get("kernel", base["kernel"])
-            gamma = p.get("gamma", base["gamma"])
-            if kernel not in ("linear", "rbf"):
-                raise NotImplementedError("GridSearchSVC: kernel %r (the HIP Gram pass computes 'linear' and 'rbf')" % (kernel,))
-            if kernel == "rbf":
-                if isinstance(gamma, str):
-                    raise NotImplementedError("GridSearchSVC: gamma=%r depends on each fold's rows; give numeric gammas" % gamma)
-                if not np.isfinite(float(gamma)) or float(gamma) < 0:
-                    raise ValueError("GridSearchSVC: gamma must be a finite non-negative number, got %r" % (gamma,))
-            if not float(p.get("C", base["C"])) > 0:
-                raise ValueError("GridSearchSVC: C must be > 0, got %r" % (p.get("C", base["C"]),))
-        return candidates, base
-
-    def _key(self, p, base):
-        kernel = p.get("kernel", base["kernel"])
-        return ("linear", None) if kernel == "linear" else ("rbf", float(p.get("gamma", base["gamma"])))
-
-    def _svc(self, p, base, kernel, probability=None):
-        from sklearn.svm import SVC
-        kw = {k: base[k] for k in _CARRY}
-        kw["C"] = p.get("C", base["C"])
-        if probability is not None:
-            kw["probability"] = probability
-        return SVC(kernel=kernel, **kw)
-
-    def _smo_plan(self, candidates, base, grp, splits, y):
-        """The batch of one group of kernels for ``_smo``: per candidate of the group (ParameterGrid order) and split, one fit made of
-        one dual per class pair in libsvm's order.  Returns (plan, [(ci, si) of fit f], [(ci, si) left to the host])."""
-        from sklearn.utils.class_weight import compute_class_weight
-        classes = np.unique(y)
-        nc = len(classes)
-        yi = np.searchsorted(classes, y).astype(np.int32)
-        pairs = [(a, b) for a in range(nc) for b in range(a + 1, nc)]
-        rows, test_rows, test_y = [], [], []
-        per_split = {}                      # si -> ([(rows_off, l, n_pos) per pair], class weights)
-        n_rows = 0
-        for si, (tr, te) in enumerate(splits):
-            if not 2 <= nc <= 8 or len(np.unique(yi[tr])) < nc or len(te) == 0:
-                continue                    # a class without rows in this fold: libsvm fits another model -- the host path's job
-            cw = base["class_weight"]
-            w = np.ones(nc) if cw is None else compute_class_weight(cw, classes=classes, y=y[tr])
-            subs = []
-            for a, b in pairs:
-                ra, rb = tr[yi[tr] == a], tr[yi[tr] == b]
-                rows += [ra, rb]
-                subs.append((n_rows, len(ra) + len(rb), len(ra)))
-                n_rows += len(ra) + len(rb)
-            per_split[si] = (subs, w)
-        problems, fits, on_device, host = [], [], [], []
-        n_alpha = n_test = 0
-        for ci, p in enumerate(candidates):
-            key = self._key(p, base)
-            if key not in grp:
-                continue
-            C = float(p.get("C", base["C"]))
-            for si, (tr, te) in enumerate(splits):
-                if si not in per_split:
-                    host.append((ci, si))
-                    continue
-                subs, w = per_split[si]
-                fits.append((len(problems), len(te), n_test))
-                on_device.append((ci, si))
-                test_rows.append(te)
-                test_y.append(yi[te])
-                n_test += len(te)
-                for (off, l, n_pos), (a, b) in zip(subs, pairs):
-                    problems.append((grp.index(key), l, n_pos, int(bool(base["shrinking"])), int(base["max_iter"]), 0, off, n_alpha,
-                                     C * w[a], C * w[b], float(base["tol"])))
-                    n_alpha += l
-        cat = lambda parts: np.concatenate(parts).astype(np.int32) if parts else np.zeros(0, np.int32)
-        plan = {"problems": np.array(problems, dtype=SMO_PROBLEM), "rows": cat(rows), "fits": np.array(fits, dtype=SMO_FIT),
-                "test_rows": cat(test_rows), "test_y": cat(test_y), "n_classes": nc}
-        return plan, on_device, host
-
-    def fit(self, X, y):
-        from sklearn.base import clone
-        from sklearn.metrics import accuracy_score, make_scorer
-        from sklearn.model_selection import check_cv
-        candidates, base = self._check()
-        X32 = _rows(X)
-        y = np.asarray(y)
-        if y.ndim != 1 or y.shape[0] != X32.shape[0]:
-            raise ValueError("Found input variables with inconsistent numbers of samples: [%d, %d]" % (X32.shape[0], len(y)))
-        N, D = X32.shape
-        cv = check_cv(self.cv, y, classifier=True)
-        splits = [(np.asarray(tr), np.asarray(te)) for tr, te in cv.split(X32, y)]
-        n_splits = len(splits)
-        if n_splits == 0:
-            raise ValueError("No fits were performed. Was the CV iterator empty? Were there no candidates?")
-        if not candidates:
-            raise ValueError("No fits were performed. Was the CV iterator empty? Were there no candidates?")
-
-        keys = []
-        for p in candidates:
-            k = self._key(p, base)
-            if k not in keys:
-                keys.append(k)
-        mat_bytes = N * N * 8
-        per = min(8, int(self.max_gram_bytes // mat_bytes))
-        if per < 1:
-            raise ValueError("GridSearchSVC: one %d x %d kernel matrix takes %d bytes, more than max_gram_bytes=%d"
-                             % (N, N, mat_bytes, self.max_gram_bytes))
-        groups = [keys[i:i + per] for i in range(0, len(keys), per)]
-        # joblib's convention (what GridSearchCV's n_jobs means): None -> 1, -1 -> every CPU this process may use, -2 -> all but one;
-        # joblib counts the CPUs of the process's affinity mask and cgroup quota, not the whole machine's
-        from joblib import effective_n_jobs
-        nj = max(1, min(effective_n_jobs(self.n_jobs), len(candidates) * n_splits))
-        if self.verbose > 0:
-            print("Fitting %d folds for each of %d candidates, totalling %d fits" % (n_splits, len(candidates),
-                                                                                   n_splits * len(candidates)), flush=True)
-
-        scores = np.zeros((len(candidates), n_splits))
-        fit_t = np.zeros_like(scores)
-        score_t = np.zeros_like(scores)
-
-        # The split fits run WITHOUT libsvm's Platt step (probability=False), whatever the base estimator says: the score is
-        # accuracy of predict(), which does not use the Platt parameters, and the SMO solve is the same either way (libsvm fits
-        # the pairwise models independently of the Platt cross-validation), so decision values and split scores are the bits
-        # GridSearchCV gets -- at a sixth of the SMO work.  It also keeps libsvm's process-wide random generator (used only by
-        # that cross-validation, outside the GIL) out of the concurrent fits.  The refit below keeps the base estimator's setting.
-        def one(K, ci, si):
-            tr, te = splits[si]
-            est = self._svc(candidates[ci], base, "precomputed", probability=False)
-            t0 = time.perf_counter()
-            est.fit(K[np.ix_(tr, tr)], y[tr])
-            t1 = time.perf_counter()
-            s = est.score(K[np.ix_(te, tr)], y[te])
-            t2 = time.perf_counter()
-            scores[ci, si], fit_t[ci, si], score_t[ci, si] = s, t1 - t0, t2 - t1
-            if self.verbose > 1:
-                p = candidates[ci]
-                print("[CV %d/%d] END %s; total time=%5.1fs" % (si + 1, n_splits, ", ".join("%s=%s" % (k, p[k]) for k in sorted(p)),
-                                                             t2 - t0), flush=True)
-
-        mats = {}
-        fetch = {}                              # device search: kernel key -> function returning its host matrix (last group only)
-        resident = {}                           # device search: kernel key -> (matrix index, solve hook) of the resident matrices (same)
-        with ThreadPoolExecutor(max_workers=nj) as pool:
-            for grp in groups:
-                todo = [(ci, si) for ci, p in enumerate(candidates) if self._key(p, base) in grp for si in range(n_splits)]
-                if self.solver == "device":
-                    plan, on_device, todo = self._smo_plan(candidates, base, grp, splits, y)
-                    out = _smo(X32, grp, plan, self.device)
-                    fetch = {k: (lambda i=i, m=out["matrix"]: m(i)) for i, k in enumerate(grp)}
-                    resident = {k: (i, out["solve"]) for i, k in enumerate(grp)} if "solve" in out else {}
-                    mats = {}
-                    for f, (ci, si) in enumerate(on_device):
-                        scores[ci, si] = float(out["correct"][f]) / len(splits[si][1])
-                        fit_t[ci, si] = out["solve_s"] / len(on_device)
-                        score_t[ci, si] = out["score_s"] / len(on_device)
-                        if self.verbose > 1:
-                            p = candidates[ci]
-                            print("[CV %d/%d] END %s; total time=%5.1fs" % (si + 1, n_splits, ", ".join("%s=%s" % (k, p[k]) for k in sorted(p)),
-                                                                         fit_t[ci, si] + score_t[ci, si]), flush=True)
-                    for k in sorted({self._key(candidates[ci], base) for ci, _ in todo}, key=grp.index):
-                        mats[k] = fetch[k]()
-                else:
-                    mats = dict(zip(grp, _gram(X32, grp, self.device)))
-                jobs = [pool.submit(one, mats[self._key(candidates[ci], base)], ci, si) for ci, si in todo]
-                for j in jobs:
-                    j.result()
-
-        res = _cv_results(candidates, n_splits, fit_t, score_t, scores)
-        self.cv_results_ = res
-        self.n_splits_ = n_splits
-        self.scorer_ = make_scorer(accuracy_score)
-        self.multimetric_ = False
-        self.best_index_ = int(res["rank_test_score"].argmin())
-        self.best_score_ = float(res["mean_test_score"][self.best_index_])
-        self.best_params_ = candidates[self.best_index_]
-
-        if self.refit:
-            best = self.best_params_
-            key = self._key(best, base)
-            if self.refit_solver == "device":
-                # the winner's matrix where the search left it, or (host search, or a winner of an earlier group) computed again
-                matrix, run = resident.get(key, (0, lambda plan: _smo(X32, [key], plan, self.device)))
-                params = {k: base[k] for k in _FIT_CARRY}
-                params["C"] = best.get("C", base["C"])
-                t0 = time.perf_counter()
-                fitted = _fit_batch(params, y, run, matrix)
-                self.refit_time_ = time.perf_counter() - t0
-            else:
-                K = mats[key] if key in mats else fetch[key]() if key in fetch else _gram(X32, [key], self.device)[0]
-                t0 = time.perf_counter()
-                pre = self._svc(best, base, "precomputed").fit(K, y)
-                self.refit_time_ = time.perf_counter() - t0
-                params = pre.get_params()
-                fitted = {k: v for k, v in vars(pre).items() if k not in params}
-            self.best_estimator_ = _adopt(clone(self.estimator).set_params(**best), fitted, X32, key)
-        self.classes_ = np.unique(y)
-        return self
-
-    # GridSearchCV delegates these to best_estimator_
-    def predict(self, X):
-        return self.best_estimator_.predict(X)
-
-    def decision_function(self, X):
-        return self.best_estimator_.decision_function(X)
-
-    def predict_proba(self, X):
-        return self.best_estimator_.predict_proba(X)
-
-    def score(self, X, y):
-        return self.best_estimator_.score(X, y)
-
-
-def find_best_svm_estimator(X, y, cv, random_seed, solver="host", refit_solver="host"):
-    """Exhaustive search over specified parameter values for svm (train.py:462-491, the same grid, base estimator and log lines).
-    ``solver="device"`` runs the search's fits on the GPU and ``refit_solver="device"`` the refit of the winner (GridSearchSVC);
-    the result is the same.
-
-    Returns:
-        optimized svm estimator.
-
-    Note:
-        https://www.csie.ntu.edu.tw/~cjlin/papers/guide/guide.pdf
-    """
-    from sklearn import svm
-    print('\n Finding best svm estimator...')
-    Cs = [0.01, 0.1, 1, 10, 100]
-    gammas = [0.001, 0.01, 0.1, 1, 10]
-    param_grid = [
-        {'C': Cs, 'kernel': ['linear']},
-        {'C': Cs, 'gamma': gammas, 'kernel': ['rbf']}
-    ]
-    init_est = svm.SVC(probability=True, class_weight='balanced',
-                       random_state=random_seed, cache_size=1000, verbose=False)
-    grid_search = GridSearchSVC(estimator=init_est, param_grid=param_grid, verbose=2, n_jobs=4, cv=cv, solver=solver,
-                                refit_solver=refit_solver)
-    grid_search.fit(X, y)
-    logger.info('\n Best estimator:')
-    logger.info(grid_search.best_estimator_)
-    logger.info('\n Best score for {}-fold search:'.format(grid_search.n_splits_))
-    logger.info(grid_search.best_score_)
-    logger.info('\n Best hyperparameters:')
-    logger.info(grid_search.best_params_)
-    return grid_search.best_estimator_
-
-
-# ---- SGDClassifier(loss='log_loss').fit on the device (sk: = sklearn/linear_model/_stochastic_gradient.py, scikit-learn 1.7.2) ----
-# rml_sgd_problem / rml_sgd_fit of include/radarml.h
-SGD_PROBLEM = np.dtype([("n", "<i4"), ("penalty", "<i4"), ("average", "<i4"), ("max_iter", "<i4"), ("n_iter_no_change", "<i4"),
-                        ("shuffle", "<i4"), ("seed", "<u4"), ("warm", "<i4"), ("rows_off", "<i8"), ("y_off", "<i8"), ("out", "<i8"),
-                        ("alpha", "<f8"), ("l1_ratio", "<f8"), ("tol", "<f8"), ("weight_pos", "<f8"), ("weight_neg", "<f8"), ("t0", "<f8")])
-SGD_FIT = np.dtype([("prob0", "<i4"), ("n_test", "<i4"), ("test_off", "<i8")])
-_SGD_PENALTY = {"l1": _lib.SGD_L1, "l2": _lib.SGD_L2, "elasticnet": _lib.SGD_ELASTICNET}
-_SGD_GRID_KEYS = ("alpha", "penalty", "l1_ratio", "average", "max_iter", "tol", "n_iter_no_change", "shuffle")
+# ---- SGDClassifier(loss='log_loss').fit / partial_fit (sk: = sklearn/linear_model/_stochastic_gradient.py, scikit-learn 1.7.2) -----
 _SGD_OVERFLOW = "Floating-point under-/overflow occurred at epoch #%d. Scaling input data with StandardScaler or MinMaxScaler might help."
 _SGD_MAX_ITER = ("Maximum number of iteration reached before convergence. Consider increasing max_iter to improve the fit.")
-
-
-def sgd_shuffle(seed, perm):
-    """``rml_sgd_shuffle``: one ``SequentialDataset.shuffle(seed)`` pass (Fisher-Yates on scikit-learn's xorshift generator) over the
-    int32 index array ``perm``; returns the permuted copy."""
-    perm = np.array(perm, dtype=np.int32)
-    _lib.check(_lib.load().rml_sgd_shuffle(int(seed), len(perm), perm.ctypes.data), "rml_sgd_shuffle")
-    return perm
-
-
-def sgd_device(Xd, plan, device=None, check=True):
-    """``rml_sgd_solve`` + ``rml_sgd_score`` on the DEVICE rows ``Xd`` (an (N, D) float32 tensor with unit column stride; its row
-    stride is the ld of the C call) for ``plan``: a dict of
-    ``problems`` (SGD_PROBLEM records), ``rows`` / ``y`` (int32: the problems' rows and 0 / 1 labels), ``n_out`` (output slots),
-    ``fits`` (SGD_FIT records), ``test_rows`` / ``test_y`` (int32: held-out rows and their class indices), ``n_classes`` and, for
-    warm problems, ``init``: host arrays ``coef`` / ``avg_coef`` (n_out, D) and ``intercept`` / ``avg_intercept`` (n_out).
-    Returns host arrays ``intercept``, ``avg_intercept``, ``n_iter``, ``t``, ``status`` per slot, ``dec``, ``labels`` per held-out
-    row, ``correct`` per fit, ``solve_s`` / ``score_s`` (the wall time of the two batched calls), and ``coefs``: a function
-    slots -> host (coef, avg_coef) of those slots (the weights stay on the device until asked for).  A problem or a held-out row
-    that names a row outside the matrix raises RadarMLError (``check=False``: status -1 / label -1 are returned instead)."""
-    import torch
-    lib = _lib.load()
-    dev = _lib.device_of(device if device is not None else Xd.device)
-    ctx = _lib.context(dev)
-    probs = np.ascontiguousarray(plan["problems"], dtype=SGD_PROBLEM)
-    fits = np.ascontiguousarray(plan.get("fits", np.zeros(0, SGD_FIT)), dtype=SGD_FIT)
-    if Xd.dtype != torch.float32 or Xd.dim() != 2 or Xd.stride(1) != 1 or Xd.stride(0) < Xd.shape[1]:
-        raise ValueError("sgd_device: the rows are an (N, D) float32 tensor with unit column stride")
-    N, D, ld = int(Xd.shape[0]), int(Xd.shape[1]), int(Xd.stride(0))
-    n_out = int(plan["n_out"])
-    C = int(plan.get("n_classes", 2))
-    n_dec = 1 if C == 2 else C
-    with torch.cuda.device(dev):
-        i32 = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(dev)
-        rows, y = i32(plan["rows"]), i32(plan["y"])
-        te_rows, te_y = i32(plan.get("test_rows", np.zeros(0, np.int32))), i32(plan.get("test_y", np.zeros(0, np.int32)))
-        n_test = int(te_rows.numel())
-        init = plan.get("init")
-        f64 = lambda a, shape: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64).reshape(shape)).to(dev)
-        if init is None:
-            coef = torch.zeros((max(n_out, 1), D), dtype=torch.float64, device=dev)
-            avg_coef = torch.zeros_like(coef)
-            icpt = torch.zeros(max(n_out, 1), dtype=torch.float64, device=dev)
-            avg_icpt = torch.zeros_like(icpt)
-        else:
-            coef, avg_coef = f64(init["coef"], (n_out, D)), f64(init["avg_coef"], (n_out, D))
-            icpt, avg_icpt = f64(init["intercept"], (n_out,)), f64(init["avg_intercept"], (n_out,))
-        n_iter = torch.zeros(max(n_out, 1), dtype=torch.int32, device=dev)
-        t = torch.zeros(max(n_out, 1), dtype=torch.float64, device=dev)
-        status = torch.zeros(max(n_out, 1), dtype=torch.int32, device=dev)
-        dec = torch.zeros(max(n_test * n_dec, 1), dtype=torch.float64, device=dev)
-        labels = torch.zeros(max(n_test, 1), dtype=torch.int32, device=dev)
-        correct = torch.zeros(max(len(fits), 1), dtype=torch.int32, device=dev)
-        st = _lib.stream_ptr(dev)
-        torch.cuda.synchronize(dev)
-        t0 = time.perf_counter()
-        _lib.check(lib.rml_sgd_solve(ctx, _lib.ptr(Xd), N, D, ld, probs.ctypes.data, len(probs), _lib.ptr(rows), int(rows.numel()),
-                                     _lib.ptr(y), int(y.numel()), n_out, _lib.ptr(coef), _lib.ptr(avg_coef), _lib.ptr(icpt),
-                                     _lib.ptr(avg_icpt), _lib.ptr(n_iter), _lib.ptr(t), _lib.ptr(status), st), "rml_sgd_solve")
-        torch.cuda.synchronize(dev)
-        t1 = time.perf_counter()
-        if len(fits):
-            _lib.check(lib.rml_sgd_score(ctx, _lib.ptr(Xd), N, D, ld, probs.ctypes.data, len(probs), n_out, _lib.ptr(coef),
-                                         _lib.ptr(avg_coef), _lib.ptr(icpt), _lib.ptr(avg_icpt), _lib.ptr(t), C, fits.ctypes.data,
-                                         len(fits), _lib.ptr(te_rows), _lib.ptr(te_y), n_test, _lib.ptr(dec), _lib.ptr(labels),
-                                         _lib.ptr(correct), st), "rml_sgd_score")
-        torch.cuda.synchronize(dev)
-        t2 = time.perf_counter()
-
-        def coefs(slots):
-            with torch.cuda.device(dev):
-                idx = torch.as_tensor(list(slots), dtype=torch.long, device=dev)
-                return coef[idx].cpu().numpy(), avg_coef[idx].cpu().numpy()
-
-        out = {"intercept": icpt.cpu().numpy()[:n_out], "avg_intercept": avg_icpt.cpu().numpy()[:n_out],
-               "n_iter": n_iter.cpu().numpy()[:n_out], "t": t.cpu().numpy()[:n_out], "status": status.cpu().numpy()[:n_out],
-               "dec": dec.cpu().numpy()[:n_test * n_dec].reshape(n_test, n_dec), "labels": labels.cpu().numpy()[:n_test],
-               "correct": correct.cpu().numpy()[:len(fits)], "solve_s": t1 - t0, "score_s": t2 - t1, "coefs": coefs}
-    if check and (out["status"][probs["out"]] < 0).any():
-        raise _lib.RadarMLError("rml_sgd_solve: a problem names a row outside the matrix")
-    if check and (out["labels"] < 0).any():
-        raise _lib.RadarMLError("rml_sgd_score: a held-out row outside the matrix")
-    return out
-
-
-def _sgd(X, plan, device=None):
-    """The float32 host rows ``X`` uploaded ONCE, every problem of ``plan`` solved on them in one ``rml_sgd_solve`` call and every
-    held-out row scored in one ``rml_sgd_score`` call (``sgd_device``).  Returns ``sgd_device``'s dict plus ``solve``: a function
-    plan -> ``sgd_device``'s dict of another plan on the same resident rows (the refit of a search's winner).
-
-    All device work of the SGD fits and of their search goes through this function (tests replace it to run the logic without a GPU)."""
-    import torch
-    dev = _lib.device_of(device)
-    with torch.cuda.device(dev):
-        Xd = torch.from_numpy(np.ascontiguousarray(X, dtype=np.float32)).to(dev)
-        out = sgd_device(Xd, plan, dev)
-    out["solve"] = lambda plan2: sgd_device(Xd, plan2, dev)
-    return out
 
 
 def _sgd_seeds(random_state, n_classes):
@@ -880,6 +642,63 @@ def _sgd_check_rows(who, n):
         raise NotImplementedError("%s: %d training rows (rml_sgd_solve takes at most %d per problem)" % (who, n, _lib.SGD_MAX_ROWS))
 
 
+def _sgd_check_overflow(out):
+    if (out["status"] == 2).any():
+        raise ValueError(_SGD_OVERFLOW % int(out["n_iter"][np.nonzero(out["status"] == 2)[0][0]]))
+
+
+class _SGDState:
+    """The solver's side of an ``SGDClassifier`` (``prm``: its ``_sgd_params``) whose ``classes_``, parameter arrays, ``t_`` and
+    ``_expanded_class_weight`` are in place, as fit_binary and _prepare_fit_binary (sk:348-365, 736-751) see it: one problem per class
+    of ``positives`` (the second class alone for two), each on views of the estimator's arrays, so that what they alias stays aliased."""
+
+    def __init__(self, est, prm):
+        self.est, self.prm, self.nc = est, prm, len(est.classes_)
+        self.positives = [1] if self.nc == 2 else list(range(self.nc))
+        self.avg = prm["average"] > 0
+
+    def views(self, c):
+        """(coef, intercept, avg_coef, avg_intercept, j) of class ``c``: its weight rows, and the intercept arrays with its index."""
+        est, K = self.est, len(self.positives)
+        j = 0 if self.nc == 2 else c
+        if self.avg:
+            return est._standard_coef.reshape(K, -1)[j], est._standard_intercept, est._average_coef.reshape(K, -1)[j], est._average_intercept, j
+        return est.coef_.reshape(K, -1)[j], est.intercept_, None, None, j
+
+    def init(self):
+        """The state of every problem as the ``init`` of a plan: host ``coef`` / ``avg_coef`` (K, D), ``intercept`` / ``avg_intercept`` (K)."""
+        K, D = len(self.positives), self.est.coef_.shape[-1]
+        init = {"coef": np.zeros((K, D)), "avg_coef": np.zeros((K, D)), "intercept": np.zeros(K), "avg_intercept": np.zeros(K)}
+        for k, c in enumerate(self.positives):
+            coef, icpt, acoef, aicpt, j = self.views(c)
+            init["coef"][k], init["intercept"][k] = coef, icpt[j]
+            if self.avg:
+                init["avg_coef"][k], init["avg_intercept"][k] = acoef, aicpt[j]
+        return init
+
+    def problems(self, n, seeds, y_offs, max_iter):
+        """The warm SGD_PROBLEM records from ``t_`` on: problem k on ``n`` rows, its labels at ``y_offs[k]``, to output slot k."""
+        w = self.est._expanded_class_weight
+        return np.array([_sgd_problem(self.prm, n, seeds[k], 0, y_offs[k], k, w[c], w[0] if self.nc == 2 else 1.0, t0=float(self.est.t_),
+                                      warm=1, max_iter=max_iter) for k, c in enumerate(self.positives)], dtype=SGD_PROBLEM)
+
+    def store(self, coefs, avg_coefs, avg_intercept):
+        """Write the solver's weights (per problem) back through the views; the standard intercept is the caller's."""
+        for k, c in enumerate(self.positives):
+            coef, _, acoef, aicpt, j = self.views(c)
+            coef[:] = coefs[k]
+            if self.avg:
+                acoef[:] = avg_coefs[k]
+                aicpt[j] = avg_intercept[k]
+
+    def select(self, averaged):
+        """With averaging on: ``coef_`` / ``intercept_`` alias the averaged or the standard arrays, as scikit-learn leaves them."""
+        est = self.est
+        coef = est._average_coef if averaged else est._standard_coef
+        est.coef_ = coef.reshape(1, -1) if self.nc == 2 else coef
+        est.intercept_ = est._average_intercept if averaged else est._standard_intercept
+
+
 def _sgd_run(est, y, max_iter, run, who):
     """``BaseSGDClassifier._partial_fit`` (sk:583-666) after its validation, on an estimator whose ``classes_``, parameter arrays and
     ``t_`` are in place: one problem per class (one for two classes) from the estimator's current state, solved by ``run(plan)``
@@ -894,72 +713,32 @@ def _sgd_run(est, y, max_iter, run, who):
     if ((yi >= nc) | (classes[np.minimum(yi, nc - 1)] != y)).any():
         raise ValueError("%s: y holds labels outside classes_ %r" % (who, classes))
     est._expanded_class_weight = compute_class_weight(est.class_weight, classes=classes, y=y)
-    positives = [1] if nc == 2 else list(range(nc))
+    st = _SGDState(est, prm)
+    K = len(st.positives)
     seeds = _sgd_seeds(est.random_state, nc)
-    avg = prm["average"] > 0
-    D = est.coef_.shape[-1]
-
-    def state(c):                       # _prepare_fit_binary (sk:348-365): views of the estimator's arrays
-        if nc == 2:
-            return ((est._standard_coef.ravel(), est._standard_intercept, est._average_coef.ravel(), est._average_intercept) if avg
-                    else (est.coef_.ravel(), est.intercept_, None, None)), 0
-        return ((est._standard_coef[c], est._standard_intercept, est._average_coef[c], est._average_intercept) if avg
-                else (est.coef_[c], est.intercept_, None, None)), c
-
-    K = len(positives)
-    init = {"coef": np.zeros((K, D)), "avg_coef": np.zeros((K, D)), "intercept": np.zeros(K), "avg_intercept": np.zeros(K)}
-    problems, ys = [], []
-    for k, c in enumerate(positives):
-        (coef, icpt, acoef, aicpt), j = state(c)
-        init["coef"][k], init["intercept"][k] = coef, icpt[j]
-        if avg:
-            init["avg_coef"][k], init["avg_intercept"][k] = acoef, aicpt[j]
-        wpos = est._expanded_class_weight[c]
-        wneg = est._expanded_class_weight[0] if nc == 2 else 1.0
-        problems.append(_sgd_problem(prm, n, seeds[k], 0, k * n, k, wpos, wneg, t0=float(est.t_), warm=1, max_iter=max_iter))
-        ys.append((yi == c).astype(np.int32))
-    plan = {"problems": np.array(problems, dtype=SGD_PROBLEM), "rows": np.arange(n, dtype=np.int32), "y": np.concatenate(ys),
-            "n_out": K, "init": init, "n_classes": nc}
+    plan = {"problems": st.problems(n, seeds, [k * n for k in range(K)], max_iter), "rows": np.arange(n, dtype=np.int32),
+            "y": np.concatenate([(yi == c).astype(np.int32) for c in st.positives]), "n_out": K, "init": st.init(), "n_classes": nc}
     out = run(plan)
-    if (out["status"] == 2).any():
-        raise ValueError(_SGD_OVERFLOW % int(out["n_iter"][np.nonzero(out["status"] == 2)[0][0]]))
-    coefs, acoefs = out["coefs"](range(K))
-    n_iter_ = 0
-    for k, c in enumerate(positives):
-        (coef, _, acoef, aicpt), j = state(c)
-        coef[:] = coefs[k]
-        if avg:
-            acoef[:] = acoefs[k]
-            aicpt[j] = out["avg_intercept"][k]
-        n_iter_ = max(n_iter_, int(out["n_iter"][k]))
+    _sgd_check_overflow(out)
+    st.store(*out["coefs"](range(K)), out["avg_intercept"])
+    n_iter_ = int(out["n_iter"][:K].max())
+    # the tail of _fit_binary (sk:753-768) for two classes, of _fit_multiclass (sk:807-823) for more
     if nc == 2:
-        intercept = float(out["intercept"][0])
-        est.t_ += n_iter_ * n
-        est.n_iter_ = n_iter_
-        if avg:
-            if prm["average"] <= est.t_ - 1:
-                est.coef_ = est._average_coef.reshape(1, -1)
-                est.intercept_ = est._average_intercept
-            else:
-                est.coef_ = est._standard_coef.reshape(1, -1)
-                est._standard_intercept = np.atleast_1d(intercept)
-                est.intercept_ = est._standard_intercept
-        else:
-            est.coef_ = est.coef_.reshape(1, -1)
-            est.intercept_ = np.atleast_1d(intercept)
+        intercept = np.atleast_1d(float(out["intercept"][0]))
     else:
         for k in range(K):
             est.intercept_[k] = out["intercept"][k]
-        est.t_ += n_iter_ * n
-        est.n_iter_ = n_iter_
-        if avg:
-            if prm["average"] <= est.t_ - 1.0:
-                est.coef_ = est._average_coef
-                est.intercept_ = est._average_intercept
-            else:
-                est.coef_ = est._standard_coef
-                est._standard_intercept = np.atleast_1d(est.intercept_)
-                est.intercept_ = est._standard_intercept
+        intercept = est.intercept_
+    est.t_ += n_iter_ * n
+    est.n_iter_ = n_iter_
+    if st.avg:
+        averaged = prm["average"] <= est.t_ - 1
+        if not averaged:
+            est._standard_intercept = np.atleast_1d(intercept)
+        st.select(averaged)
+    elif nc == 2:
+        est.coef_ = est.coef_.reshape(1, -1)
+        est.intercept_ = intercept
     return est
 
 
@@ -996,13 +775,6 @@ def _sgd_fit(est, X32, y, run, who):
     return est
 
 
-def _check_y(X32, y):
-    y = np.asarray(y)
-    if y.ndim != 1 or y.shape[0] != X32.shape[0]:
-        raise ValueError("Found input variables with inconsistent numbers of samples: [%d, %d]" % (X32.shape[0], len(y)))
-    return y
-
-
 def fit_sgd(estimator, X, y, device=None):
     """``estimator.fit(X, y)`` for an unfitted ``sklearn.linear_model.SGDClassifier`` on the GPU: one ``rml_sgd_solve`` call, one
     workgroup per class (one for two classes) running scikit-learn's ``_plain_sgd64``.  Supported: ``loss='log_loss'`` (or the old
@@ -1031,269 +803,7 @@ def partial_fit_sgd(estimator, X, y, classes=None, device=None):
     return _sgd_run(est, y, 1, lambda plan: _sgd(X32, plan, device), who)
 
 
-class GridSearchSGD:
-    """``GridSearchCV(SGDClassifier(loss='log_loss'), param_grid)`` on the GPU: the counterpart of ``GridSearchSVC`` for the
-    reference's default model, with the same subset of ``GridSearchCV``'s surface (``fit(X, y)``, ``best_estimator_``,
-    ``best_params_``, ``best_score_``, ``best_index_``, ``cv_results_``, ``n_splits_``, ``refit_time_``, ``scorer_``: accuracy).
-
-    The rows are uploaded once.  Every candidate (``ParameterGrid`` order) x split x class is one problem of ONE ``rml_sgd_solve``
-    call, every held-out row is scored by ONE ``rml_sgd_score`` call from the weights where the solve left them, and the winner is
-    refitted on all rows by one more solve on the resident rows (``fit_sgd``'s path).  The grid may vary ``alpha``, ``penalty``,
-    ``l1_ratio``, ``average``, ``max_iter``, ``tol``, ``n_iter_no_change`` and ``shuffle``; everything else is the base estimator's,
-    under ``fit_sgd``'s restrictions.  ``class_weight`` is formed per fold as scikit-learn forms it.  The batch has no per-fit
-    times: ``fit_time`` / ``score_time`` are the batch's solve / score time divided evenly among its fits."""
-
-    def __init__(self, estimator, param_grid, cv=5, refit=True, device=None, scoring=None, verbose=0, n_jobs=None):
-        self.estimator = estimator
-        self.param_grid = param_grid
-        self.cv = cv
-        self.refit = refit
-        self.device = device
-        self.scoring = scoring
-        self.verbose = verbose
-        self.n_jobs = n_jobs                # accepted for GridSearchCV's signature; the batch is one launch whatever it says
-
-    def _check(self):
-        from sklearn.linear_model import SGDClassifier
-        from sklearn.model_selection import ParameterGrid
-        if type(self.estimator) is not SGDClassifier:
-            raise NotImplementedError("GridSearchSGD searches sklearn.linear_model.SGDClassifier, not %s" % type(self.estimator).__name__)
-        if self.scoring not in (None, "accuracy"):
-            raise NotImplementedError("GridSearchSGD scores by accuracy (GridSearchCV's default for a classifier), not %r" % (self.scoring,))
-        if callable(self.refit) or not isinstance(self.refit, bool):
-            raise NotImplementedError("GridSearchSGD: refit must be True or False, not %r" % (self.refit,))
-        grids = [self.param_grid] if isinstance(self.param_grid, dict) else list(self.param_grid)
-        for g in grids:
-            bad = sorted(set(g) - set(_SGD_GRID_KEYS))
-            if bad:
-                raise NotImplementedError("GridSearchSGD searches %s, not %s" % (", ".join(_SGD_GRID_KEYS), ", ".join(bad)))
-        candidates = list(ParameterGrid(self.param_grid))
-        base = self.estimator.get_params()
-        prms = [_sgd_params(dict(base, **p), "GridSearchSGD") for p in candidates]
-        return candidates, base, prms
-
-    def _plan(self, prms, base, splits, y):
-        """The batch of the search for ``_sgd``: per candidate and split one fit of one problem per class (one for two classes), on
-        the split's shared row list and per-class label lists.  Returns (plan, [(ci, si) of fit f])."""
-        from sklearn.utils.class_weight import compute_class_weight
-        classes = np.unique(y)
-        nc = len(classes)
-        yi = np.searchsorted(classes, y).astype(np.int32)
-        positives = [1] if nc == 2 else list(range(nc))
-        rows, ys, test_rows, test_y, per_split = [], [], [], [], []
-        n_rows = n_y = 0
-        for tr, te in splits:
-            if len(np.unique(yi[tr])) < nc:
-                raise NotImplementedError("GridSearchSGD: a split whose training rows miss a class (scikit-learn fits a model of fewer "
-                                          "classes there)")
-            _sgd_check_rows("GridSearchSGD", len(tr))
-            w = compute_class_weight(base["class_weight"], classes=classes, y=y[tr])
-            y_offs = []
-            for c in positives:
-                ys.append((yi[tr] == c).astype(np.int32))
-                y_offs.append(n_y)
-                n_y += len(tr)
-            per_split.append((n_rows, y_offs, w))
-            rows.append(tr)
-            n_rows += len(tr)
-        problems, fits, which = [], [], []
-        n_test = 0
-        for ci, prm in enumerate(prms):
-            for si, (tr, te) in enumerate(splits):
-                rows_off, y_offs, w = per_split[si]
-                seeds = _sgd_seeds(base["random_state"], nc)
-                fits.append((len(problems), len(te), n_test))
-                which.append((ci, si))
-                test_rows.append(te)
-                test_y.append(yi[te])
-                n_test += len(te)
-                for k, c in enumerate(positives):
-                    problems.append(_sgd_problem(prm, len(tr), seeds[k], rows_off, y_offs[k], len(problems), w[c],
-                                                 w[0] if nc == 2 else 1.0))
-        cat = lambda parts: np.concatenate(parts).astype(np.int32) if parts else np.zeros(0, np.int32)
-        plan = {"problems": np.array(problems, dtype=SGD_PROBLEM), "rows": cat(rows), "y": cat(ys), "n_out": len(problems),
-                "fits": np.array(fits, dtype=SGD_FIT), "test_rows": cat(test_rows), "test_y": cat(test_y), "n_classes": nc}
-        return plan, which
-
-    def fit(self, X, y):
-        import warnings
-        from sklearn.base import clone
-        from sklearn.exceptions import ConvergenceWarning
-        from sklearn.metrics import accuracy_score, make_scorer
-        from sklearn.model_selection import check_cv
-        candidates, base, prms = self._check()
-        X32 = _rows(X)
-        y = _check_y(X32, y)
-        if not 2 <= len(np.unique(y)) <= 8:
-            raise ValueError("GridSearchSGD takes 2..8 classes, got %d" % len(np.unique(y)))
-        cv = check_cv(self.cv, y, classifier=True)
-        splits = [(np.asarray(tr), np.asarray(te)) for tr, te in cv.split(X32, y)]
-        n_splits = len(splits)
-        if n_splits == 0 or not candidates:
-            raise ValueError("No fits were performed. Was the CV iterator empty? Were there no candidates?")
-        if self.verbose > 0:
-            print("Fitting %d folds for each of %d candidates, totalling %d fits" % (n_splits, len(candidates),
-                                                                                   n_splits * len(candidates)), flush=True)
-        plan, which = self._plan(prms, base, splits, y)
-        out = _sgd(X32, plan, self.device)
-        if (out["status"] == 2).any():
-            raise ValueError(_SGD_OVERFLOW % int(out["n_iter"][np.nonzero(out["status"] == 2)[0][0]]))
-        probs = plan["problems"]
-        if ((probs["tol"] > -np.inf) & (out["n_iter"][probs["out"]] == probs["max_iter"])).any():
-            warnings.warn(_SGD_MAX_ITER, ConvergenceWarning)
-        scores = np.zeros((len(candidates), n_splits))
-        fit_t = np.full_like(scores, out["solve_s"] / len(which))
-        score_t = np.full_like(scores, out["score_s"] / len(which))
-        for f, (ci, si) in enumerate(which):
-            scores[ci, si] = float(out["correct"][f]) / len(splits[si][1])
-            if self.verbose > 1:
-                p = candidates[ci]
-                print("[CV %d/%d] END %s; total time=%5.1fs" % (si + 1, n_splits, ", ".join("%s=%s" % (k, p[k]) for k in sorted(p)),
-                                                             fit_t[ci, si] + score_t[ci, si]), flush=True)
-        res = _cv_results(candidates, n_splits, fit_t, score_t, scores)
-        self.cv_results_ = res
-        self.n_splits_ = n_splits
-        self.scorer_ = make_scorer(accuracy_score)
-        self.multimetric_ = False
-        self.best_index_ = int(res["rank_test_score"].argmin())
-        self.best_score_ = float(res["mean_test_score"][self.best_index_])
-        self.best_params_ = candidates[self.best_index_]
-        self.solve_time_, self.score_time_ = out["solve_s"], out["score_s"]
-        if self.refit:
-            est = clone(self.estimator).set_params(**self.best_params_)
-            _sgd_prepare(est, "GridSearchSGD")
-            t0 = time.perf_counter()
-            self.best_estimator_ = _sgd_fit(est, X32, y, out["solve"], "GridSearchSGD")
-            self.refit_time_ = time.perf_counter() - t0
-        self.classes_ = np.unique(y)
-        return self
-
-    # GridSearchCV delegates these to best_estimator_
-    def predict(self, X):
-        return self.best_estimator_.predict(X)
-
-    def decision_function(self, X):
-        return self.best_estimator_.decision_function(X)
-
-    def predict_proba(self, X):
-        return self.best_estimator_.predict_proba(X)
-
-    def score(self, X, y):
-        return self.best_estimator_.score(X, y)
-
-
-def find_best_sgd_svm_estimator(X, y, cv, random_seed, device=None):
-    """Exhaustive search over specified parameter values for svm using sgd (train.py:350-381, the same grid, base estimator and
-    log lines), every fit of the search and the refit on the GPU (GridSearchSGD).
-
-    Returns:
-        optimized svm estimator.
-    """
-    from sklearn import linear_model
-    max_iter = max(np.ceil(10**6 / len(X)), 1000)
-    small_alphas = [10.0e-08, 10.0e-09, 10.0e-10]
-    alphas = [10.0e-04, 10.0e-05, 10.0e-06, 10.0e-07]
-    l1_ratios = [0.075, 0.15, 0.30]
-    param_grid = [
-        {'alpha': alphas, 'penalty': ['l1', 'l2'], 'average': [False]},
-        {'alpha': alphas, 'penalty': ['elasticnet'], 'average': [False],
-         'l1_ratio': l1_ratios},
-        {'alpha': small_alphas, 'penalty': ['l1', 'l2'], 'average': [True]},
-        {'alpha': small_alphas, 'penalty': ['elasticnet'], 'average': [True],
-         'l1_ratio': l1_ratios}
-    ]
-    init_est = linear_model.SGDClassifier(loss='log', max_iter=max_iter,
-                                          random_state=random_seed, n_jobs=-1, warm_start=True)
-    grid_search = GridSearchSGD(estimator=init_est, param_grid=param_grid, verbose=2, n_jobs=-1, cv=cv, device=device)
-    grid_search.fit(X, y)
-    logger.info('\n Best estimator:')
-    logger.info(grid_search.best_estimator_)
-    logger.info('\n Best score for {}-fold search:'.format(grid_search.n_splits_))
-    logger.info(grid_search.best_score_)
-    logger.info('\n Best hyperparameters:')
-    logger.info(grid_search.best_params_)
-    return grid_search.best_estimator_
-
-
-# ---- the online loop of train.py:409-438: a chain of partial_fit calls resident on the device (rml_sgd_online) -----------------
-# rml_sgd_step of include/radarml.h
-SGD_STEP = np.dtype([("off", "<i8"), ("n", "<i4"), ("score", "<i4"), ("seed", "<u4", (8,))])
-RANDOM_SEED = 1234                      # train.py:32
-
-
-def sgd_online_device(Xd, plan, device=None, check=True, fill=None):
-    """``rml_sgd_online`` on the DEVICE rows ``Xd`` (as ``sgd_device`` takes them) for ``plan``: a dict of ``problems`` (K SGD_PROBLEM
-    records of one estimator, class order; K = 1 for two classes), ``n_classes``, ``steps`` (SGD_STEP records), ``rows`` / ``cls``
-    (int32: the steps' rows and their class indices), ``test_rows`` / ``test_y`` (int32, optional), ``init`` (host ``coef`` /
-    ``avg_coef`` (K, D), ``intercept`` / ``avg_intercept`` (K): the state of problem k, stored at its slot), ``avg_flag`` and
-    optionally ``n_out`` (output slots, default K).  Returns host arrays per PROBLEM ``coef``, ``avg_coef``, ``intercept``,
-    ``avg_intercept``, ``t``, ``status``, and ``avg_flag``, ``fail_step``, ``correct`` (per step), ``labels`` / ``dec`` (of the last
-    scored step).  Two uploads, one call, two copies back: the only wait is for those.  A row outside the matrix raises
-    RadarMLError (``check=False``: status -1 is returned).  ``fill``: what the outputs without an initial value hold before the
-    call (default 0)."""
-    import torch
-    lib = _lib.load()
-    dev = _lib.device_of(device if device is not None else Xd.device)
-    ctx = _lib.context(dev)
-    probs = np.ascontiguousarray(plan["problems"], dtype=SGD_PROBLEM)
-    steps = np.ascontiguousarray(plan["steps"], dtype=SGD_STEP)
-    if Xd.dtype != torch.float32 or Xd.dim() != 2 or Xd.stride(1) != 1 or Xd.stride(0) < Xd.shape[1]:
-        raise ValueError("sgd_online_device: the rows are an (N, D) float32 tensor with unit column stride")
-    N, D, ld = int(Xd.shape[0]), int(Xd.shape[1]), int(Xd.stride(0))
-    C = int(plan["n_classes"])
-    K, n_dec, S = len(probs), (1 if C == 2 else C), len(steps)
-    if K != n_dec:
-        raise ValueError("sgd_online_device: %d problems for %d classes" % (K, C))
-    n_out = int(plan.get("n_out", K))
-    out = probs["out"].astype(np.int64)
-    if ((out < 0) | (out >= n_out)).any():
-        raise ValueError("sgd_online_device: an output slot outside [0, %d)" % n_out)
-    i32 = lambda a: np.ascontiguousarray(a, dtype=np.int32).ravel()
-    rows, cls = i32(plan["rows"]), i32(plan["cls"])
-    te_rows, te_y = i32(plan.get("test_rows", [])), i32(plan.get("test_y", []))
-    n_test = len(te_rows)
-    init = plan["init"]
-    fill = 0 if fill is None else fill
-    # one float64 and one int32 block hold every in / out array: [coef | avg_coef | intercept | avg_intercept | t | dec] and
-    # [status | avg_flag | fail_step | correct | labels | rows | cls | test_rows | test_y]
-    f_off = np.cumsum([0, n_out * D, n_out * D, n_out, n_out, n_out, max(n_test * n_dec, 1)])
-    hf = np.full(int(f_off[-1]), float(fill))
-    for name, j, width in (("coef", 0, D), ("avg_coef", 1, D), ("intercept", 2, 1), ("avg_intercept", 3, 1)):
-        hf[f_off[j]:f_off[j + 1]].reshape(n_out, width)[out] = np.asarray(init[name], dtype=np.float64).reshape(K, width)
-    i_off = np.cumsum([0, n_out, 1, 1, max(S, 1), max(n_test, 1), max(len(rows), 1), max(len(cls), 1), max(n_test, 1), max(n_test, 1)])
-    hi = np.full(int(i_off[-1]), int(fill), dtype=np.int32)
-    hi[i_off[1]] = int(bool(plan.get("avg_flag", False)))
-    for j, a in ((5, rows), (6, cls), (7, te_rows), (8, te_y)):
-        hi[i_off[j]:i_off[j] + len(a)] = a
-    with torch.cuda.device(dev):
-        df, di = torch.from_numpy(hf).to(dev), torch.from_numpy(hi).to(dev)
-        fp = lambda j: _lib.ptr(df[int(f_off[j]):])
-        ip = lambda j: _lib.ptr(di[int(i_off[j]):])
-        _lib.check(lib.rml_sgd_online(ctx, _lib.ptr(Xd), N, D, ld, probs.ctypes.data, C, steps.ctypes.data, S, ip(5), ip(6), len(rows),
-                                      ip(7), ip(8), n_test, n_out, fp(0), fp(1), fp(2), fp(3), fp(4), ip(1), ip(0), ip(2), ip(3), ip(4), fp(5),
-                                      _lib.stream_ptr(dev)), "rml_sgd_online")
-        rf, ri = df.cpu().numpy(), di[:int(i_off[5])].cpu().numpy()
-    f = lambda j, width: rf[f_off[j]:f_off[j + 1]].reshape(n_out, width)[out]
-    res = {"coef": f(0, D), "avg_coef": f(1, D), "intercept": f(2, 1)[:, 0], "avg_intercept": f(3, 1)[:, 0], "t": f(4, 1)[:, 0],
-           "status": ri[:n_out][out], "avg_flag": bool(ri[i_off[1]]), "fail_step": int(ri[i_off[2]]), "correct": ri[i_off[3]:i_off[3] + S],
-           "labels": ri[i_off[4]:i_off[4] + n_test], "dec": rf[f_off[5]:f_off[5] + n_test * n_dec].reshape(n_test, n_dec)}
-    if check and (res["status"] < 0).any():
-        raise _lib.RadarMLError("rml_sgd_online: a step or the held-out list names a row outside the matrix")
-    return res
-
-
-def _sgd_online(X, plan, device=None):
-    """The rows ``X`` (float32 host rows, uploaded ONCE, or a CUDA tensor taken where it is) and the whole chain of partial_fit steps
-    of ``plan`` in one ``rml_sgd_online`` call (``sgd_online_device``).
-
-    All device work of ``partial_fit_sgd_steps`` goes through this function (tests replace it to run the logic without a GPU)."""
-    import torch
-    dev = _lib.device_of(device if device is not None or not isinstance(X, torch.Tensor) else X.device)
-    with torch.cuda.device(dev):
-        Xd = X.to(dev) if isinstance(X, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(X, dtype=np.float32)).to(dev)
-        return sgd_online_device(Xd, plan, dev)
-
-
+# ---- the online loop of train.py:409-438 as one resident chain ---------------------------------------------------------------------
 def _sgd_partial_prepare(est, n_features, classes, who):
     """What ``SGDClassifier.partial_fit`` does to the estimator before its solver runs (sk:583-631)."""
     if est.class_weight == "balanced" and not hasattr(est, "classes_"):
@@ -1373,9 +883,8 @@ def partial_fit_sgd_steps(estimator, X, y, steps, classes=None, test=None, score
     yi = np.full(N, -1, dtype=np.int32)
     yi[used] = class_index(y[used], True)
     est._expanded_class_weight = compute_class_weight(est.class_weight, classes=classes_, y=y[steps[-1]])
-    positives = [1] if nc == 2 else list(range(nc))
-    K = len(positives)
-    avg = prm["average"] > 0
+    st = _SGDState(est, prm)
+    K = len(st.positives)
     score_every = int(score_every)
     if score_every < 1:
         raise ValueError("%s: score_every must be >= 1" % who)
@@ -1401,50 +910,24 @@ def partial_fit_sgd_steps(estimator, X, y, steps, classes=None, test=None, score
         rec[s]["score"] = int(test is not None and (s + 1) % score_every == 0)
         rec[s]["seed"][:K] = fixed if fixed is not None else _sgd_seeds(est.random_state, nc)
     rows = np.concatenate(row_parts)
-
-    def state(c):                       # _prepare_fit_binary (sk:348-365): views of the estimator's arrays
-        j = 0 if nc == 2 else c
-        if avg:
-            return est._standard_coef.reshape(K, -1)[j], est._standard_intercept, est._average_coef.reshape(K, -1)[j], est._average_intercept, j
-        return est.coef_.reshape(K, -1)[j], est.intercept_, None, None, j
-
-    init = {"coef": np.zeros((K, D)), "avg_coef": np.zeros((K, D)), "intercept": np.zeros(K), "avg_intercept": np.zeros(K)}
-    problems = []
-    for k, c in enumerate(positives):
-        coef, icpt, acoef, aicpt, j = state(c)
-        init["coef"][k], init["intercept"][k] = coef, icpt[j]
-        if avg:
-            init["avg_coef"][k], init["avg_intercept"][k] = acoef, aicpt[j]
-        wpos = est._expanded_class_weight[c]
-        wneg = est._expanded_class_weight[0] if nc == 2 else 1.0
-        problems.append(_sgd_problem(prm, 1, 0, 0, 0, k, wpos, wneg, t0=float(est.t_), warm=1, max_iter=1))
-    plan = {"problems": np.array(problems, dtype=SGD_PROBLEM), "n_classes": nc, "steps": rec, "rows": rows.astype(np.int32),
-            "cls": yi[rows], "test_rows": te_rows.astype(np.int32), "test_y": te_y, "init": init,
-            "avg_flag": bool(avg and est.intercept_ is est._average_intercept)}
+    # the rows, labels and seeds of a problem are its steps': the records carry the estimator's state and parameters
+    plan = {"problems": st.problems(1, [0] * K, [0] * K, 1), "n_classes": nc, "steps": rec, "rows": rows.astype(np.int32),
+            "cls": yi[rows], "test_rows": te_rows.astype(np.int32), "test_y": te_y, "init": st.init(),
+            "avg_flag": bool(st.avg and est.intercept_ is est._average_intercept)}
     out = _sgd_online(rows_of, plan, device)
     if (out["status"] == 2).any():
         raise ValueError(_SGD_OVERFLOW % 1)
-    for k, c in enumerate(positives):
-        coef, icpt, acoef, aicpt, j = state(c)
-        coef[:] = out["coef"][k]
-        if avg:
-            acoef[:] = out["avg_coef"][k]
-            aicpt[j] = out["avg_intercept"][k]
+    st.store(out["coef"], out["avg_coef"], out["avg_intercept"])
     SI = np.array(out["intercept"], dtype=np.float64)
     est.t_ = float(out["t"].max())
     est.n_iter_ = 1
-    if avg:
+    if st.avg:
         # the standard intercept in an array of its own, as _fit_binary / _fit_multiclass leave it once averaging has begun
         if est._standard_intercept is est._average_intercept:
             est._standard_intercept = SI
         else:
             est._standard_intercept[:] = SI
-        if out["avg_flag"]:
-            est.coef_ = est._average_coef.reshape(1, -1) if nc == 2 else est._average_coef
-            est.intercept_ = est._average_intercept
-        else:
-            est.coef_ = est._standard_coef.reshape(1, -1) if nc == 2 else est._standard_coef
-            est.intercept_ = est._standard_intercept
+        st.select(out["avg_flag"])
     else:
         est.coef_ = est.coef_.reshape(K, -1)
         if nc == 2:
@@ -1458,6 +941,518 @@ def partial_fit_sgd_steps(estimator, X, y, steps, classes=None, test=None, score
     return est, acc
 
 
+# ---- the searches: GridSearchCV's scaffold, GridSearchSVC, GridSearchSGD ------------------------------------------------------------
+def _masked_params(candidates):
+    """``param_*`` entries of ``cv_results_`` (GridSearchCV's layout: one masked array per parameter)."""
+    vals = {}
+    for i, p in enumerate(candidates):
+        for name, v in p.items():
+            vals.setdefault("param_%s" % name, {})[i] = v
+    out = {}
+    for key, d in vals.items():
+        arr = np.array(list(d.values()))
+        dtype = arr.dtype if arr.dtype.kind != "U" and arr.ndim == 1 else object
+        ma = np.ma.MaskedArray(np.empty(len(candidates), dtype=dtype), mask=True)
+        for i, v in d.items():
+            ma[i] = v
+        out[key] = ma
+    return out
+
+
+def _cv_results(candidates, n_splits, fit_t, score_t, scores):
+    """``cv_results_`` in GridSearchCV's layout from (candidate, split) arrays of fit times, score times and test scores."""
+    res = {}
+
+    def store(name, arr, splits_=False, rank=False):
+        if splits_:
+            for s in range(n_splits):
+                res["split%d_%s" % (s, name)] = arr[:, s]
+        mean = np.average(arr, axis=1)
+        res["mean_%s" % name] = mean
+        res["std_%s" % name] = np.sqrt(np.average((arr - mean[:, None]) ** 2, axis=1))
+        if rank:
+            from scipy.stats import rankdata
+            res["rank_%s" % name] = rankdata(-mean, method="min").astype(np.int32, copy=False)
+
+    store("fit_time", fit_t)
+    store("score_time", score_t)
+    res.update(_masked_params(candidates))
+    res["params"] = candidates
+    store("test_score", scores, splits_=True, rank=True)
+    return res
+
+
+class _GridSearch:
+    """What ``GridSearchSVC`` and ``GridSearchSGD`` share of ``GridSearchCV``'s scaffold; a subclass has its plan builder and ``fit``."""
+
+    def __init__(self, estimator, param_grid, cv, n_jobs, refit, device, scoring, verbose):
+        self.estimator = estimator
+        self.param_grid = param_grid
+        self.cv = cv
+        self.n_jobs = n_jobs
+        self.refit = refit
+        self.device = device
+        self.scoring = scoring
+        self.verbose = verbose
+
+    def _check_search(self, who, est_type, accuracy_of, grid_keys):
+        """The checks of the search ``who`` for estimators of exactly ``est_type`` over ``grid_keys`` (``accuracy_of``: a word on its
+        score).  Returns (candidates in ``ParameterGrid`` order, the base estimator's parameters)."""
+        from sklearn.model_selection import ParameterGrid
+        if type(self.estimator) is not est_type:        # named by its public module: sklearn.svm._classes -> sklearn.svm
+            raise NotImplementedError("%s searches %s.%s, not %s" % (who, est_type.__module__.split("._")[0], est_type.__name__,
+                                                                    type(self.estimator).__name__))
+        if self.scoring not in (None, "accuracy"):
+            raise NotImplementedError("%s scores by accuracy (%s), not %r" % (who, accuracy_of, self.scoring))
+        if callable(self.refit) or not isinstance(self.refit, bool):
+            raise NotImplementedError("%s: refit must be True or False, not %r" % (who, self.refit))
+        grids = [self.param_grid] if isinstance(self.param_grid, dict) else list(self.param_grid)
+        for g in grids:
+            bad = sorted(set(g) - set(grid_keys))
+            if bad:
+                raise NotImplementedError("%s searches %s, not %s" % (who, ", ".join(grid_keys), ", ".join(bad)))
+        return list(ParameterGrid(self.param_grid)), self.estimator.get_params()
+
+    def _check_data(self, X32, y):
+        """What a subclass asks of the validated rows and labels (raises)."""
+
+    def _setup(self, X, y, candidates):
+        """The validated float32 rows, the labels and the list of (train, test) splits; prints the header of the search."""
+        from sklearn.model_selection import check_cv
+        X32 = _rows(X)
+        y = _check_y(X32, y)
+        self._check_data(X32, y)
+        cv = check_cv(self.cv, y, classifier=True)
+        splits = [(np.asarray(tr), np.asarray(te)) for tr, te in cv.split(X32, y)]
+        if not splits or not candidates:
+            raise ValueError("No fits were performed. Was the CV iterator empty? Were there no candidates?")
+        if self.verbose > 0:
+            print("Fitting %d folds for each of %d candidates, totalling %d fits" % (len(splits), len(candidates),
+                                                                                   len(splits) * len(candidates)), flush=True)
+        return X32, y, splits
+
+    def _end_line(self, p, si, n_splits, seconds):
+        """The line of one finished fit: candidate ``p`` on split ``si``."""
+        if self.verbose > 1:
+            print("[CV %d/%d] END %s; total time=%5.1fs" % (si + 1, n_splits, ", ".join("%s=%s" % (k, p[k]) for k in sorted(p)), seconds),
+                  flush=True)
+
+    def _finish(self, candidates, n_splits, fit_t, score_t, scores):
+        """``cv_results_`` .. ``best_params_`` from the (candidate, split) arrays of fit times, score times and test scores."""
+        from sklearn.metrics import accuracy_score, make_scorer
+        res = _cv_results(candidates, n_splits, fit_t, score_t, scores)
+        self.cv_results_ = res
+        self.n_splits_ = n_splits
+        self.scorer_ = make_scorer(accuracy_score)
+        self.multimetric_ = False
+        self.best_index_ = int(res["rank_test_score"].argmin())
+        self.best_score_ = float(res["mean_test_score"][self.best_index_])
+        self.best_params_ = candidates[self.best_index_]
+
+    # GridSearchCV delegates these to best_estimator_
+    def predict(self, X):
+        return self.best_estimator_.predict(X)
+
+    def decision_function(self, X):
+        return self.best_estimator_.decision_function(X)
+
+    def predict_proba(self, X):
+        return self.best_estimator_.predict_proba(X)
+
+    def score(self, X, y):
+        return self.best_estimator_.score(X, y)
+
+
+def _log_best(grid_search):
+    """The lines the reference's ``find_best_*`` log after their search; returns the winner."""
+    logger.info('\n Best estimator:')
+    logger.info(grid_search.best_estimator_)
+    logger.info('\n Best score for {}-fold search:'.format(grid_search.n_splits_))
+    logger.info(grid_search.best_score_)
+    logger.info('\n Best hyperparameters:')
+    logger.info(grid_search.best_params_)
+    return grid_search.best_estimator_
+
+
+# ---- GridSearchSVC and the reference's find_best_svm_estimator ---------------------------------------------------------------------
+_GRID_KEYS = ("C", "kernel", "gamma")
+# SVC constructor parameters that carry from the base estimator into every fit
+_CARRY = ("C", "probability", "class_weight", "random_state", "cache_size", "tol", "shrinking", "max_iter",
+          "decision_function_shape", "break_ties")
+# where the kernel matrices of a searched group are afterwards, three dicts by kernel key: ``host`` copies, ``fetch`` functions that
+# copy one back from the device, ``resident`` (matrix index, ``solve`` hook) pairs of those kept there
+_Matrices =namedtuple("_Matrices", "host fetch resident")
+
+
+class GridSearchSVC(_GridSearch):
+    """``GridSearchCV(SVC(...), param_grid)`` for C, ``linear`` / ``rbf`` kernels and numeric gamma, on GPU kernel matrices.
+
+    The subset of ``GridSearchCV``'s surface that train.py uses: ``fit(X, y)``, ``best_estimator_``, ``best_params_``, ``best_score_``,
+    ``best_index_``, ``cv_results_``, ``n_splits_``, ``refit_time_``, ``scorer_`` (accuracy).  Fit order: rows validated; every distinct
+    kernel of the grid computed by ``rml_gram`` (grouped so that the host copies stay under ``max_gram_bytes``); the candidates in
+    ``ParameterGrid`` order x the splits fitted by libsvm on ``K[train, train]`` and scored on ``K[test, train]`` on a pool of
+    ``n_jobs`` threads (libsvm releases the GIL); the best point refitted on all rows.
+
+    ``solver="device"`` keeps the kernel matrices on the GPU and replaces the host fits and scores of the search: per group of
+    kernels, every candidate x split x class-pair dual is solved by ONE ``rml_smo_solve`` call (libsvm's SMO, one workgroup per
+    dual, the same iterates bit for bit) and every held-out row is scored by ONE ``rml_smo_score`` call; only the winner's matrix
+    is copied back, for the same host refit (``probability`` and libsvm's Platt step included).  ``tol``, ``shrinking``,
+    ``max_iter`` and ``class_weight`` of the base estimator are honoured (weighted C as scikit-learn forms it: ``compute_class_weight``
+    on the fold's labels, times C).  A split whose training rows miss a class is fitted on the host as before.  The batch has no
+    per-fit times: ``fit_time`` / ``score_time`` of a device fit are the batch's solve / score time divided evenly among its fits.
+    ``solver="host"`` (the default) is the search described above.
+
+    ``refit_solver="device"`` refits the winner on the GPU as well (``fit_svc``'s batch: the duals of libsvm's fit and of its Platt
+    cross-validation in one ``rml_smo_solve`` call, ``rml_platt_fit`` per class pair) -- after a device search on the matrix still
+    resident there, so that no kernel matrix is copied back at all.  The estimator is the same, bit for bit.
+    ``refit_solver="host"`` (the default) is libsvm's fit on the host copy of the winner's matrix."""
+
+    def __init__(self, estimator, param_grid, cv=5, n_jobs=4, refit=True, device=None, max_gram_bytes=8 << 30, scoring=None,
+                 verbose=0, solver="host", refit_solver="host"):
+        super().__init__(estimator, param_grid, cv, n_jobs, refit, device, scoring, verbose)
+        self.max_gram_bytes = max_gram_bytes
+        self.solver = solver
+        self.refit_solver = refit_solver
+
+    # ---- argument checks (before any work) ----
+    def _check(self):
+        from sklearn.svm import SVC
+        if self.solver not in ("host", "device"):
+            raise ValueError("GridSearchSVC: solver must be 'host' or 'device', got %r" % (self.solver,))
+        if self.refit_solver not in ("host", "device"):
+            raise ValueError("GridSearchSVC: refit_solver must be 'host' or 'device', got %r" % (self.refit_solver,))
+        candidates, base = self._check_search("GridSearchSVC", SVC, "SVC.score, GridSearchCV's default", _GRID_KEYS)
+        for p in candidates:
+            _check_kernel("GridSearchSVC", p.get("kernel", base["kernel"]), p.get("gamma", base["gamma"]), p.get("C", base["C"]))
+        return candidates, base
+
+    def _check_data(self, X32, y):
+        # what max_gram_bytes and n_jobs can raise in the stages of fit is raised here: before the search prints its header
+        self._groups([], None, X32.shape[0]), self._threads(1)
+
+    def _key(self, p, base):
+        return _kernel_key(p.get("kernel", base["kernel"]), p.get("gamma", base["gamma"]))
+
+    def _svc(self, p, base, kernel, probability=None):
+        from sklearn.svm import SVC
+        kw = {k: base[k] for k in _CARRY}
+        kw["C"] = p.get("C", base["C"])
+        if probability is not None:
+            kw["probability"] = probability
+        return SVC(kernel=kernel, **kw)
+
+    def _smo_plan(self, candidates, base, grp, splits, y):
+        """The batch of one group of kernels for ``_smo``: per candidate of the group (ParameterGrid order) and split, one fit made of
+        one dual per class pair in libsvm's order.  Returns (plan, [(ci, si) of fit f], [(ci, si) left to the host])."""
+        from sklearn.utils.class_weight import compute_class_weight
+        classes = np.unique(y)
+        nc = len(classes)
+        yi = np.searchsorted(classes, y).astype(np.int32)
+        pairs = [(a, b) for a in range(nc) for b in range(a + 1, nc)]
+        rows, test_rows, test_y = [], [], []
+        per_split = {}                      # si -> ([(rows_off, l, n_pos) per pair], class weights)
+        n_rows = 0
+        for si, (tr, te) in enumerate(splits):
+            if not 2 <= nc <= 8 or len(np.unique(yi[tr])) < nc or len(te) == 0:
+                continue                    # a class without rows in this fold: libsvm fits another model -- the host path's job
+            cw = base["class_weight"]
+            w = np.ones(nc) if cw is None else compute_class_weight(cw, classes=classes, y=y[tr])
+            subs = []
+            for a, b in pairs:
+                ra, rb = tr[yi[tr] == a], tr[yi[tr] == b]
+                rows += [ra, rb]
+                subs.append((n_rows, len(ra) + len(rb), len(ra)))
+                n_rows += len(ra) + len(rb)
+            per_split[si] = (subs, w)
+        problems, fits, on_device, host = [], [], [], []
+        n_alpha = n_test = 0
+        for ci, p in enumerate(candidates):
+            key = self._key(p, base)
+            if key not in grp:
+                continue
+            C = float(p.get("C", base["C"]))
+            for si, (tr, te) in enumerate(splits):
+                if si not in per_split:
+                    host.append((ci, si))
+                    continue
+                subs, w = per_split[si]
+                fits.append((len(problems), len(te), n_test))
+                on_device.append((ci, si))
+                test_rows.append(te)
+                test_y.append(yi[te])
+                n_test += len(te)
+                for (off, l, n_pos), (a, b) in zip(subs, pairs):
+                    problems.append((grp.index(key), l, n_pos, int(bool(base["shrinking"])), int(base["max_iter"]), 0, off, n_alpha,
+                                     C * w[a], C * w[b], float(base["tol"])))
+                    n_alpha += l
+        plan = {"problems": np.array(problems, dtype=SMO_PROBLEM), "rows": _cat_i32(rows), "fits": np.array(fits, dtype=SMO_FIT),
+                "test_rows": _cat_i32(test_rows), "test_y": _cat_i32(test_y), "n_classes": nc}
+        return plan, on_device, host
+
+    # ---- the stages of fit ----
+    def _threads(self, n_fits):
+        # joblib's convention (what GridSearchCV's n_jobs means): None -> 1, -1 -> every CPU this process may use, -2 -> all but one;
+        # joblib counts the CPUs of the process's affinity mask and cgroup quota, not the whole machine's
+        from joblib import effective_n_jobs
+        return max(1, min(effective_n_jobs(self.n_jobs), n_fits))
+
+    def _groups(self, candidates, base, N):
+        """The distinct kernels of the grid in candidate order, in groups of at most 8 whose host copies stay under ``max_gram_bytes``."""
+        mat_bytes = N * N * 8
+        per = min(8, int(self.max_gram_bytes // mat_bytes))
+        if per < 1:
+            raise ValueError("GridSearchSVC: one %d x %d kernel matrix takes %d bytes, more than max_gram_bytes=%d"
+                             % (N, N, mat_bytes, self.max_gram_bytes))
+        keys = []
+        for p in candidates:
+            k = self._key(p, base)
+            if k not in keys:
+                keys.append(k)
+        return [keys[i:i + per] for i in range(0, len(keys), per)]
+
+    def _fit_on_host(self, s, pool, mats, todo):
+        """libsvm's fit and score of the (candidate, split) pairs ``todo`` on slices of the host matrices ``mats``, on the pool."""
+        # The split fits run WITHOUT libsvm's Platt step (probability=False), whatever the base estimator says: the score is
+        # accuracy of predict(), which does not use the Platt parameters, and the SMO solve is the same either way (libsvm fits
+        # the pairwise models independently of the Platt cross-validation), so decision values and split scores are the bits
+        # GridSearchCV gets -- at a sixth of the SMO work.  It also keeps libsvm's process-wide random generator (used only by
+        # that cross-validation, outside the GIL) out of the concurrent fits.  The refit below keeps the base estimator's setting.
+        def one(K, ci, si):
+            tr, te = s.splits[si]
+            est = self._svc(s.candidates[ci], s.base, "precomputed", probability=False)
+            t0 = time.perf_counter()
+            est.fit(K[np.ix_(tr, tr)], s.y[tr])
+            t1 = time.perf_counter()
+            acc = est.score(K[np.ix_(te, tr)], s.y[te])
+            t2 = time.perf_counter()
+            s.scores[ci, si], s.fit_t[ci, si], s.score_t[ci, si] = acc, t1 - t0, t2 - t1
+            self._end_line(s.candidates[ci], si, len(s.splits), t2 - t0)
+
+        jobs = [pool.submit(one, mats[self._key(s.candidates[ci], s.base)], ci, si) for ci, si in todo]
+        for j in jobs:
+            j.result()
+
+    def _search_host(self, s, grp, pool):
+        """One group of kernels searched on the host: its matrices by ``_gram``, every fit of its candidates on the pool."""
+        todo = [(ci, si) for ci, p in enumerate(s.candidates) if self._key(p, s.base) in grp for si in range(len(s.splits))]
+        mats = dict(zip(grp, _gram(s.X32, grp, self.device)))
+        self._fit_on_host(s, pool, mats, todo)
+        return _Matrices(mats, {}, {})
+
+    def _search_device(self, s, grp, pool):
+        """One group of kernels searched on the device: ``_smo_plan``'s batch by ``_smo``; what it leaves to the host is fitted there."""
+        plan, on_device, todo = self._smo_plan(s.candidates, s.base, grp, s.splits, s.y)
+        out = _smo(s.X32, grp, plan, self.device)
+        fetch = {k: (lambda i=i, m=out["matrix"]: m(i)) for i, k in enumerate(grp)}
+        resident = {k: (i, out["solve"]) for i, k in enumerate(grp)} if "solve" in out else {}
+        for f, (ci, si) in enumerate(on_device):
+            s.scores[ci, si] = float(out["correct"][f]) / len(s.splits[si][1])
+            s.fit_t[ci, si] = out["solve_s"] / len(on_device)
+            s.score_t[ci, si] = out["score_s"] / len(on_device)
+            self._end_line(s.candidates[ci], si, len(s.splits), s.fit_t[ci, si] + s.score_t[ci, si])
+        mats = {k: fetch[k]() for k in sorted({self._key(s.candidates[ci], s.base) for ci, _ in todo}, key=grp.index)}
+        self._fit_on_host(s, pool, mats, todo)
+        return _Matrices(mats, fetch, resident)
+
+    def _refit(self, s, where):
+        """The winner refitted on all rows, on its kernel matrix from ``where`` (the ``_Matrices`` of the last group) or computed again."""
+        from sklearn.base import clone
+        best = self.best_params_
+        key = self._key(best, s.base)
+        if self.refit_solver == "device":
+            # the winner's matrix where the search left it, or (host search, or a winner of an earlier group) computed again
+            matrix, run = where.resident.get(key, (0, lambda plan: _smo(s.X32, [key], plan, self.device)))
+            params = {k: s.base[k] for k in _FIT_CARRY}
+            params["C"] = best.get("C", s.base["C"])
+            t0 = time.perf_counter()
+            fitted = _fit_batch(params, s.y, run, matrix)
+            self.refit_time_ = time.perf_counter() - t0
+        else:
+            K = (where.host[key] if key in where.host else where.fetch[key]() if key in where.fetch
+                 else _gram(s.X32, [key], self.device)[0])
+            t0 = time.perf_counter()
+            pre = self._svc(best, s.base, "precomputed").fit(K, s.y)
+            self.refit_time_ = time.perf_counter() - t0
+            params = pre.get_params()
+            fitted = {k: v for k, v in vars(pre).items() if k not in params}
+        self.best_estimator_ = _adopt(clone(self.estimator).set_params(**best), fitted, s.X32, key)
+
+    def fit(self, X, y):
+        candidates, base = self._check()
+        X32, y, splits = self._setup(X, y, candidates)
+        groups = self._groups(candidates, base, X32.shape[0])
+        scores = np.zeros((len(candidates), len(splits)))         # with fit_t, score_t: (candidate, split) arrays the fits fill in
+        s = SimpleNamespace(X32=X32, y=y, candidates=candidates, base=base, splits=splits, scores=scores, fit_t=np.zeros_like(scores),
+                            score_t=np.zeros_like(scores))
+        search = self._search_device if self.solver == "device" else self._search_host
+        with ThreadPoolExecutor(max_workers=self._threads(len(candidates) * len(splits))) as pool:
+            for grp in groups:
+                where = search(s, grp, pool)            # the refit reads that of the last group
+        self._finish(candidates, len(splits), s.fit_t, s.score_t, s.scores)
+        if self.refit:
+            self._refit(s, where)
+        self.classes_ = np.unique(y)
+        return self
+
+
+def find_best_svm_estimator(X, y, cv, random_seed, solver="host", refit_solver="host"):
+    """Exhaustive search over specified parameter values for svm (train.py:462-491, the same grid, base estimator and log lines).
+    ``solver="device"`` runs the search's fits on the GPU and ``refit_solver="device"`` the refit of the winner (GridSearchSVC);
+    the result is the same.
+
+    Returns:
+        optimized svm estimator.
+
+    Note:
+        https://www.csie.ntu.edu.tw/~cjlin/papers/guide/guide.pdf
+    """
+    from sklearn import svm
+    print('\n Finding best svm estimator...')
+    Cs = [0.01, 0.1, 1, 10, 100]
+    gammas = [0.001, 0.01, 0.1, 1, 10]
+    param_grid = [
+        {'C': Cs, 'kernel': ['linear']},
+        {'C': Cs, 'gamma': gammas, 'kernel': ['rbf']}
+    ]
+    init_est = svm.SVC(probability=True, class_weight='balanced',
+                       random_state=random_seed, cache_size=1000, verbose=False)
+    grid_search = GridSearchSVC(estimator=init_est, param_grid=param_grid, verbose=2, n_jobs=4, cv=cv, solver=solver,
+                                refit_solver=refit_solver)
+    grid_search.fit(X, y)
+    return _log_best(grid_search)
+
+
+# ---- GridSearchSGD and the reference's find_best_sgd_svm_estimator -----------------------------------------------------------------
+_SGD_GRID_KEYS = ("alpha", "penalty", "l1_ratio", "average", "max_iter", "tol", "n_iter_no_change", "shuffle")
+
+
+class GridSearchSGD(_GridSearch):
+    """``GridSearchCV(SGDClassifier(loss='log_loss'), param_grid)`` on the GPU: the counterpart of ``GridSearchSVC`` for the
+    reference's default model, with the same subset of ``GridSearchCV``'s surface (``fit(X, y)``, ``best_estimator_``,
+    ``best_params_``, ``best_score_``, ``best_index_``, ``cv_results_``, ``n_splits_``, ``refit_time_``, ``scorer_``: accuracy).
+
+    The rows are uploaded once.  Every candidate (``ParameterGrid`` order) x split x class is one problem of ONE ``rml_sgd_solve``
+    call, every held-out row is scored by ONE ``rml_sgd_score`` call from the weights where the solve left them, and the winner is
+    refitted on all rows by one more solve on the resident rows (``fit_sgd``'s path).  The grid may vary ``alpha``, ``penalty``,
+    ``l1_ratio``, ``average``, ``max_iter``, ``tol``, ``n_iter_no_change`` and ``shuffle``; everything else is the base estimator's,
+    under ``fit_sgd``'s restrictions.  ``class_weight`` is formed per fold as scikit-learn forms it.  The batch has no per-fit
+    times: ``fit_time`` / ``score_time`` are the batch's solve / score time divided evenly among its fits."""
+
+    def __init__(self, estimator, param_grid, cv=5, refit=True, device=None, scoring=None, verbose=0, n_jobs=None):
+        # n_jobs is accepted for GridSearchCV's signature; the batch is one launch whatever it says
+        super().__init__(estimator, param_grid, cv, n_jobs, refit, device, scoring, verbose)
+
+    def _check(self):
+        from sklearn.linear_model import SGDClassifier
+        candidates, base = self._check_search("GridSearchSGD", SGDClassifier, "GridSearchCV's default for a classifier", _SGD_GRID_KEYS)
+        prms = [_sgd_params(dict(base, **p), "GridSearchSGD") for p in candidates]
+        return candidates, base, prms
+
+    def _check_data(self, X32, y):
+        if not 2 <= len(np.unique(y)) <= 8:
+            raise ValueError("GridSearchSGD takes 2..8 classes, got %d" % len(np.unique(y)))
+
+    def _plan(self, prms, base, splits, y):
+        """The batch of the search for ``_sgd``: per candidate and split one fit of one problem per class (one for two classes), on
+        the split's shared row list and per-class label lists.  Returns (plan, [(ci, si) of fit f])."""
+        from sklearn.utils.class_weight import compute_class_weight
+        classes = np.unique(y)
+        nc = len(classes)
+        yi = np.searchsorted(classes, y).astype(np.int32)
+        positives = [1] if nc == 2 else list(range(nc))
+        rows, ys, test_rows, test_y, per_split = [], [], [], [], []
+        n_rows = n_y = 0
+        for tr, te in splits:
+            if len(np.unique(yi[tr])) < nc:
+                raise NotImplementedError("GridSearchSGD: a split whose training rows miss a class (scikit-learn fits a model of fewer "
+                                          "classes there)")
+            _sgd_check_rows("GridSearchSGD", len(tr))
+            w = compute_class_weight(base["class_weight"], classes=classes, y=y[tr])
+            y_offs = []
+            for c in positives:
+                ys.append((yi[tr] == c).astype(np.int32))
+                y_offs.append(n_y)
+                n_y += len(tr)
+            per_split.append((n_rows, y_offs, w))
+            rows.append(tr)
+            n_rows += len(tr)
+        problems, fits, which = [], [], []
+        n_test = 0
+        for ci, prm in enumerate(prms):
+            for si, (tr, te) in enumerate(splits):
+                rows_off, y_offs, w = per_split[si]
+                seeds = _sgd_seeds(base["random_state"], nc)
+                fits.append((len(problems), len(te), n_test))
+                which.append((ci, si))
+                test_rows.append(te)
+                test_y.append(yi[te])
+                n_test += len(te)
+                for k, c in enumerate(positives):
+                    problems.append(_sgd_problem(prm, len(tr), seeds[k], rows_off, y_offs[k], len(problems), w[c],
+                                                 w[0] if nc == 2 else 1.0))
+        plan = {"problems": np.array(problems, dtype=SGD_PROBLEM), "rows": _cat_i32(rows), "y": _cat_i32(ys), "n_out": len(problems),
+                "fits": np.array(fits, dtype=SGD_FIT), "test_rows": _cat_i32(test_rows), "test_y": _cat_i32(test_y), "n_classes": nc}
+        return plan, which
+
+    def fit(self, X, y):
+        import warnings
+        from sklearn.base import clone
+        from sklearn.exceptions import ConvergenceWarning
+        candidates, base, prms = self._check()
+        X32, y, splits = self._setup(X, y, candidates)
+        n_splits = len(splits)
+        plan, which = self._plan(prms, base, splits, y)
+        out = _sgd(X32, plan, self.device)
+        _sgd_check_overflow(out)
+        probs = plan["problems"]
+        if ((probs["tol"] > -np.inf) & (out["n_iter"][probs["out"]] == probs["max_iter"])).any():
+            warnings.warn(_SGD_MAX_ITER, ConvergenceWarning)
+        scores = np.zeros((len(candidates), n_splits))
+        fit_t = np.full_like(scores, out["solve_s"] / len(which))
+        score_t = np.full_like(scores, out["score_s"] / len(which))
+        for f, (ci, si) in enumerate(which):
+            scores[ci, si] = float(out["correct"][f]) / len(splits[si][1])
+            self._end_line(candidates[ci], si, n_splits, fit_t[ci, si] + score_t[ci, si])
+        self._finish(candidates, n_splits, fit_t, score_t, scores)
+        self.solve_time_, self.score_time_ = out["solve_s"], out["score_s"]
+        if self.refit:
+            est = clone(self.estimator).set_params(**self.best_params_)
+            _sgd_prepare(est, "GridSearchSGD")
+            t0 = time.perf_counter()
+            self.best_estimator_ = _sgd_fit(est, X32, y, out["solve"], "GridSearchSGD")
+            self.refit_time_ = time.perf_counter() - t0
+        self.classes_ = np.unique(y)
+        return self
+
+
+def find_best_sgd_svm_estimator(X, y, cv, random_seed, device=None):
+    """Exhaustive search over specified parameter values for svm using sgd (train.py:350-381, the same grid, base estimator and
+    log lines), every fit of the search and the refit on the GPU (GridSearchSGD).
+
+    Returns:
+        optimized svm estimator.
+    """
+    from sklearn import linear_model
+    max_iter = max(np.ceil(10**6 / len(X)), 1000)
+    small_alphas = [10.0e-08, 10.0e-09, 10.0e-10]
+    alphas = [10.0e-04, 10.0e-05, 10.0e-06, 10.0e-07]
+    l1_ratios = [0.075, 0.15, 0.30]
+    param_grid = [
+        {'alpha': alphas, 'penalty': ['l1', 'l2'], 'average': [False]},
+        {'alpha': alphas, 'penalty': ['elasticnet'], 'average': [False],
+         'l1_ratio': l1_ratios},
+        {'alpha': small_alphas, 'penalty': ['l1', 'l2'], 'average': [True]},
+        {'alpha': small_alphas, 'penalty': ['elasticnet'], 'average': [True],
+         'l1_ratio': l1_ratios}
+    ]
+    init_est = linear_model.SGDClassifier(loss='log', max_iter=max_iter,
+                                          random_state=random_seed, n_jobs=-1, warm_start=True)
+    grid_search = GridSearchSGD(estimator=init_est, param_grid=param_grid, verbose=2, n_jobs=-1, cv=cv, device=device)
+    grid_search.fit(X, y)
+    return _log_best(grid_search)
+
+
+# ---- the flows of the reference: sgd_fit and svc_fit, with their class balancing and feature rows ----------------------------------
 def balance_indices(labels):
     """The index form of ``balance_classes``: the positions it takes its balanced set from, in its order, or None where the
     labels are balanced already (it then returns its input)."""
@@ -1658,6 +1653,7 @@ def svc_fit(train, proj_mask, epochs, folds=5, batch_size=32, solver="host", ref
     return find_best_svm_estimator(Xh, y_train, list(skf.split(Xh, y_train)), RANDOM_SEED, solver=solver, refit_solver=refit_solver)
 
 
+# ---- calibration and evaluation ----------------------------------------------------------------------------------------------------
 def calibrate_prefit(clf, X_val, y_val):
     """``CalibratedClassifierCV(clf, cv='prefit').fit(X_val, y_val)`` (train.py:722-724) for a fitted SVC or SGDClassifier: the
     decision values of the validation rows come from the GPU twin (``from_sklearn(clf).decision_function``), the two-parameter
