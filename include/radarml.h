@@ -883,6 +883,32 @@ int rml_sgan_generate(rml_ctx* ctx, const float* z, int64_t N, int latent_dim, i
                       const float* dense_b, const void* up_wt, const float* up_bias, const float* out_w, const float* out_b, float* y_xz,
                       float* y_yz, float* y_xy, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- SGAN discriminator in training: the 3x3 stride-2 convolutions of layers 2 and 3 and their gradients (sgan.py:137-158;
+ * csrc/conv_train.hip) -------------------------------------------------------------------------------------------------------------
+ * A VALID convolution of an already padded tensor, no bias.  x: N x hp x wp x cin (NHWC, dense), hp = 2 Ho + 1, wp = 2 Wo + 1 -- what
+ * rml_bn_lrelu_pad_forward / rml_conv1_bn_lrelu_pad_forward write; w: [cout][3][3][cin], the channels_last storage of a (cout, cin, 3, 3)
+ * tensor; z: N x Ho x Wo x cout.  All of float16 (dtype 0) or bfloat16 (dtype 1), float32 accumulation on the matrix cores, one rounding.
+ *   forward  z[n,oy,ox,co] = sum x[n,2oy+ky,2ox+kx,ci] w[co,ky,kx,ci]
+ *   dgrad    dx[n,y,x,ci]  = sum over ky = y, kx = x (mod 2), co of dz[n,(y-ky)/2,(x-kx)/2,co] w[co,ky,kx,ci]: EVERY element of the padded dx
+ *            is written (the bottom / right pad row and column too)
+ *   wgrad    dw[co,ky,kx,ci] = sum over n, oy, ox of dz[n,oy,ox,co] x[n,2oy+ky,2ox+kx,ci], of the half type, in w's layout
+ * No atomics, no zeroed workspace; every output has one summation order that depends on the shapes alone (the same call gives the same
+ * bits; a sample's z does not depend on the batch around it).  Asynchronous on `stream`, no allocation, no synchronisation.
+ * rml_conv3s2_supported (HOST): cin -> cout of 128 -> 64 or 64 -> 32, hp and wp odd in [3, 8193]; anything else: 0, and the three passes
+ * return RML_ERR_UNSUPPORTED before any launch.  workspace: rml_conv3s2_workspace_bytes(..., pass) bytes (0 for unsupported shapes),
+ * 16-byte aligned like every tensor; its contents need no initialisation. */
+#define RML_CONV3S2_FORWARD 0
+#define RML_CONV3S2_DGRAD 1
+#define RML_CONV3S2_WGRAD 2
+int rml_conv3s2_supported(int cin, int cout, int hp, int wp);
+int64_t rml_conv3s2_workspace_bytes(rml_ctx* ctx, int64_t n, int hp, int wp, int cin, int cout, int pass);
+int rml_conv3s2_forward(rml_ctx* ctx, const void* x, const void* w, int dtype, int64_t n, int hp, int wp, int cin, int cout, void* z,
+                        void* workspace, int64_t workspace_bytes, void* stream);
+int rml_conv3s2_dgrad(rml_ctx* ctx, const void* dz, const void* w, int dtype, int64_t n, int hp, int wp, int cin, int cout, void* dx,
+                      void* workspace, int64_t workspace_bytes, void* stream);
+int rml_conv3s2_wgrad(rml_ctx* ctx, const void* x, const void* dz, int dtype, int64_t n, int hp, int wp, int cin, int cout, void* dw,
+                      void* workspace, int64_t workspace_bytes, void* stream);
+
 /* ---- Adam update of the SGAN discriminator (sgan.py:206, 214: Adam(lr=0.0002, beta_1=0.5) inside train_on_batch, sgan.py:525-532) ----
  * ONE pass over all parameters with the loss-scale bookkeeping of a half-precision step on the device (csrc/optim.hip).
  * table: DEVICE array of n_tensors + 1 records of rml_adam_entry_bytes() bytes each,

@@ -492,6 +492,103 @@ def conv1_bn_lrelu_pad(x_padded, conv, bn, slope, pad, dtype):
     return y
 
 
+CONV3S2_FORWARD, CONV3S2_DGRAD, CONV3S2_WGRAD = 0, 1, 2
+
+
+def conv3s2_wgrad_plan(pixels):
+    """``(pieces, pixels per piece)`` of the weight gradient of csrc/conv_train.hip (its ``wgrad_plan``): a function of the number of
+    output pixels N * Ho * Wo alone."""
+    pixels = int(pixels)
+    n = min(max(-(-pixels // 256), 1), 128)
+    ln = max(-(-(-(-pixels // n)) // 64) * 64, 64)
+    return (-(-pixels // ln) if pixels > 0 else 1), ln
+
+
+def conv3s2_wgrad_chain(pixels, cin):
+    """Longest float32 summation chain behind an element of the weight gradient: the pixels of one piece (the matrix cores add a wave's
+    share of them one after the other) + the partial sums ``k_conv_wreduce`` adds (pieces x the k phases of a workgroup)."""
+    pieces, ln = conv3s2_wgrad_plan(pixels)
+    return ln + pieces * (4 // (int(cin) // 32))
+
+
+def _conv3s2_function():
+    """torch.autograd.Function around csrc/conv_train.hip: the 3x3 stride-2 convolution of an already padded channels_last half tensor,
+    its data gradient and its weight gradient, each one call into the library on the current stream."""
+    torch = _torch()
+    if getattr(_conv3s2_function, "_cls", None) is not None:
+        return _conv3s2_function._cls
+    from . import _lib
+
+    def run(name, which, a, b, out, dtype, n, hp, wp, cin, cout):
+        lib = _lib.load()
+        dev = out.device
+        with torch.cuda.device(dev):
+            hctx = _lib.context(dev)
+            nbytes = int(lib.rml_conv3s2_workspace_bytes(hctx, n, hp, wp, cin, cout, which))
+            ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+            _lib.check(getattr(lib, name)(hctx, _lib.ptr(a), _lib.ptr(b), 1 if dtype == torch.bfloat16 else 0, n, hp, wp, cin, cout,
+                                          _lib.ptr(out), _lib.ptr(ws), nbytes, _lib.stream_ptr(dev)), name)
+
+    class Conv3S2(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, x, w):
+            n, cin, hp, wp = x.shape
+            cout = w.shape[0]
+            z = torch.empty((n, cout, (hp - 1) // 2, (wp - 1) // 2), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
+            if n:
+                run("rml_conv3s2_forward", CONV3S2_FORWARD, x, w, z, x.dtype, n, hp, wp, cin, cout)
+            ctx.save_for_backward(x, w)
+            return z
+
+        @staticmethod
+        def backward(ctx, dz):
+            x, w = ctx.saved_tensors
+            n, cin, hp, wp = x.shape
+            cout = w.shape[0]
+            if dz.dtype != x.dtype or not dz.is_contiguous(memory_format=torch.channels_last):
+                dz = dz.to(x.dtype).contiguous(memory_format=torch.channels_last)
+            dx = dw = None
+            if ctx.needs_input_grad[0]:
+                dx = torch.empty_like(x, memory_format=torch.channels_last)
+                if n:
+                    run("rml_conv3s2_dgrad", CONV3S2_DGRAD, dz, w, dx, x.dtype, n, hp, wp, cin, cout)
+            if ctx.needs_input_grad[1]:
+                if n:
+                    dw = torch.empty_like(w, memory_format=torch.channels_last)
+                    run("rml_conv3s2_wgrad", CONV3S2_WGRAD, x, dz, dw, x.dtype, n, hp, wp, cin, cout)
+                else:
+                    dw = torch.zeros_like(w, memory_format=torch.channels_last)
+            return dx, dw
+
+    _conv3s2_function._cls = Conv3S2
+    return Conv3S2
+
+
+def conv3s2_supported(x_padded, w_half):
+    """True when :func:`conv3s2` runs csrc/conv_train.hip on these tensors: CUDA, float16 or bfloat16 (both alike), a (Cout, Cin, 3, 3)
+    kernel on an (N, Cin, 2 Ho + 1, 2 Wo + 1) input of a shape ``rml_conv3s2_supported`` takes (128 -> 64 or 64 -> 32 channels)."""
+    torch = _torch()
+    if not (x_padded.is_cuda and w_half.is_cuda and x_padded.dtype in (torch.float16, torch.bfloat16) and w_half.dtype == x_padded.dtype
+            and x_padded.dim() == 4 and w_half.dim() == 4 and tuple(w_half.shape[2:]) == (3, 3) and w_half.shape[1] == x_padded.shape[1]):
+        return False
+    from . import _lib
+    return bool(_lib.load().rml_conv3s2_supported(int(w_half.shape[1]), int(w_half.shape[0]), int(x_padded.shape[2]), int(x_padded.shape[3])))
+
+
+def conv3s2(x_padded, w_half):
+    """``F.conv2d(x_padded, w_half, None, stride=2)`` of an already padded input -- what ``bn_lrelu_pad`` / ``conv1_bn_lrelu_pad``
+    write -- on the project's own matrix-core kernels (csrc/conv_train.hip), forward and both gradients: no convolution library, no
+    zeroed workspace, the same bits on every call, and a backward that computes only the gradients autograd asks for.  Anything the
+    kernels do not take (:func:`conv3s2_supported`: CPU tensors, float32, other channel counts) IS ``F.conv2d``, bit for bit."""
+    torch = _torch()
+    if not conv3s2_supported(x_padded, w_half):
+        import torch.nn.functional as F
+        return F.conv2d(x_padded, w_half, None, stride=2)
+    x = x_padded if x_padded.is_contiguous(memory_format=torch.channels_last) else x_padded.contiguous(memory_format=torch.channels_last)
+    w = w_half if w_half.is_contiguous(memory_format=torch.channels_last) else w_half.contiguous(memory_format=torch.channels_last)
+    return _conv3s2_function().apply(x, w)
+
+
 def _conv7_tanh_function():
     """torch.autograd.Function around csrc/gen.hip: the generator's Conv2D(1, 7x7, 'same', tanh) output layer."""
     torch = _torch()

@@ -89,6 +89,9 @@ class Discriminator(_nn().Module):
         # backward of the fused conv + batch-norm layers: zeros for the (cancelled) convolution bias, or no gradient at all
         # (nn_common.fused_step_scope; DiscriminatorTrainer turns the zeros off unless torch's DDP wraps the model)
         self.zero_bias_grads = True
+        # the stride-2 convolutions of layers 2 and 3 in the fused training path: "library" (F.conv2d, i.e. MIOpen) or "hip"
+        # (nn_common.conv3s2: csrc/conv_train.hip, forward and both gradients; reproducible bit for bit)
+        self.conv_impl = "library"
         self._packs = {}                            # name -> (key of the tensors it was made from, value): _cached
         for mod in self.modules():
             if isinstance(mod, (nn.Conv2d, nn.Linear)):
@@ -96,16 +99,17 @@ class Discriminator(_nn().Module):
                 nn.init.zeros_(mod.bias)
 
     @staticmethod
-    def _branch(x, br, half=None):
+    def _branch(x, br, half=None, conv_impl="library"):
         """[Conv2D 'same' s2 + BatchNorm + LeakyReLU] x 3 (sgan.py:137-158).  On the GPU under half-precision autocast and
         in training mode: batch norm + LeakyReLU + the bottom/right zero pad of the next convolution are one fused HIP op
         (nn_common.bn_lrelu_pad), the convolutions run without their bias (batch norm cancels it; its gradient is exactly
         zero and is handed back as such), and the 1-channel first layer is one autograd node whose backward sums the weight
         gradient without materialising the gradient of the convolution output (nn_common.conv1_bn_lrelu_pad).
+        ``conv_impl="hip"``: the other convolutions of that path are nn_common.conv3s2 (csrc/conv_train.hip) instead of F.conv2d.
         Otherwise the plain PyTorch layers run."""
         import torch
         import torch.nn.functional as F
-        from .nn_common import bn_lrelu_pad, conv1_bn_lrelu_pad, tf_same_pad
+        from .nn_common import bn_lrelu_pad, conv1_bn_lrelu_pad, conv3s2, tf_same_pad
         layers = list(br)
         nlayer = len(layers) // 3
         even = all(s % (2 ** nlayer) == 0 for s in x.shape[-2:])
@@ -124,7 +128,8 @@ class Discriminator(_nn().Module):
                     and c % 8 == 0 and 256 % (c // 8) == 0 and bn.track_running_stats and bn.affine and bn.momentum is not None):
                 x = conv1_bn_lrelu_pad(x, conv, bn, act.negative_slope, pad, adt)
                 continue
-            z = F.conv2d(x, half.get(conv.weight, conv.weight) if half else conv.weight, None, stride=2)
+            w = half.get(conv.weight, conv.weight) if half else conv.weight
+            z = conv3s2(x, w.to(x.dtype)) if conv_impl == "hip" else F.conv2d(x, w, None, stride=2)
             x = bn_lrelu_pad(z, bn, act.negative_slope, pad=pad, conv_bias=conv.bias)
         return x
 
@@ -135,7 +140,7 @@ class Discriminator(_nn().Module):
         from .nn_common import cast_all, fused_step_scope
         adt = torch.get_autocast_dtype("cuda") if (xz.is_cuda and torch.is_autocast_enabled("cuda")) else None
         if not (_FUSED_LAYERS and self.training and adt in (torch.float16, torch.bfloat16)):
-            outs = [self._branch(x, br) for x, br in zip((xz, yz, xy), self.branches)]
+            outs = [self._branch(x, br, None, self.conv_impl) for x, br in zip((xz, yz, xy), self.branches)]
             fv = flatten_nhwc(torch.cat(outs, dim=1))
             h = self.drop(self.act(self.bn1(self.fc1(fv))))
             h = self.drop(self.act(self.bn2(self.fc2(h))))
@@ -146,7 +151,7 @@ class Discriminator(_nn().Module):
         ws += [self.fc1.weight, self.fc1.bias, self.fc2.weight, self.fc2.bias, self.fc3.weight, self.fc3.bias]
         half = dict(zip(ws, cast_all(adt, *ws)))
         with fused_step_scope(bias_grads=self.zero_bias_grads):
-            outs = [self._branch(x, br, half) for x, br in zip((xz, yz, xy), self.branches)]
+            outs = [self._branch(x, br, half, self.conv_impl) for x, br in zip((xz, yz, xy), self.branches)]
         fv = flatten_nhwc(torch.cat(outs, dim=1))
         h = self.drop(self.act(self.bn1(F.linear(fv, half[self.fc1.weight], half[self.fc1.bias]))))
         h = self.drop(self.act(self.bn2(F.linear(h, half[self.fc2.weight], half[self.fc2.bias]))))
@@ -440,8 +445,14 @@ class DiscriminatorTrainer:
     """c_model / d_model ``train_on_batch`` (sgan.py:525-532) with the reference's optimizers, fp16 autocast and,
     when torch.distributed is initialised, DistributedDataParallel gradient all-reduce."""
 
-    def __init__(self, model, lr=2e-4, beta1=0.5, amp_dtype="float16", ddp=None, use_graph=False, tune_convolutions=False):
-        """``use_graph``: capture forward + backward of each head in a HIP graph (torch.cuda.graphs) after three eager
+    def __init__(self, model, lr=2e-4, beta1=0.5, amp_dtype="float16", ddp=None, use_graph=False, tune_convolutions=False,
+                 convolutions="library"):
+        """``convolutions``: "library" (default) leaves the model's layer-2 and layer-3 convolutions to ``F.conv2d``; "hip" runs them and
+        their gradients on csrc/conv_train.hip (``model.conv_impl``; nn_common.conv3s2): no convolution library, no workspace zeroing,
+        and a step that gives the same bits on every run.  Every update that goes through the model follows it -- c, d, d on fakes,
+        the generator update of :class:`GanTrainer`, graph replay and both ddp modes.  Any other value: ValueError.
+
+        ``use_graph``: capture forward + backward of each head in a HIP graph (torch.cuda.graphs) after three eager
         warm-up steps and replay it afterwards; the optimizer, the loss scaler and the gradient all-reduce stay outside
         the graph.  Inputs must keep their shapes.  With the fused layers the step is launch-bound on the host side,
         which is what the graph removes.
@@ -461,6 +472,9 @@ class DiscriminatorTrainer:
         weight-gradient kernel win)."""
         import torch
         import torch.distributed as dist
+        if convolutions not in ("library", "hip"):
+            raise ValueError("convolutions must be 'library' or 'hip', got %r" % (convolutions,))
+        model.conv_impl = convolutions
         self._tune = bool(tune_convolutions)
         self.model = model
         self.device = next(model.parameters()).device
@@ -718,13 +732,18 @@ def _evaluate_c(trainer, x, y, batch_size=4096, fused=False):
 DiscriminatorTrainer.evaluate = _evaluate_c
 
 
-def define_discriminator(xz_shape=(128, 128, 1), yz_shape=(128, 128, 1), xy_shape=(128, 128, 1), n_classes=3, device=None):
+def define_discriminator(xz_shape=(128, 128, 1), yz_shape=(128, 128, 1), xy_shape=(128, 128, 1), n_classes=3, device=None,
+                         convolutions="library"):
     """Counterpart of sgan.define_discriminator (sgan.py:160): one shared trunk; the d / c heads are the two
-    losses of :class:`DiscriminatorTrainer`."""
+    losses of :class:`DiscriminatorTrainer`.  ``convolutions``: the model's ``conv_impl`` ("library" or "hip", see the trainer)."""
     import torch
+    if convolutions not in ("library", "hip"):
+        raise ValueError("convolutions must be 'library' or 'hip', got %r" % (convolutions,))
     dev = torch.device(device) if device is not None else (
         torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu"))
-    return Discriminator([xz_shape, yz_shape, xy_shape], n_classes).to(dev).to(memory_format=torch.channels_last)
+    model = Discriminator([xz_shape, yz_shape, xy_shape], n_classes).to(dev).to(memory_format=torch.channels_last)
+    model.conv_impl = convolutions
+    return model
 
 
 # ---- generator (sgan.py:57-122) ------------------------------------------------------------------------------------------
