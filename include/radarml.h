@@ -909,6 +909,32 @@ int rml_conv3s2_dgrad(rml_ctx* ctx, const void* dz, const void* w, int dtype, in
 int rml_conv3s2_wgrad(rml_ctx* ctx, const void* x, const void* dz, int dtype, int64_t n, int hp, int wp, int cin, int cout, void* dw,
                       void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- SGAN generator in training: Conv2DTranspose(128 -> 128, 4x4, stride 2, 'same') and its gradients (sgan.py:65-87;
+ * csrc/convt_train.hip) ------------------------------------------------------------------------------------------------------------
+ * No bias (the batch norm behind the layer cancels it).  h, w are the INPUT plane.  x: N x h x w x cin (NHWC, dense); z, dz: N x 2h x 2w x
+ * cout; w: [cin][4][4][cout], the channels_last storage of torch's (cin, cout, 4, 4) ConvTranspose2d weight; dw like w.  All of float16
+ * (dtype 0) or bfloat16 (dtype 1), float32 accumulation on the matrix cores, one rounding.  With oy = 2 iy + ky - 1, ox = 2 ix + kx - 1
+ * and everything outside a plane zero:
+ *   forward  z[n,oy,ox,co]  = sum over iy, ix, ci of x[n,iy,ix,ci] w[ci,ky,kx,co]: at most 2 x 2 taps per output pixel, four phase GEMMs
+ *   dgrad    dx[n,iy,ix,ci] = sum over ky, kx, co of dz[n,2iy+ky-1,2ix+kx-1,co] w[ci,ky,kx,co]
+ *   wgrad    dw[ci,ky,kx,co] = sum over n, iy, ix of x[n,iy,ix,ci] dz[n,2iy+ky-1,2ix+kx-1,co], of the half type
+ * No atomics, no zeroed workspace; every output has one summation order that depends on the shapes alone (the same call gives the same
+ * bits; a sample's z and dx do not depend on the batch around it).  Asynchronous on `stream`, no allocation, no synchronisation.
+ * rml_convt4s2_supported (HOST): cin = cout = 128, h and w multiples of 8 in [8, 128] (the domain of rml_gen_up_supported); anything
+ * else: 0, and the three passes return RML_ERR_UNSUPPORTED before any launch.  workspace: rml_convt4s2_workspace_bytes(..., pass) bytes (0
+ * for unsupported shapes; a smaller one: RML_ERR_INVALID), 16-byte aligned like every tensor; its contents need no initialisation. */
+#define RML_CONVT4S2_FORWARD 0
+#define RML_CONVT4S2_DGRAD 1
+#define RML_CONVT4S2_WGRAD 2
+int rml_convt4s2_supported(int cin, int cout, int h, int w);
+int64_t rml_convt4s2_workspace_bytes(rml_ctx* ctx, int64_t n, int h, int w, int cin, int cout, int pass);
+int rml_convt4s2_forward(rml_ctx* ctx, const void* x, const void* w, int dtype, int64_t n, int h, int w_, int cin, int cout, void* z,
+                         void* workspace, int64_t workspace_bytes, void* stream);
+int rml_convt4s2_dgrad(rml_ctx* ctx, const void* dz, const void* w, int dtype, int64_t n, int h, int w_, int cin, int cout, void* dx,
+                       void* workspace, int64_t workspace_bytes, void* stream);
+int rml_convt4s2_wgrad(rml_ctx* ctx, const void* x, const void* dz, int dtype, int64_t n, int h, int w_, int cin, int cout, void* dw,
+                       void* workspace, int64_t workspace_bytes, void* stream);
+
 /* ---- Adam update of the SGAN discriminator (sgan.py:206, 214: Adam(lr=0.0002, beta_1=0.5) inside train_on_batch, sgan.py:525-532) ----
  * ONE pass over all parameters with the loss-scale bookkeeping of a half-precision step on the device (csrc/optim.hip).
  * table: DEVICE array of n_tensors + 1 records of rml_adam_entry_bytes() bytes each,

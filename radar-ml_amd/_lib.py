@@ -165,6 +165,14 @@ SIGNATURES = {
                                   c_void_p]),
     "rml_conv3s2_wgrad": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int64,
                                   c_void_p]),
+    "rml_convt4s2_supported": (c_int, [c_int, c_int, c_int, c_int]),
+    "rml_convt4s2_workspace_bytes": (c_int64, [c_void_p, c_int64, c_int, c_int, c_int, c_int, c_int]),
+    "rml_convt4s2_forward": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int64,
+                                     c_void_p]),
+    "rml_convt4s2_dgrad": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int64,
+                                   c_void_p]),
+    "rml_convt4s2_wgrad": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int64,
+                                   c_void_p]),
     "rml_adam_entry_bytes": (c_int, []),
     "rml_adam_step": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_float, c_float, c_float, c_float, c_void_p, c_void_p, c_void_p,
                               c_void_p, c_int, c_float, c_float, c_int, c_void_p]),

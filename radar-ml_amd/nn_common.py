@@ -589,6 +589,105 @@ def conv3s2(x_padded, w_half):
     return _conv3s2_function().apply(x, w)
 
 
+CONVT4S2_FORWARD, CONVT4S2_DGRAD, CONVT4S2_WGRAD = 0, 1, 2
+
+
+def convt4s2_wgrad_plan(pixels):
+    """``(pieces, pixels per piece)`` of the weight gradient of csrc/convt_train.hip (its ``wgrad_plan``): a function of the number of
+    input pixels N * H * W alone."""
+    pixels = int(pixels)
+    n = min(max(-(-pixels // 128), 1), 64)
+    ln = max(-(-(-(-pixels // n)) // 64) * 64, 64)
+    return (-(-pixels // ln) if pixels > 0 else 1), ln
+
+
+def convt4s2_wgrad_chain(pixels):
+    """Longest float32 summation chain behind an element of the weight gradient: the pixels of one piece (the matrix cores add them
+    one after the other) + the partial sums ``k_convt_wreduce`` adds (one per piece)."""
+    pieces, ln = convt4s2_wgrad_plan(pixels)
+    return ln + pieces
+
+
+def _convt4s2_function():
+    """torch.autograd.Function around csrc/convt_train.hip: the 4x4 stride-2 'same' transposed convolution of a channels_last half
+    tensor, its data gradient and its weight gradient, each one call into the library on the current stream."""
+    torch = _torch()
+    if getattr(_convt4s2_function, "_cls", None) is not None:
+        return _convt4s2_function._cls
+    from . import _lib
+
+    def run(name, which, a, b, out, dtype, n, h, w, cin, cout):
+        lib = _lib.load()
+        dev = out.device
+        with torch.cuda.device(dev):
+            hctx = _lib.context(dev)
+            nbytes = int(lib.rml_convt4s2_workspace_bytes(hctx, n, h, w, cin, cout, which))
+            ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+            _lib.check(getattr(lib, name)(hctx, _lib.ptr(a), _lib.ptr(b), 1 if dtype == torch.bfloat16 else 0, n, h, w, cin, cout,
+                                          _lib.ptr(out), _lib.ptr(ws), nbytes, _lib.stream_ptr(dev)), name)
+
+    class ConvT4S2(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, x, w):
+            n, cin, h, wd = x.shape
+            cout = w.shape[1]
+            z = torch.empty((n, cout, 2 * h, 2 * wd), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
+            if n:
+                run("rml_convt4s2_forward", CONVT4S2_FORWARD, x, w, z, x.dtype, n, h, wd, cin, cout)
+            ctx.save_for_backward(x, w)
+            return z
+
+        @staticmethod
+        def backward(ctx, dz):
+            x, w = ctx.saved_tensors
+            n, cin, h, wd = x.shape
+            cout = w.shape[1]
+            if dz.dtype != x.dtype or not dz.is_contiguous(memory_format=torch.channels_last):
+                dz = dz.to(x.dtype).contiguous(memory_format=torch.channels_last)
+            dx = dw = None
+            if ctx.needs_input_grad[0]:
+                dx = torch.empty_like(x, memory_format=torch.channels_last)
+                if n:
+                    run("rml_convt4s2_dgrad", CONVT4S2_DGRAD, dz, w, dx, x.dtype, n, h, wd, cin, cout)
+            if ctx.needs_input_grad[1]:
+                if n:
+                    dw = torch.empty_like(w, memory_format=torch.channels_last)
+                    run("rml_convt4s2_wgrad", CONVT4S2_WGRAD, x, dz, dw, x.dtype, n, h, wd, cin, cout)
+                else:
+                    dw = torch.zeros_like(w, memory_format=torch.channels_last)
+            return dx, dw
+
+    _convt4s2_function._cls = ConvT4S2
+    return ConvT4S2
+
+
+def convt4s2_supported(x, w_half):
+    """True when :func:`convt4s2` runs csrc/convt_train.hip on these tensors: CUDA, float16 or bfloat16 (both alike), a (Cin, Cout, 4, 4)
+    ConvTranspose2d kernel on an (N, Cin, H, W) input of a shape ``rml_convt4s2_supported`` takes (128 -> 128 channels, H and W
+    multiples of 8 in [8, 128])."""
+    torch = _torch()
+    if not (x.is_cuda and w_half.is_cuda and x.dtype in (torch.float16, torch.bfloat16) and w_half.dtype == x.dtype
+            and x.dim() == 4 and w_half.dim() == 4 and tuple(w_half.shape[2:]) == (4, 4) and w_half.shape[0] == x.shape[1]):
+        return False
+    from . import _lib
+    return bool(_lib.load().rml_convt4s2_supported(int(w_half.shape[0]), int(w_half.shape[1]), int(x.shape[2]), int(x.shape[3])))
+
+
+def convt4s2(x, w_half):
+    """``F.conv_transpose2d(x, w_half, None, stride=2, padding=1)`` with a 4x4 kernel -- Keras' Conv2DTranspose(4x4, strides 2, 'same')
+    without its bias -- on the project's own matrix-core kernels (csrc/convt_train.hip), forward and both gradients: no convolution
+    library, no zeroed workspace, the same bits on every call, and a backward that computes only the gradients autograd asks for.
+    Anything the kernels do not take (:func:`convt4s2_supported`: CPU tensors, float32, other channel counts or plane sizes) IS
+    ``F.conv_transpose2d``, bit for bit."""
+    torch = _torch()
+    if not convt4s2_supported(x, w_half):
+        import torch.nn.functional as F
+        return F.conv_transpose2d(x, w_half, None, stride=2, padding=1)
+    x = x if x.is_contiguous(memory_format=torch.channels_last) else x.contiguous(memory_format=torch.channels_last)
+    w = w_half if w_half.is_contiguous(memory_format=torch.channels_last) else w_half.contiguous(memory_format=torch.channels_last)
+    return _convt4s2_function().apply(x, w)
+
+
 def _conv7_tanh_function():
     """torch.autograd.Function around csrc/gen.hip: the generator's Conv2D(1, 7x7, 'same', tanh) output layer."""
     torch = _torch()

@@ -16,7 +16,8 @@ The generator side of the loop (sgan.py:57-122, 220-235, 439-543) is here too: :
 (``gan_model.train_on_batch``: the generator and -- the reference's quirk -- the discriminator's BatchNorm gammas and betas are
 trained, every other discriminator weight is frozen for that step only), ``generate_fake_samples``, the
 ``generated_data_*.pickle`` product (``generated_samples`` / ``save_generated``) and the four-update loop :func:`train`.  On
-the GPU under half-precision autocast the transposed convolutions run through the library, BatchNorm + ReLU is the fused op of the
+the GPU under half-precision autocast the transposed convolutions run through the library -- or, with ``convolutions="hip"``
+(``Generator.conv_impl``), on csrc/convt_train.hip with both of their gradients (nn_common.convt4s2) --, BatchNorm + ReLU is the fused op of the
 discriminator (slope 0) and the 7x7 one-channel output layer is csrc/gen.hip (nn_common.conv7_tanh).  In inference mode
 (``g_model.predict``: the fake samples of every step, the data product) the whole generator can run on csrc/gen_infer.hip --
 ``Generator.forward_fused``, ``predict(fused=True)``, :func:`generate_dataset`: the BatchNorm layers folded into the transposed
@@ -779,6 +780,9 @@ class Generator(_nn().Module):
             br.out = nn.Conv2d(self.channels, 1, 7, padding=3)
             self.branches.append(br)
         self._packs = {}                            # name -> (key of the tensors it was made from, value): generator_packs
+        # the transposed convolutions in training mode: "library" (F.conv_transpose2d, i.e. MIOpen) or "hip" (nn_common.convt4s2:
+        # csrc/convt_train.hip, forward and both gradients; reproducible bit for bit).  Inference and forward_fused never read it
+        self.conv_impl = "library"
         for mod in self.modules():
             if isinstance(mod, (nn.Conv2d, nn.ConvTranspose2d, nn.Linear)):
                 nn.init.normal_(mod.weight, 0.0, 0.02)      # RandomNormal(stddev=0.02), sgan.py:60
@@ -787,7 +791,7 @@ class Generator(_nn().Module):
     def _branch(self, z, br, adt):
         import torch
         import torch.nn.functional as F
-        from .nn_common import bn_lrelu_pad, conv7_tanh, conv7_tanh_fused
+        from .nn_common import bn_lrelu_pad, conv7_tanh, conv7_tanh_fused, convt4s2
         n = z.shape[0]
         h = F.relu(br.dense(z)).reshape(n, self.base, self.base, self.channels).permute(0, 3, 1, 2)      # NHWC storage, no copy
         fused = _FUSED_LAYERS and z.is_cuda and self.training and adt in (torch.float16, torch.bfloat16)
@@ -795,7 +799,11 @@ class Generator(_nn().Module):
             if not self.training:
                 h = F.relu(bn(up(h)))
                 continue
-            zt = F.conv_transpose2d(h, up.weight, None, stride=2, padding=1)
+            if getattr(self, "conv_impl", "library") == "hip":      # a model pickled before the attribute existed: the library
+                # the float32 master weight gets its gradient through the cast to the activations' (autocast) type
+                zt = convt4s2(h, up.weight.to(h.dtype))
+            else:
+                zt = F.conv_transpose2d(h, up.weight, None, stride=2, padding=1)
             if fused:
                 h = bn_lrelu_pad(zt, bn, slope=0.0, pad=0, conv_bias=up.bias)
             else:
@@ -963,12 +971,17 @@ class Generator(_nn().Module):
         return self
 
 
-def define_generator(latent_dim=100, device=None):
-    """Counterpart of sgan.define_generator (sgan.py:90-122): the model on the device, channels_last."""
+def define_generator(latent_dim=100, device=None, convolutions="library"):
+    """Counterpart of sgan.define_generator (sgan.py:90-122): the model on the device, channels_last.  ``convolutions``: the model's
+    ``conv_impl`` ("library" or "hip", see :class:`GanTrainer`)."""
     import torch
+    if convolutions not in ("library", "hip"):
+        raise ValueError("convolutions must be 'library' or 'hip', got %r" % (convolutions,))
     dev = torch.device(device) if device is not None else (
         torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu"))
-    return Generator(latent_dim=latent_dim).to(dev).to(memory_format=torch.channels_last)
+    model = Generator(latent_dim=latent_dim).to(dev).to(memory_format=torch.channels_last)
+    model.conv_impl = convolutions
+    return model
 
 
 def fold_generator(model):
@@ -1030,10 +1043,18 @@ class GanTrainer:
     trained parameters only: the weight-gradient convolutions are skipped) and nothing is frozen afterwards.  The loss scale is the
     discriminator trainer's.  ``.grad`` is never touched, so a trainer with captured heads keeps its gradient tensors."""
 
-    def __init__(self, generator, disc_trainer, lr=2e-4, beta1=0.5):
+    def __init__(self, generator, disc_trainer, lr=2e-4, beta1=0.5, convolutions=None):
+        """``convolutions``: None (default) leaves ``generator.conv_impl`` as it is; "library" runs the generator's transposed
+        convolutions in training mode through ``F.conv_transpose2d``; "hip" runs them and their gradients on csrc/convt_train.hip
+        (nn_common.convt4s2): no convolution library, no workspace zeroing, every gradient the same bits on every call.  With a
+        discriminator trainer that also uses ``convolutions="hip"`` the g update then runs no library convolution at all."""
         import torch
         import torch.distributed as dist
         nn = _nn()
+        if convolutions not in (None, "library", "hip"):
+            raise ValueError("convolutions must be None, 'library' or 'hip', got %r" % (convolutions,))
+        if convolutions is not None:
+            generator.conv_impl = convolutions
         if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
             raise NotImplementedError("GanTrainer: data parallelism of the generator step is not implemented")
         self.generator, self.disc_trainer, self.disc = generator, disc_trainer, disc_trainer.model
