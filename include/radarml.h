@@ -772,6 +772,32 @@ int rml_dense_tail_lrelu(rml_ctx* ctx, const uint16_t* feat, int64_t ld_feat, in
                          const float* w2t, const float* b2, const float* w3, const float* b3, int n_classes, float slope,
                          float* workspace, int64_t workspace_bytes, float* proba, void* stream);
 
+/* The same trunk at float32-class accuracy (csrc/sgan_x3.hip) -- c_model.predict is float32 Keras (sgan.py:132-199): the arithmetic of
+ * rml_dnn_trunk_x3 on the layers of rml_sgan_trunk.  Every operand is carried as `parts` bf16 numbers and every product as the
+ * matrix-core products of the part pairs (i, j) with i + j < parts, the smallest terms first, float32 accumulation: parts = 2 ("x3",
+ * ~2^-16 relative per product) or 3 ("x6", ~2^-24); anything else RML_ERR_INVALID.  Planes float32; folded weights float32 with k =
+ * (ky*3+kx)*Cin + cin: w1 [3][128][9], b1 [3][128], w2 [3][64][1152], b2 [3][64], w3 [3][32][576], b3 [3][32] (NOT rounded to bf16);
+ * feat[b][(h*(W/8)+w)*96 + branch*32 + n] float32.  conv1's bias rides in three bf16 K slots, the other biases start the float32
+ * accumulators (all exact); LeakyReLU(slope), 0 <= slope <= 1, in float32; the layer-2 activation goes through the workspace as
+ * float32.  No atomics, one owner and one order per sum: a sample's features are the same bits alone, at any position of any batch,
+ * and on a second call.  The second opinion of the margin guard (radar-ml_amd/sgan.py), not the fast path.
+ * rml_sgan_trunk_x3_supported (HOST, no device; sgan.py:132-199 at 128 x 128 does): H and W multiples of 8, at most 4096; anything
+ * else: 0, and rml_sgan_trunk_x3 returns RML_ERR_UNSUPPORTED without a launch.
+ * workspace: rml_sgan_trunk_x3_workspace_bytes(B, H, W) bytes (the layers of sgan.py:132-199 in operand order for either part count
+ * + the layer-2 activation; 0 for unsupported planes; non-decreasing in B), 16-byte aligned, as are the planes, w2, b2, w3, b3 and
+ * feat; a shorter one: RML_ERR_INVALID.  B = 0: nothing is launched. */
+int rml_sgan_trunk_x3_supported(int H, int W);
+int64_t rml_sgan_trunk_x3_workspace_bytes(int64_t B, int H, int W);
+int rml_sgan_trunk_x3(rml_ctx* ctx, const float* xz, const float* yz, const float* xy, int64_t B, int H, int W, const float* w1,
+                      const float* b1, const float* w2, const float* b2, const float* w3, const float* b3, float slope, int parts,
+                      float* feat, void* workspace, int64_t workspace_bytes, void* stream);
+/* rml_dnn_dense_tail_f32 with LeakyReLU(slope) behind the two hidden layers (sgan.py:187-199 on the float32 rows of
+ * rml_sgan_trunk_x3; the BatchNorm1d layers folded into w1 / b1 and w2t / b2 on the host): the same fixed K splits, the same
+ * workspace size (rml_dnn_dense_tail_f32_workspace_bytes), a row's result depends on that row alone. */
+int rml_dense_tail_lrelu_f32(rml_ctx* ctx, const float* feat, int64_t ld_feat, int64_t N, int64_t K, const float* w1, const float* b1,
+                             const float* w2t, const float* b2, const float* w3, const float* b3, int n_classes, float slope,
+                             float* workspace, int64_t workspace_bytes, float* proba, void* stream);
+
 /* ---- dnn.py training step (dnn.py:347-390: model.fit on the model of dnn.py:45-91), float32 -----------------------------------
  * One step on the batch rows[0..B) of RESIDENT data: three float32 plane sets xz / yz / xy, [N][H][W] each, already scaled to
  * [-1, 1] and resized (H, W multiples of 4, W <= 128: rml_dnn_train_supported; others RML_ERR_UNSUPPORTED), labels [N] int32 in

@@ -130,7 +130,13 @@ SIGNATURES = {
                                c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_int64, c_void_p]),
     "rml_dense_tail_lrelu": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                      c_void_p, c_int, c_float, c_void_p, c_int64, c_void_p, c_void_p]),
-    "rml_dnn_train_supported": (c_int, [c_int, c_int, c_int]),
+    "rml_sgan_trunk_x3_supported": (c_int, [c_int, c_int]),
+    "rml_sgan_trunk_x3_workspace_bytes": (c_int64, [c_int64, c_int, c_int]),
+    "rml_sgan_trunk_x3": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                  c_void_p, c_void_p, c_float, c_int, c_void_p, c_void_p, c_int64, c_void_p]),
+    "rml_dense_tail_lrelu_f32": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                         c_void_p, c_int, c_float, c_void_p, c_int64, c_void_p, c_void_p]),
+    "rml_dnn_train_supported":(c_int, [c_int, c_int, c_int]),
     "rml_dnn_train_workspace_bytes": (c_int64, [c_int, c_int, c_int, c_int]),
     "rml_dnn_train_step": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_void_p, c_int,
                                    c_void_p, c_void_p, c_int, c_uint64, c_int64, c_float, c_int, c_void_p, c_int64, c_void_p, c_void_p,

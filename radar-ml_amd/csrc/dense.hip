@@ -459,19 +459,21 @@ extern "C" int64_t rml_dnn_dense_tail_f32_workspace_bytes(int64_t N, int64_t K) 
     return ((K + kF32Split - 1) / kF32Split) * N * kHidden * (int64_t)sizeof(float);
 }
 
-extern "C" int rml_dnn_dense_tail_f32(rml_ctx* ctx, const float* feat, int64_t ld_feat, int64_t N, int64_t K, const float* w1, const float* b1,
-                                      const float* w2t, const float* b2, const float* w3, const float* b3, int n_classes, float* workspace,
-                                      int64_t workspace_bytes, float* proba, void* stream) {
-    RML_REQUIRE(ctx && N >= 0 && K > 0, RML_ERR_INVALID, "rml_dnn_dense_tail_f32: bad arguments");
+// the float32 tail with either activation: k_fc1_f32 is shared, the finishing kernel is instantiated per activation (the relu
+// instance, and with it every bit of rml_dnn_dense_tail_f32, is the one the bf16 tail uses)
+static int dense_tail_f32(const char* who, rml_ctx* ctx, const float* feat, int64_t ld_feat, int64_t N, int64_t K, const float* w1, const float* b1,
+                          const float* w2t, const float* b2, const float* w3, const float* b3, int n_classes, bool lrelu, float slope,
+                          float* workspace, int64_t workspace_bytes, float* proba, void* stream) {
+    RML_REQUIRE(ctx && N >= 0 && K > 0, RML_ERR_INVALID, "%s: bad arguments", who);
     RML_REQUIRE(K % 4 == 0 && ld_feat >= K && ld_feat % 4 == 0, RML_ERR_UNSUPPORTED,
-                "rml_dnn_dense_tail_f32: K = %lld and ld_feat must be multiples of 4", (long long)K);
-    RML_REQUIRE(n_classes >= 1 && n_classes <= 16, RML_ERR_UNSUPPORTED, "rml_dnn_dense_tail_f32: 1..16 classes");
+                "%s: K = %lld and ld_feat must be multiples of 4", who, (long long)K);
+    RML_REQUIRE(n_classes >= 1 && n_classes <= 16, RML_ERR_UNSUPPORTED, "%s: 1..16 classes", who);
     if (N == 0) return RML_OK;
-    RML_REQUIRE(feat && w1 && b1 && w2t && b2 && w3 && b3 && workspace && proba, RML_ERR_INVALID, "rml_dnn_dense_tail_f32: NULL argument");
+    RML_REQUIRE(feat && w1 && b1 && w2t && b2 && w3 && b3 && workspace && proba, RML_ERR_INVALID, "%s: NULL argument", who);
     RML_REQUIRE(((reinterpret_cast<uintptr_t>(feat) | reinterpret_cast<uintptr_t>(w1) | reinterpret_cast<uintptr_t>(workspace)) & 15) == 0,
-                RML_ERR_INVALID, "rml_dnn_dense_tail_f32: feat, w1 and the workspace need 16-byte alignment");
-    RML_REQUIRE(N < (int64_t)1 << 31 && K < (int64_t)1 << 30, RML_ERR_UNSUPPORTED, "rml_dnn_dense_tail_f32: too large");
-    RML_REQUIRE(workspace_bytes >= rml_dnn_dense_tail_f32_workspace_bytes(N, K), RML_ERR_INVALID, "rml_dnn_dense_tail_f32: workspace too small");
+                RML_ERR_INVALID, "%s: feat, w1 and the workspace need 16-byte alignment", who);
+    RML_REQUIRE(N < (int64_t)1 << 31 && K < (int64_t)1 << 30, RML_ERR_UNSUPPORTED, "%s: too large", who);
+    RML_REQUIRE(workspace_bytes >= rml_dnn_dense_tail_f32_workspace_bytes(N, K), RML_ERR_INVALID, "%s: workspace too small", who);
     RML_HIP(hipSetDevice(ctx->device));
     hipStream_t st = static_cast<hipStream_t>(stream);
     Fc1F32Args fa{};
@@ -480,13 +482,28 @@ extern "C" int rml_dnn_dense_tail_f32(rml_ctx* ctx, const float* feat, int64_t l
     fa.partial = workspace;
     const bool two = N >= 4096;                             // (the choice changes no bit of the result: see k_fc1_f32)
     const int64_t tiles = two ? (N + 255) / 256 : (N + 127) / 128;
-    RML_REQUIRE(tiles * fa.S < (int64_t)1 << 31, RML_ERR_UNSUPPORTED, "rml_dnn_dense_tail_f32: too large");
+    RML_REQUIRE(tiles * fa.S < (int64_t)1 << 31, RML_ERR_UNSUPPORTED, "%s: too large", who);
     if (two) hipLaunchKernelGGL(k_fc1_f32<2>, dim3((unsigned)(tiles * fa.S)), dim3(256), 0, st, fa);
     else hipLaunchKernelGGL(k_fc1_f32<1>, dim3((unsigned)(tiles * fa.S)), dim3(256), 0, st, fa);
     FinishArgs fi{};
     fi.partial = workspace; fi.S = fa.S; fi.N = N; fi.b1 = b1; fi.w2t = w2t; fi.b2 = b2; fi.w3 = w3; fi.b3 = b3; fi.C = n_classes; fi.out = proba;
+    fi.slope = slope;
     const int64_t blocks = (N + 3) / 4;
-    hipLaunchKernelGGL(k_dense_finish<false>, dim3((unsigned)(blocks < 2 * ctx->num_cu ? blocks : 2 * ctx->num_cu)), dim3(256), 0, st, fi);
+    const dim3 grid((unsigned)(blocks < 2 * ctx->num_cu ? blocks : 2 * ctx->num_cu));
+    if (lrelu) hipLaunchKernelGGL(k_dense_finish<true>, grid, dim3(256), 0, st, fi);
+    else hipLaunchKernelGGL(k_dense_finish<false>, grid, dim3(256), 0, st, fi);
     RML_HIP(hipGetLastError());
     return RML_OK;
+}
+
+extern "C" int rml_dnn_dense_tail_f32(rml_ctx* ctx, const float* feat, int64_t ld_feat, int64_t N, int64_t K, const float* w1, const float* b1,
+                                      const float* w2t, const float* b2, const float* w3, const float* b3, int n_classes, float* workspace,
+                                      int64_t workspace_bytes, float* proba, void* stream) {
+    return dense_tail_f32("rml_dnn_dense_tail_f32", ctx, feat, ld_feat, N, K, w1, b1, w2t, b2, w3, b3, n_classes, false, 0.0f, workspace, workspace_bytes, proba, stream);
+}
+
+extern "C" int rml_dense_tail_lrelu_f32(rml_ctx* ctx, const float* feat, int64_t ld_feat, int64_t N, int64_t K, const float* w1, const float* b1,
+                                        const float* w2t, const float* b2, const float* w3, const float* b3, int n_classes, float slope,
+                                        float* workspace, int64_t workspace_bytes, float* proba, void* stream) {
+    return dense_tail_f32("rml_dense_tail_lrelu_f32", ctx, feat, ld_feat, N, K, w1, b1, w2t, b2, w3, b3, n_classes, true, slope, workspace, workspace_bytes, proba, stream);
 }

@@ -14,6 +14,7 @@ import numpy as np
 from . import dnn_guard
 from . import prep
 from .dnn_guard import LABEL_GUARD, LABEL_GUARD_X3, LABEL_GUARD_X6, LABEL_GUARD_F32      # noqa: F401  (the margin guard's levels)
+from .dnn_guard import rescore_route      # noqa: F401  (lives with the re-scoring passes both classifiers share; importable here as before)
 from .nn_common import make_same_conv, to_nchw, flatten_nhwc, tf_same_pad
 
 RESCALE = (80, 80)          # dnn.py:33
@@ -22,17 +23,6 @@ rng = np.random.default_rng(prep.RANDOM_SEED)       # dnn.py:30: the noise draws
 
 def _rng(given):
     return given if given is not None else rng
-
-
-def rescore_route(n_rows, N, fused, host):
-    """Which pass of ``Classifier.rescore_exact`` scores ``n_rows`` (None: all) of ``N`` frames.  ``fused``: precision, mode, planes
-    and volumes fit rml_dnn_exact_features; ``host``: host volumes.  Sparse: fewer than half of the frames are wanted."""
-    sparse = n_rows is not None and 2 * n_rows < N
-    if sparse and fused and not host:
-        return "fused_gather"       # one library call per pass: gather, projection, resize, trunk
-    if n_rows is None:
-        return "all"
-    return "gather" if sparse else "dense_blocks"
 
 
 class History:
@@ -287,7 +277,7 @@ def _module_base():
     return nn.Module
 
 
-class Classifier(_module_base()):
+class Classifier(dnn_guard.ExactRescore, _module_base()):
     def __init__(self, shapes, n_classes):
         import torch
         import torch.nn as nn
@@ -879,12 +869,6 @@ class Classifier(_module_base()):
                                                   _lib.ptr(feat), _lib.stream_ptr(dev)), "rml_dnn_exact_features")
         return feat
 
-    # frames per pass of rescore_exact: the gathered volumes, their float rows, three float32 planes and 150 KB of float32 features each
-    RESCORE_BYTES = 2 << 30
-    # frames per block of its dense route (nothing is gathered there: a pass is bounded by its intermediates -- 270 KB per frame --
-    # not by RESCORE_BYTES of volumes)
-    RESCORE_BLOCK = 16384
-
     def rescore_exact(self, volumes, rescale=(80, 80), mode="max", precision="float64", rows=None, ijk=None):
         """(n,X,Y,Z) volumes -> (n, n_classes) probabilities through the reference's chain without a rounding the reference does
         not have: projection (exact), (p - 127.5) / 127.5 and Pillow's bicubic resize in float64 rounded to float32 planes as
@@ -897,97 +881,16 @@ class Classifier(_module_base()):
 
         ``mode="slice"``: ``ijk`` (n,3) or (n,T,3) -- the result has n*T rows, frame-major, and ``rows`` indexes THOSE: row r is scored
         from frame r // T at ijk[r] (``nn_common.slice_row_targets``), through ``process_volumes(mode="slice", ijk=...)`` (exact), the
-        Pillow-exact resize and :meth:`forward_exact`."""
+        Pillow-exact resize and :meth:`forward_exact`.  The passes themselves: dnn_guard.ExactRescore."""
+        return self._rescore(volumes, rescale, mode, precision, rows, ijk)
+
+    def _one_call_route(self, volumes, rescale, mode, precision):
         import torch
-        from . import common, nn_common
-        N = int(volumes.shape[0])
-        dims = tuple(int(v) for v in volumes.shape[1:])
-        step = max(64, min(16384, self.RESCORE_BYTES // max(1, dims[0] * dims[1] * dims[2] * volumes.element_size())))
-        host = not volumes.is_cuda
-        dev = next(self.parameters()).device
-        if mode == "slice":
-            return self._rescore_slices(volumes, rescale, precision, rows, ijk, step)
+        return (precision in ("x3", "x6") and volumes.is_cuda and mode != "slice" and self.x3_supported(int(rescale[1]), int(rescale[0]))
+                and volumes.dtype in (torch.float32, torch.uint8) and volumes.is_contiguous())
 
-        def score(v, pick=None):
-            if host:
-                v = v.to(dev)
-            feat = common.process_volumes(v, mode=mode, scale=False)
-            if pick is not None:
-                feat = feat[pick]
-            xs = nn_common.preprocess_features(feat, dims, rescale, out_dtype="float32")
-            return self.forward_exact(*xs, precision=precision)
-
-        with torch.no_grad():
-            fused = (precision in ("x3", "x6") and not host and mode != "slice" and self.x3_supported(int(rescale[1]), int(rescale[0]))
-                     and volumes.dtype in (torch.float32, torch.uint8) and volumes.is_contiguous())
-            route = rescore_route(None if rows is None else int(rows.numel()), N, fused, host)
-            if route == "dense_blocks":
-                return self._rescore_dense_blocks(volumes, rows, score)
-            if route == "fused_gather":
-                outs = [self._tail_float32(self.exact_features(volumes, rows[s:s + step], rescale, mode, 3 if precision == "x6" else 2))
-                        for s in range(0, int(rows.numel()), step)]
-            elif route == "all":
-                outs = [score(volumes[s:s + step]) for s in range(0, N, step)]
-            else:
-                outs = self._rescore_gather(volumes, rows, step, score)
-        return torch.cat(outs) if len(outs) != 1 else outs[0]
-
-    def _rescore_slices(self, volumes, rescale, precision, rows, ijk, step):
-        """:meth:`rescore_exact` on target slices.  All rows: blocks of frames with their (T,3) indices, no volume duplicated; an index
-        tensor: the frames of ``step`` rows gathered (a frame once per wanted target of it: the guard asks for a handful of rows)."""
-        import torch
-        from . import common, nn_common
-        if ijk is None:
-            raise ValueError("rescore_exact: mode='slice' needs ijk")
-        N = int(volumes.shape[0])
-        dims = tuple(int(v) for v in volumes.shape[1:])
-        host = not volumes.is_cuda
-        dev = next(self.parameters()).device
-        ijk, T = nn_common.slice_targets_arg(ijk, N)
-        ijk = ijk.reshape(N, T, 3)
-        if rows is not None and 2 * int(rows.numel()) >= N * T:
-            # at least half of the rows are wanted (a model without margins): every row by blocks of frames, no gather, and pick
-            return self._rescore_slices(volumes, rescale, precision, None, ijk, step)[rows.to(dev)]
-
-        def score(v, idx):
-            feat = common.process_volumes(v.to(dev) if host else v, mode="slice", ijk=idx, scale=False)
-            xs = nn_common.preprocess_features(feat, dims, rescale, out_dtype="float32")
-            return self.forward_exact(*xs, precision=precision)
-
-        with torch.no_grad():
-            if rows is None:
-                fstep = max(1, step // T)
-                outs = [score(volumes[s:s + fstep], ijk[s:s + fstep]) for s in range(0, N, fstep)]
-            else:
-                flat = ijk.reshape(N * T, 3)
-                outs = []
-                for s in range(0, int(rows.numel()), step):
-                    r = rows[s:s + step]
-                    frames, _ = nn_common.slice_row_targets(r, T)
-                    outs.append(score(volumes[frames.cpu() if host else frames.to(volumes.device)], flat[r.to(flat.device)]))
-            if not outs:
-                return torch.zeros((0, self.n_classes), dtype=torch.float64 if precision == "float64" else torch.float32, device=dev)
-        return torch.cat(outs) if len(outs) != 1 else outs[0]
-
-    @staticmethod
-    def _rescore_gather(volumes, rows, step, score):
-        """the sparse route for host volumes and for what the library call does not take: gather ``step`` frames, score them"""
-        host = not volumes.is_cuda
-        return [score(volumes[rows[s:s + step].cpu() if host else rows[s:s + step]]) for s in range(0, int(rows.numel()), step)]
-
-    def _rescore_dense_blocks(self, volumes, rows, score):
-        """the dense route: every block of RESCORE_BLOCK contiguous frames that holds a wanted frame is projected whole, the wanted
-        feature rows picked (in ascending order) and their probabilities put back in the order of ``rows``"""
-        import torch
-        N, blk, dev = int(volumes.shape[0]), self.RESCORE_BLOCK, next(self.parameters()).device
-        srt, order = torch.sort(rows)
-        cuts = torch.searchsorted(srt, torch.arange(0, N + blk, blk, device=srt.device, dtype=srt.dtype)).cpu().tolist()
-        outs = [score(volumes[s:s + blk], (srt[cuts[i]:cuts[i + 1]] - s).to(dev))
-                for i, s in enumerate(range(0, N, blk)) if cuts[i + 1] > cuts[i]]
-        got = torch.cat(outs)
-        res = torch.empty_like(got)
-        res[order.to(dev)] = got
-        return res
+    def _one_call(self, volumes, rows, rescale, mode, precision):
+        return self._tail_float32(self.exact_features(volumes, rows, rescale, mode, 3 if precision == "x6" else 2))
 
     # ---- training (dnn.py:89-90, 347-390) ------------------------------------------------------------------------
     def compile(self, lr=0.0002, beta_1=0.5, beta_2=0.999, epsilon=1e-7, seed=0):

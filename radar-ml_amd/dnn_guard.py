@@ -1,9 +1,11 @@
-"""The margin guard of the CNN row (dnn.py ``Classifier._guard``): float64 labels from a bf16 chain.
+"""The margin guard of the CNN row (dnn.py ``Classifier._guard``) and of the SGAN classifier (sgan.py ``Discriminator._guard``, with its own
+stage thresholds): float64 labels from a bf16 chain.
 
 Rows of a probability table whose top-2 gap is too small for a bf16 chain are replaced by what exact-input arithmetic gives.  The
 POLICY (:class:`MarginGuard`: which rows, how often, through which precision) is plain Python on tensors of any device; the DEVICE
 OPERATIONS it needs -- the gaps, the candidate pick, one round's bookkeeping -- sit behind :class:`GuardOps`, whose CUDA form
-(:class:`CudaOps`) is two kernels of csrc/guard.hip.
+(:class:`CudaOps`) is two kernels of csrc/guard.hip.  :class:`ExactRescore` holds the passes of ``rescore_exact`` -- volumes to exact planes to the
+model's ``forward_exact`` -- that both models share.
 
 ``last_guard`` (``MarginGuard.last``, ``Classifier.last_guard``) after a call -- the one list of its keys:
   rows               rows of the table
@@ -74,6 +76,127 @@ def run_padded(fn, idx, size):
     return torch.cat(outs)
 
 
+def rescore_route(n_rows, N, fused, host):
+    """Which pass of ``rescore_exact`` scores ``n_rows`` (None: all) of ``N`` frames.  ``fused``: precision, mode, planes
+    and volumes fit rml_dnn_exact_features; ``host``: host volumes.  Sparse: fewer than half of the frames are wanted."""
+    sparse = n_rows is not None and 2 * n_rows < N
+    if sparse and fused and not host:
+        return "fused_gather"       # one library call per pass: gather, projection, resize, trunk
+    if n_rows is None:
+        return "all"
+    return "gather" if sparse else "dense_blocks"
+
+
+class ExactRescore:
+    """The passes of ``rescore_exact`` that do not depend on the model (dnn.py ``Classifier``, sgan.py ``Discriminator``): volumes ->
+    exact projection (``common.process_volumes(scale=False)``) -> Pillow-bit-identical float32 planes
+    (``nn_common.preprocess_features``) -> the model's ``forward_exact(xz, yz, xy, precision=...)``, in bounded passes, by the route
+    :func:`rescore_route` picks.  The model brings ``forward_exact``, ``n_classes`` and ``parameters()``; one that can go from
+    volumes to probabilities in one library call per pass says so in ``_one_call_route`` and does it in ``_one_call``."""
+
+    # frames per pass of rescore_exact: the gathered volumes, their float rows, three float32 planes and the float32 features each
+    RESCORE_BYTES = 2 << 30
+    # frames per block of its dense route (nothing is gathered there: a pass is bounded by its intermediates -- 270 KB per frame
+    # at the CNN's 80 x 80 -- not by RESCORE_BYTES of volumes)
+    RESCORE_BLOCK = 16384
+
+    def _one_call_route(self, volumes, rescale, mode, precision):
+        return False
+
+    def _one_call(self, volumes, rows, rescale, mode, precision):
+        raise NotImplementedError
+
+    def _rescore(self, volumes, rescale, mode, precision, rows, ijk):
+        import torch
+        from . import common, nn_common
+        N = int(volumes.shape[0])
+        dims = tuple(int(v) for v in volumes.shape[1:])
+        step = max(64, min(16384, self.RESCORE_BYTES // max(1, dims[0] * dims[1] * dims[2] * volumes.element_size())))
+        host = not volumes.is_cuda
+        dev = next(self.parameters()).device
+        if mode == "slice":
+            return self._rescore_slices(volumes, rescale, precision, rows, ijk, step)
+
+        def score(v, pick=None):
+            if host:
+                v = v.to(dev)
+            feat = common.process_volumes(v, mode=mode, scale=False)
+            if pick is not None:
+                feat = feat[pick]
+            xs = nn_common.preprocess_features(feat, dims, rescale, out_dtype="float32")
+            return self.forward_exact(*xs, precision=precision)
+
+        with torch.no_grad():
+            fused = not host and bool(self._one_call_route(volumes, rescale, mode, precision))
+            route = rescore_route(None if rows is None else int(rows.numel()), N, fused, host)
+            if route == "dense_blocks":
+                return self._rescore_dense_blocks(volumes, rows, score)
+            if route == "fused_gather":
+                outs = [self._one_call(volumes, rows[s:s + step], rescale, mode, precision) for s in range(0, int(rows.numel()), step)]
+            elif route == "all":
+                outs = [score(volumes[s:s + step]) for s in range(0, N, step)]
+            else:
+                outs = self._rescore_gather(volumes, rows, step, score)
+        return torch.cat(outs) if len(outs) != 1 else outs[0]
+
+    def _rescore_slices(self, volumes, rescale, precision, rows, ijk, step):
+        """:meth:`_rescore` on target slices.  All rows: blocks of frames with their (T,3) indices, no volume duplicated; an index
+        tensor: the frames of ``step`` rows gathered (a frame once per wanted target of it: the guard asks for a handful of rows)."""
+        import torch
+        from . import common, nn_common
+        if ijk is None:
+            raise ValueError("rescore_exact: mode='slice' needs ijk")
+        N = int(volumes.shape[0])
+        dims = tuple(int(v) for v in volumes.shape[1:])
+        host = not volumes.is_cuda
+        dev = next(self.parameters()).device
+        ijk, T = nn_common.slice_targets_arg(ijk, N)
+        ijk = ijk.reshape(N, T, 3)
+        if rows is not None and 2 * int(rows.numel()) >= N * T:
+            # at least half of the rows are wanted (a model without margins): every row by blocks of frames, no gather, and pick
+            return self._rescore_slices(volumes, rescale, precision, None, ijk, step)[rows.to(dev)]
+
+        def score(v, idx):
+            feat = common.process_volumes(v.to(dev) if host else v, mode="slice", ijk=idx, scale=False)
+            xs = nn_common.preprocess_features(feat, dims, rescale, out_dtype="float32")
+            return self.forward_exact(*xs, precision=precision)
+
+        with torch.no_grad():
+            if rows is None:
+                fstep = max(1, step // T)
+                outs = [score(volumes[s:s + fstep], ijk[s:s + fstep]) for s in range(0, N, fstep)]
+            else:
+                flat = ijk.reshape(N * T, 3)
+                outs = []
+                for s in range(0, int(rows.numel()), step):
+                    r = rows[s:s + step]
+                    frames, _ = nn_common.slice_row_targets(r, T)
+                    outs.append(score(volumes[frames.cpu() if host else frames.to(volumes.device)], flat[r.to(flat.device)]))
+            if not outs:
+                return torch.zeros((0, self.n_classes), dtype=torch.float64 if precision == "float64" else torch.float32, device=dev)
+        return torch.cat(outs) if len(outs) != 1 else outs[0]
+
+    @staticmethod
+    def _rescore_gather(volumes, rows, step, score):
+        """the sparse route for host volumes and for what the library call does not take: gather ``step`` frames, score them"""
+        host = not volumes.is_cuda
+        return [score(volumes[rows[s:s + step].cpu() if host else rows[s:s + step]]) for s in range(0, int(rows.numel()), step)]
+
+    def _rescore_dense_blocks(self, volumes, rows, score):
+        """the dense route: every block of RESCORE_BLOCK contiguous frames that holds a wanted frame is projected whole, the wanted
+        feature rows picked (in ascending order) and their probabilities put back in the order of ``rows``"""
+        import torch
+        N, blk, dev = int(volumes.shape[0]), self.RESCORE_BLOCK, next(self.parameters()).device
+        srt, order = torch.sort(rows)
+        cuts = torch.searchsorted(srt, torch.arange(0, N + blk, blk, device=srt.device, dtype=srt.dtype)).cpu().tolist()
+        outs = [score(volumes[s:s + blk], (srt[cuts[i]:cuts[i + 1]] - s).to(dev))
+                for i, s in enumerate(range(0, N, blk)) if cuts[i + 1] > cuts[i]]
+        got = torch.cat(outs)
+        res = torch.empty_like(got)
+        res[order.to(dev)] = got
+        return res
+
+
 class GuardOps:
     """What the policy asks of the device.  ``gaps(proba)`` -> (N,) float32 top-2 gaps, 0 for a row with a non-finite value;
     ``apply(proba, rows, fresh, thr_close, gap)``: proba[rows] <- fresh, gap[rows] <- +inf when ``gap`` is given; returns (largest
@@ -138,8 +261,10 @@ class MarginGuard:
     is where the next call on the same weights starts (the same rows, the same bits when the call is repeated; one round instead
     of two in the steady state)."""
 
-    def __init__(self):
+    def __init__(self, stages=STAGES):
+        """``stages``: the cascade (:data:`STAGES` -- the CNN's thresholds; the SGAN classifier hands in its own)."""
         self.last = None
+        self.stages = tuple(stages)
         self._key, self._gap = None, 0.0
 
     def run(self, proba, eps, rescore, ops, params):
@@ -171,7 +296,7 @@ class MarginGuard:
         return proba
 
     def _cascade(self, proba, rows, rescore, ops, gap, rep):
-        for st in STAGES:
+        for st in self.stages:
             fresh = rescore(rows, st.precision).float().contiguous()
             err, still, close = ops.apply(proba, rows, fresh, st.close, gap if st.marks_gap else None)
             rep[st.count] += int(rows.numel())
@@ -197,7 +322,15 @@ class MarginGuard:
             idx = rows[pos:pos + FLOAT64_CHUNK]
             p64 = run_padded(lambda r: rescore(r, "float64"), idx, FLOAT64_CHUNK)
             e6 = max(e6, float((p6[pos:pos + FLOAT64_CHUNK].double() - p64.double()).abs().max()))
-            proba[idx] = p64.to(proba.dtype)
+            p32 = p64.to(proba.dtype)
+            tied = p32.argmax(dim=1) != p64.argmax(dim=1)
+            if bool(tied.any()):
+                # a float64 gap below the table's own resolution: rounding made the two largest equal (argmax would take the first).
+                # The float64 winner stays on top, by one unit in the last place
+                r = tied.nonzero().squeeze(1)
+                top = p32[r].max(dim=1).values
+                p32[r, p64[r].argmax(dim=1)] = torch.nextafter(top, torch.full_like(top, 2.0))
+            proba[idx] = p32
             pos += int(idx.numel())
             if pos < n and float(gs[pos]) >= max(8.0 * e6, 1e-6):
                 break

@@ -29,8 +29,9 @@ import pickle
 
 import numpy as np
 
+from . import dnn_guard
 from . import prep
-from .nn_common import make_same_conv, to_nchw, flatten_nhwc
+from .nn_common import make_same_conv, to_nchw, flatten_nhwc, tf_same_pad
 
 RESCALE = (128, 128)        # sgan.py:39
 rng = np.random.default_rng(prep.RANDOM_SEED)       # sgan.py:36: the noise draws and the shuffles of preprocess_data / balance_classes
@@ -40,6 +41,24 @@ YZ_SIZE = (176, 31)
 XY_SIZE = (31, 22)
 
 logger = logging.getLogger(__name__)
+
+# The margin guard of the classifier (Discriminator.predict_volumes(label_guard=...), forward_guarded; the policy: dnn_guard.py).
+# Rows whose top-2 probability gap is below LABEL_GUARD are scored again from exact inputs.  The fused bf16 chain moves a probability
+# by up to 8.16e-3 at 128 x 128 planes (the largest "|dp|" tests/test_sgan_infer_gpu.py prints there against the plain float32 layers,
+# re-read from one run on an MI355X: 1.0e-4, 6.39e-3 and, on the batch of 70, 8.16e-3), i.e. a gap by twice that:
+# 6 x the error, the CNN's factor, = 4.9e-2.  The guard widens
+# itself from what it sees, so this only sets where round one starts.
+LABEL_GUARD = 5e-2
+# Second level: the float32-class trunk (csrc/sgan_x3.hip, bf16 operand pairs) + the float32 LeakyReLU tail; rows whose gap there is
+# below this go on to "x6" (three parts per operand), and rows whose x6 gap is below LABEL_GUARD_X6 to float64.  Each level covers at
+# least four times the error measured for the stage in front of it (tests/test_sgan_guard_gpu.py asserts that over its case set).
+# Measured on an MI355X, one run: |x3 - float64| <= 1.66e-5 and |x6 - float64| <= 1.93e-6 over the case set; on the near-tie rows
+# the guard itself re-scored in those tests (2-class models, a last layer of gain 6) |x3 - x6| reached 2.4e-5 and |x6 - float64|
+# 3.7e-6 -- more than the CNN's 5e-5 / 1e-5 allow for, so both levels are wider here.  DESIGN.md 3.6c.
+LABEL_GUARD_X3 = 2e-4
+LABEL_GUARD_X6 = 2e-5
+GUARD_STAGES = (dnn_guard.Stage("x3", LABEL_GUARD_X3, True, "rescored", "observed_error"),
+                dnn_guard.Stage("x6", LABEL_GUARD_X6, False, "rescored_x6", "observed_error_x3"))
 
 # the fused HIP layers of both models (on by default wherever they apply); `plain_layers()` runs the plain PyTorch layers instead
 # -- the library's kernels under the same autocast -- for A/B timings and for the tests that measure one path against the other
@@ -65,7 +84,7 @@ def _nn():
     return nn
 
 
-class Discriminator(_nn().Module):
+class Discriminator(dnn_guard.ExactRescore, _nn().Module):
     def __init__(self, shapes=((128, 128, 1),) * 3, n_classes=3):
         nn = _nn()
         super().__init__()
@@ -94,6 +113,7 @@ class Discriminator(_nn().Module):
         # (nn_common.conv3s2: csrc/conv_train.hip, forward and both gradients; reproducible bit for bit)
         self.conv_impl = "library"
         self._packs = {}                            # name -> (key of the tensors it was made from, value): _cached
+        self._margin = dnn_guard.MarginGuard(stages=GUARD_STAGES)
         for mod in self.modules():
             if isinstance(mod, (nn.Conv2d, nn.Linear)):
                 nn.init.normal_(mod.weight, 0.0, 0.02)      # RandomNormal(stddev=0.02), sgan.py:176
@@ -247,8 +267,183 @@ class Discriminator(_nn().Module):
         with torch.no_grad():
             return self.dense_tail_fused(self.features_fused(xz, yz, xy))
 
+    # ---- exact-input arithmetic: what the margin guard re-scores with (csrc/sgan_x3.hip + the float32 LeakyReLU tail of csrc/dense.hip) --
+    def x3_supported(self, H, W):
+        """True when csrc/sgan_x3.hip takes (H, W) planes on this model: three one-channel branches of that size, H and W multiples of
+        8 (``rml_sgan_trunk_x3_supported``), the reference's 64 / 64 / n dense layers, n <= 16."""
+        from . import _lib
+        H, W = int(H), int(W)
+        return (len(self.branches) == 3 and all(tuple(sh) == (H, W, 1) for sh in self.shapes) and self.n_classes <= 16
+                and bool(_lib.load().rml_sgan_trunk_x3_supported(H, W)))
+
+    def features_x3(self, xz, yz, xy, parts=2):
+        """The flattened trunk output in float32 from the float32-class trunk (csrc/sgan_x3.hip): (N,H,W) or (N,1,H,W) CUDA float32
+        planes -> (N, (H/8)(W/8)*96) rows in Keras' Flatten order, the BatchNorm layers folded in (float64 fold, one cast to float32).
+        ``parts`` = 2: ~2^-16 relative per product (bf16 pairs, three matrix-core products each, "x3"); 3: ~2^-24 (bf16 triples, six
+        products, "x6").  A row depends on its own planes only.  Raises ValueError for planes the kernel does not take."""
+        import torch
+        from . import _lib
+        H, W = int(xz.shape[-2]), int(xz.shape[-1])
+        if not self.x3_supported(H, W):
+            raise ValueError("the float32-class SGAN trunk takes planes of the model's own size (%s) whose height and width are multiples "
+                             "of 8: got %dx%d planes" % ("x".join(str(v) for v in self.shapes[0][:2]), H, W))
+        if not xz.is_cuda:
+            raise RuntimeError("features_x3 runs on the GPU (there is no CPU path)")
+        lib = _lib.load()
+        xs = [x.reshape(x.shape[0], x.shape[-2], x.shape[-1]).float().contiguous() for x in (xz, yz, xy)]
+        if any(tuple(x.shape) != tuple(xs[0].shape) for x in xs):
+            raise ValueError("features_x3: three plane sets of one shape expected")
+        n, dev = int(xs[0].shape[0]), xs[0].device
+        pk = self.folded_packs()
+        feat = torch.empty((n, (H // 8) * (W // 8) * 96), dtype=torch.float32, device=dev)
+        if n == 0:
+            return feat
+        nbytes = int(lib.rml_sgan_trunk_x3_workspace_bytes(n, H, W))
+        ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(lib.rml_sgan_trunk_x3(_lib.context(dev), _lib.ptr(xs[0]), _lib.ptr(xs[1]), _lib.ptr(xs[2]), n, H, W,
+                                             _lib.ptr(pk["w1"]), _lib.ptr(pk["b1"]), _lib.ptr(pk["w2f"]), _lib.ptr(pk["b2"]),
+                                             _lib.ptr(pk["w3f"]), _lib.ptr(pk["b3"]), float(pk["slope"]), int(parts), _lib.ptr(feat),
+                                             _lib.ptr(ws), nbytes, _lib.stream_ptr(dev)), "rml_sgan_trunk_x3")
+        return feat
+
+    def _tail_float32(self, fv):
+        """Dense 64 + BatchNorm + LeakyReLU, twice, Dense n, softmax in float32 on float32 CUDA feature rows (inference: no dropout;
+        the BatchNorm1d layers folded in): csrc/dense.hip ``rml_dense_tail_lrelu_f32`` -- fixed K splits added in order, so a row
+        scored alone, inside any candidate set or twice has the same bits."""
+        import torch
+        from . import _lib
+        lib = _lib.load()
+        pk = self.folded_packs()
+        n, K, dev = int(fv.shape[0]), int(fv.shape[1]), fv.device
+        if not (fv.is_cuda and fv.dtype == torch.float32 and fv.ndim == 2 and fv.is_contiguous() and K % 4 == 0
+                and tuple(pk["fc1_wf"].shape) == (64, K) and tuple(pk["fc2_wt"].shape) == (64, 64) and self.n_classes <= 16):
+            raise ValueError("_tail_float32: contiguous CUDA float32 (N, %d) feature rows expected" % int(pk["fc1_wf"].shape[1]))
+        out = torch.empty((n, self.n_classes), dtype=torch.float32, device=dev)
+        if n == 0:
+            return out
+        nbytes = int(lib.rml_dnn_dense_tail_f32_workspace_bytes(n, K))
+        ws = torch.empty((nbytes // 4,), dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(lib.rml_dense_tail_lrelu_f32(_lib.context(dev), _lib.ptr(fv), K, n, K, _lib.ptr(pk["fc1_wf"]), _lib.ptr(pk["fc1_b"]),
+                                                    _lib.ptr(pk["fc2_wt"]), _lib.ptr(pk["fc2_b"]), _lib.ptr(pk["fc3_w"]), _lib.ptr(pk["fc3_b"]),
+                                                    self.n_classes, float(pk["slope"]), _lib.ptr(ws), nbytes, _lib.ptr(out),
+                                                    _lib.stream_ptr(dev)), "rml_dense_tail_lrelu_f32")
+        return out
+
+    def _eval_layers(self, xs):
+        """The plain PyTorch layers in inference mode whatever ``self.training`` says (BatchNorm on its moving statistics, no dropout):
+        (N,1,H,W) planes -> probabilities in the planes' dtype."""
+        import torch
+        import torch.nn.functional as F
+
+        def bn(x, m):
+            return F.batch_norm(x, m.running_mean, m.running_var, m.weight, m.bias, False, 0.0, m.eps)
+        outs = []
+        for x, br in zip(xs, self.branches):
+            layers = list(br)
+            for i in range(0, len(layers), 3):
+                x = F.leaky_relu(bn(layers[i](x), layers[i + 1]), layers[i + 2].negative_slope)
+            outs.append(x)
+        slope = self.act.negative_slope
+        h = F.leaky_relu(bn(self.fc1(flatten_nhwc(torch.cat(outs, dim=1))), self.bn1), slope)
+        h = F.leaky_relu(bn(self.fc2(h), self.bn2), slope)
+        return torch.softmax(self.fc3(h), dim=-1)
+
+    def _folded64(self):
+        """:func:`fold_batchnorm` of this model (float64), cached like the packs"""
+        return self._cached("folded64", list(self.parameters()) + list(self.buffers()), lambda: fold_batchnorm(self))
+
+    def features_float64(self, xz, yz, xy):
+        """The flattened trunk output of the :func:`fold_batchnorm` model in float64 on the inputs' device, (N, (H/8)(W/8)*96): each
+        convolution as im2col -- nine strided slices -- and a matrix product, as ``dnn.Classifier.forward_exact`` does it (MIOpen has
+        no float64 convolution)."""
+        import torch
+        import torch.nn.functional as F
+        f = self._folded64()
+        slope, dt = f["slope"], torch.float64
+        with torch.no_grad():
+            outs = []
+            for x, convs in zip((xz, yz, xy), f["conv"]):
+                x = x.reshape(x.shape[0], 1, x.shape[-2], x.shape[-1]).to(dt)
+                for w, b in convs:
+                    kh, kw = int(w.shape[2]), int(w.shape[3])
+                    ph, pw = tf_same_pad(x.shape[-2], kh, 2), tf_same_pad(x.shape[-1], kw, 2)
+                    oh, ow = -(-x.shape[-2] // 2), -(-x.shape[-1] // 2)
+                    xp = F.pad(x, (pw[0], pw[1], ph[0], ph[1]))
+                    # (N, Cin, kh*kw, oh, ow) -> (N, Cin*kh*kw, oh*ow): the (cin, ky, kx) order of w.reshape(Cout, -1)
+                    cols = torch.stack([xp[:, :, ky:ky + 2 * oh - 1:2, kx:kx + 2 * ow - 1:2] for ky in range(kh) for kx in range(kw)], dim=2)
+                    cols = cols.reshape(x.shape[0], -1, oh * ow)
+                    x = F.leaky_relu(torch.matmul(w.reshape(w.shape[0], -1), cols) + b[None, :, None], slope).reshape(x.shape[0], w.shape[0], oh, ow)
+                outs.append(x)
+            return flatten_nhwc(torch.cat(outs, dim=1))
+
+    def forward_exact(self, xz, yz, xy, precision="float64"):
+        """``softmax(c_model)`` of sgan.py:132-199 in inference mode (whatever ``self.training`` says) on the inputs' device with no
+        single-bf16 operand anywhere: (N,H,W) or (N,1,H,W) planes -> (N, n_classes) probabilities.
+        "x3" / "x6": the float32-class HIP trunk (:meth:`features_x3`, two / three bf16 parts per operand) + the float32 LeakyReLU
+        tail (:meth:`_tail_float32`) -- the margin guard's first two stages; planes the kernel does not take (and CPU tensors) fall
+        to "float32".  "float32": the plain PyTorch layers with autocast off, the reference's own arithmetic.  "float64": the
+        :func:`fold_batchnorm` model (float64): :meth:`features_float64` and the dense layers."""
+        import torch
+        import torch.nn.functional as F
+        if precision not in ("x3", "x6", "float32", "float64"):
+            raise ValueError("precision must be 'x3', 'x6', 'float32' or 'float64'")
+        with torch.no_grad():
+            if precision != "float64":
+                with torch.autocast("cuda", enabled=False):
+                    xs = [x.reshape(x.shape[0], 1, x.shape[-2], x.shape[-1]).float() for x in (xz, yz, xy)]
+                    if precision in ("x3", "x6") and xs[0].is_cuda and self.x3_supported(xs[0].shape[-2], xs[0].shape[-1]):
+                        return self._tail_float32(self.features_x3(*xs, parts=3 if precision == "x6" else 2))
+                    return self._eval_layers(xs)
+            f = self._folded64()
+            slope = f["slope"]
+            h = self.features_float64(xz, yz, xy)
+            (w1, b1), (w2, b2), (w3, b3) = f["fc"]
+            # the first dense layer as a batch of K-slices and a sum (rocBLAS' float64 GEMM with a few rows and a long K runs on a
+            # handful of workgroups: dnn.Classifier.forward_exact)
+            K = int(h.shape[1])
+            kc = 256 if K % 256 == 0 else K
+            part = torch.bmm(h.reshape(h.shape[0], K // kc, kc).transpose(0, 1), w1.reshape(w1.shape[0], K // kc, kc).permute(1, 2, 0))
+            h = F.leaky_relu(part.sum(dim=0) + b1, slope)
+            h = F.leaky_relu(F.linear(h, w2, b2), slope)
+            return torch.softmax(F.linear(h, w3, b3), dim=-1)
+
+    def rescore_exact(self, volumes, rescale=RESCALE, mode="max", precision="float64", rows=None, ijk=None):
+        """(n,X,Y,Z) volumes -> (n, n_classes) probabilities without a rounding the reference does not have: exact projection
+        (``common.process_volumes(scale=False)``), (p - 127.5) / 127.5 and Pillow's bicubic resize to float32 planes as Pillow stores
+        them (csrc/resize.hip, bit-identical), then :meth:`forward_exact` in ``precision``.  ``rows``: an index tensor -- score
+        ``volumes[rows]`` in that order; ``mode="slice"``: ``ijk`` (n,3) or (n,T,3), the result has n*T rows, frame-major, ``rows``
+        indexes those and row r is scored from frame r // T at ijk[r].  Bounded passes, host or device volumes: the passes are
+        dnn_guard.ExactRescore's, shared with the CNN."""
+        return self._rescore(volumes, rescale, mode, precision, rows, ijk)
+
+    @property
+    def last_guard(self):
+        """What the last guarded call did (the keys: dnn_guard.py); None before the first one."""
+        return self._margin.last
+
+    def _guard(self, proba, eps, rescore):
+        """dnn_guard.MarginGuard with this model's stage thresholds (LABEL_GUARD_X3, LABEL_GUARD_X6) on dnn_guard.CudaOps: the rows of
+        ``proba`` whose top-2 gap is below ``eps`` are replaced by what ``rescore(rows, precision)`` gives."""
+        return self._margin.run(proba, eps, rescore, dnn_guard.CudaOps(), list(self.parameters()) + list(self.buffers()))
+
+    def forward_guarded(self, xz, yz, xy, label_guard=LABEL_GUARD):
+        """:meth:`forward_fused` with the margin guard on float32 planes: rows whose two largest probabilities are closer than
+        ``label_guard`` are scored again on the planes themselves through :meth:`forward_exact` ("x3", then "x6", then "float64" for
+        the rows that stay near a tie) and replaced, so that ``argmax`` is the float64 label (the bound is empirical: dnn_guard.py).
+        ``label_guard`` None or 0: exactly :meth:`forward_fused`.  ``self.last_guard``: what the guard did."""
+        import torch
+        p = self.forward_fused(xz, yz, xy)
+        if not label_guard:
+            self._margin.run(p, None, None, None, ())
+            return p
+        xs = [x.reshape(x.shape[0], x.shape[-2], x.shape[-1]) for x in (xz, yz, xy)]
+        with torch.no_grad(), torch.cuda.device(p.device):
+            return self._guard(p, label_guard, lambda idx, prec: self.forward_exact(*[x[idx] for x in xs], precision=prec))
+
     def predict_volumes(self, volumes, rescale=RESCALE, mode="max", ijk=None, batch_size=8192, exact_resize=False, return_numpy=True,
-                        num_targets=1, return_ijk=False):
+                        num_targets=1, return_ijk=False, label_guard=None):
         """Radar volumes -> class probabilities on the GPU: (N, X, Y, Z) volumes (float32 or uint8; numpy or torch, host or device)
         -> projections -> ``(p - 127.5) / 127.5`` and the bicubic resize of sgan.py:636-681 to ``rescale`` (Pillow's (width, height))
         -> fused trunk -> LeakyReLU tail.  Grids the fused preprocessing kernel takes (``nn_common.preprocess_supported``: at 128x128 the
@@ -259,8 +454,13 @@ class Discriminator(_nn().Module):
         N*T rows, frame-major (row b*T+t), (N,T,3) and derived targets in one preprocessing launch straight from the volumes
         (csrc/preprocess_slice.hip); ``return_ijk=True`` returns ``(proba, ijk)`` with the (N,T,3) int32 indices used (a CUDA tensor;
         NumPy with ``return_numpy``).  ``batch_size``: frames per pass; a row's result does not depend on it.
-        There is no margin guard: rows whose two largest probabilities are closer than the bf16 chain's error (a few 1e-3) can
-        take the other label than float32 Keras would give."""
+        ``label_guard`` (None or 0: off, the default -- the chain above and its bits): the margin guard (dnn_guard.py), once per call
+        behind the last pass, for every mode.  The bf16 chain moves a probability by a few 1e-3 (up to 8.2e-3 measured), so rows
+        whose two largest probabilities are closer than ``label_guard`` (``sgan.LABEL_GUARD``) are scored again from their volumes
+        from exact inputs (:meth:`rescore_exact`: "x3", then "x6", then "float64" for the rows that stay near a tie; slice rows from
+        frame r // T at the indices used) and replaced; the gap widens itself to four times the error seen.  ``argmax`` is then the
+        float64 label on every row inside the covered gap -- an empirical bound, as the CNN's.  Guarded results are not
+        batching-invariant bit for bit; unguarded ones are.  ``self.last_guard``: what the guard did."""
         import torch
         from . import common, nn_common
         if not isinstance(volumes, torch.Tensor):
@@ -300,6 +500,10 @@ class Discriminator(_nn().Module):
                 if sliced:
                     used.append(got)
                 out[s0 * T:s1 * T] = self.forward_fused(*xs)
+            if label_guard:
+                vol = volumes if volumes.dtype in (torch.uint8, torch.float32) else volumes.float()
+                at = (torch.cat(used) if len(used) != 1 else used[0]) if sliced else None
+                out = self._guard(out, label_guard, lambda idx, prec: self.rescore_exact(vol, rescale, mode, prec, rows=idx, ijk=at))
         res = out.cpu().numpy() if return_numpy else out
         if sliced and return_ijk:
             got = torch.cat(used) if used else torch.zeros((0, T, 3), dtype=torch.int32, device=dev)
@@ -400,6 +604,7 @@ def folded_packs(model):
     return {"w1": st(0, "w", torch.float32), "b1": st(0, "b", torch.float32),
             "w2t": st(1, "w", torch.bfloat16), "b2": st(1, "b", torch.float32),
             "w3t": st(2, "w", torch.bfloat16), "b3": st(2, "b", torch.float32),
+            "w2f": st(1, "w", torch.float32), "w3f": st(2, "w", torch.float32), "fc1_wf": w1.float().contiguous(),
             "fc1_w": w1.to(torch.bfloat16).contiguous(), "fc1_b": b1.float().contiguous(),
             "fc2_wt": w2.float().t().contiguous(), "fc2_b": b2.float().contiguous(),
             "fc3_w": w3.float().contiguous(), "fc3_b": b3.float().contiguous(), "slope": f["slope"]}

@@ -1,6 +1,6 @@
 """SGAN classifier inference on the fused HIP chain (csrc/sgan_infer.hip + the LeakyReLU tail of csrc/dense.hip): one JSON line.
 
-    timeout -k 10 600 python tools/sgan_infer_bench.py [--torch] [--batch 4096] [--frames 4096] [--steps 20] [--warmup 5]
+    timeout -k 10 600 python tools/sgan_infer_bench.py [--torch | --guard [--out FILE]] [--batch 4096] [--frames 4096] [--steps 20] [--warmup 5]
 
 Seeded synthetic data at the reference's size (three 128 x 128 planes, three classes).  HIP events, medians of --steps runs after
 --warmup.  Reported:
@@ -15,6 +15,12 @@ Seeded synthetic data at the reference's size (three 128 x 128 planes, three cla
   torch                   with --torch, the comparator at the same batch in the same process: DiscriminatorTrainer.predict's inner
                           call (the plain PyTorch layers in inference mode) under float16 autocast and under bfloat16 autocast, on
                           planes already on the device
+With --guard nothing of the above runs; instead, one JSON line that is also written to --out (profiles/sgan_guard_bench.json):
+  guard                   Discriminator.predict_volumes on --frames Walabot frames with label_guard off and at sgan.LABEL_GUARD, on a
+                          trained-like model (decided probabilities: few rows near a tie) and on a model with no margins (the
+                          N(0, 0.02) initialisation: every row is re-scored), with what the guard did (last_guard)
+  x3 / x6                 microseconds per row of forward_exact("x3") and ("x6") (csrc/sgan_x3.hip + rml_dense_tail_lrelu_f32) on
+                          float32 planes, at a handful of rows (8) and at 256
 No figure here is a pass / fail gate.
 """
 import argparse
@@ -47,14 +53,69 @@ def median_ms(fn, steps, warmup):
     return float(np.median(ts))
 
 
+def trained_like(model, seed=1):
+    """kernels ~ N(0, sqrt(2 / fan_in)) (activations of order one through the LeakyReLU layers), a last layer large enough for decided
+    probabilities, non-trivial biases and BatchNorm statistics: what a trained classifier looks like to the guard"""
+    import torch
+    g = torch.Generator().manual_seed(seed)
+    with torch.no_grad():
+        for mod in model.modules():
+            if isinstance(mod, (torch.nn.Conv2d, torch.nn.Linear)):
+                gain = 6.0 if mod is model.fc3 else 2.0 ** 0.5
+                mod.weight.copy_((torch.randn(mod.weight.shape, generator=g) * (gain / mod.weight[0].numel() ** 0.5)).to(mod.weight.device))
+                mod.bias.copy_((torch.randn(mod.bias.shape, generator=g) * 0.2).to(mod.bias.device))
+            elif isinstance(mod, (torch.nn.BatchNorm1d, torch.nn.BatchNorm2d)):
+                mod.weight.copy_((torch.rand(mod.weight.shape, generator=g) + 0.5).to(mod.weight.device))
+                mod.bias.copy_((torch.randn(mod.bias.shape, generator=g) * 0.3).to(mod.bias.device))
+    return model
+
+
+def guard_bench(args):
+    import torch
+    import radar_ml_amd as rml
+    from radar_ml_amd import sgan
+    torch.manual_seed(0)
+    res = {"what": "SGAN classifier margin guard", "frames": args.frames, "grid": [22, 31, 176], "planes": [3, 128, 128], "steps": args.steps,
+           "label_guard": sgan.LABEL_GUARD, "device": torch.cuda.get_device_name(0)}
+    v, _ = rml.synth_volumes(args.frames, 22, 31, 176, seed=7)
+    for name in ("trained_like", "no_margins"):
+        model = sgan.define_discriminator(device="cuda").eval()
+        with torch.no_grad():
+            for mod in model.modules():
+                if isinstance(mod, (torch.nn.BatchNorm1d, torch.nn.BatchNorm2d)):
+                    mod.running_mean.normal_(0.0, 0.1)
+                    mod.running_var.uniform_(0.5, 2.0)
+        if name == "trained_like":
+            trained_like(model)
+        off = median_ms(lambda: model.predict_volumes(v, batch_size=args.batch, return_numpy=False), args.steps, args.warmup)
+        on = median_ms(lambda: model.predict_volumes(v, batch_size=args.batch, return_numpy=False, label_guard=sgan.LABEL_GUARD), args.steps, args.warmup)
+        rep = {k: (round(x, 9) if isinstance(x, float) else x) for k, x in model.last_guard.items()}
+        res[name] = {"guard_off_ms": round(off, 4), "guard_on_ms": round(on, 4), "guard_cost": round(on / off - 1.0, 4), "last_guard": rep}
+        if name == "trained_like":
+            for rows in (8, 256):
+                xs = [torch.rand((rows, 128, 128), device="cuda") * 2 - 1 for _ in range(3)]
+                for prec in ("x3", "x6"):
+                    ms = median_ms(lambda: model.forward_exact(*xs, precision=prec), args.steps, args.warmup)
+                    res["%s_us_per_row_at_%d_rows" % (prec, rows)] = round(ms * 1e3 / rows, 3)
+    line = json.dumps(res)
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        f.write(line + "\n")
+    print(line)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--guard", action="store_true")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "sgan_guard_bench.json"))
     ap.add_argument("--torch", action="store_true")
     ap.add_argument("--batch", type=int, default=4096)
     ap.add_argument("--frames", type=int, default=4096)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     args = ap.parse_args()
+    if args.guard:
+        return guard_bench(args)
     import torch
     import radar_ml_amd as rml
     from radar_ml_amd import nn_common, sgan
