@@ -389,6 +389,29 @@ int rml_gram(rml_ctx* ctx, const float* feat, int64_t ld_feat, int64_t N, int64_
              int nk, const int* kinds, const double* gammas,
              double* out, int64_t ld_out, int64_t stride_k, void* stream);
 
+/* The same service for a search over projection masks: a row is the concatenation of `nseg` column segments (the reference's
+ * xz, yz, xy projections), and the inner products and squared norms of any union of segments are the sums of the segments' own.
+ * rml_gram_segments forms, in ONE pass over the rows, the float64 inner products G_s and squared row norms of every segment
+ * (rml_gram's arithmetic: float32 rows, exact products, float64 accumulation in ascending k within the segment).
+ *   feat: DEVICE N x ld_feat float32.  seg_len: HOST, nseg positive lengths, 1 <= nseg <= 8, sum <= ld_feat; segment s is the
+ *   columns [sum_{t<s} seg_len[t], + seg_len[s]).  Columns past the last segment are never read.
+ *   G: DEVICE; G_s at G + s * stride_s, row i at + i * ld_g (ld_g >= N, stride_s >= N * ld_g); only [0,N) x [0,N) is written.
+ *   nsq: DEVICE, nseg * N doubles: the squared norm of segment s of row i at nsq[s * N + i].
+ * Every G_s is bit-exactly symmetric.  Uses the context's workspace.
+ * rml_gram_compose writes n_out kernel matrices from them (HOST arrays of n_out >= 1 entries, any number): output k is the
+ * kernel kinds[k] / gammas[k] (as rml_gram: gamma ignored for LINEAR, otherwise finite and >= 0) of the columns of mask
+ * seg_bits[k], a non-zero subset of the nseg segments (bit s = segment s).  With g = sum G_s[i][j] and n_i = sum nsq[s * N + i]
+ * over the set bits in ascending s: d2 = (n_i + n_j) - 2 g, K = g (LINEAR) or exp(-gamma_k * d2) (RBF).  The sums associate by
+ * segment, so an output is not the bits of rml_gram on the column subset; it obeys the same error bound.  out: matrix k at
+ * out + k * stride_k, row i at + i * ld_out (ld_out >= N, stride_k >= N * ld_out).  Every output is bit-exactly symmetric (what
+ * rml_smo_solve requires).  Both calls: deterministic run to run, N == 0 is a no-op, asynchronous on `stream`, no environment
+ * variable read. */
+int rml_gram_segments(rml_ctx* ctx, const float* feat, int64_t ld_feat, int64_t N, int nseg, const int64_t* seg_len,
+                      double* G, int64_t ld_g, int64_t stride_s, double* nsq, void* stream);
+int rml_gram_compose(rml_ctx* ctx, const double* G, int64_t ld_g, int64_t stride_s, const double* nsq, int64_t N, int nseg,
+                     int n_out, const int* seg_bits, const int* kinds, const double* gammas,
+                     double* out, int64_t ld_out, int64_t stride_k, void* stream);
+
 /* ---- SVC duals of a grid search on the device ---------------------------------------------------------------------
  * rml_smo_solve: a batch of independent binary C-SVC duals (one per grid point x fold x class pair), each solved by one
  * workgroup running libsvm's Solver::Solve as scikit-learn ships it (sklearn/svm/src/libsvm/svm.cpp: Solver, lines

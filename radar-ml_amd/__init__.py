@@ -17,7 +17,7 @@ from .synth import synth_volumes
 from .augment import DataGenerator, augment_planes, rotation_params
 from .train import (GridSearchSVC, find_best_svm_estimator, fit_svc, GridSearchSGD, find_best_sgd_svm_estimator, fit_sgd,
                     partial_fit_sgd, partial_fit_sgd_steps, balance_classes, balance_indices, sgd_fit, svc_fit, calibrate_prefit,
-                    evaluate_model)
+                    evaluate_model, ProjMaskSearchSVC, find_best_proj_mask_svm_estimator, svc_fit_masks)
 
 __all__ = [
     "RadarMLError", "ProjMask", "ProjZoom", "DerivedTarget", "RADAR_MAX", "RADAR_MIN",
@@ -28,6 +28,7 @@ __all__ = [
     "DataGenerator", "augment_planes", "rotation_params", "GridSearchSVC", "find_best_svm_estimator", "fit_svc",
     "GridSearchSGD", "find_best_sgd_svm_estimator", "fit_sgd", "partial_fit_sgd",
     "partial_fit_sgd_steps", "balance_classes", "balance_indices", "sgd_fit", "svc_fit", "calibrate_prefit", "evaluate_model",
+    "ProjMaskSearchSVC", "find_best_proj_mask_svm_estimator", "svc_fit_masks",
     "define_classifier", "train_classifier", "define_discriminator", "fold_batchnorm", "folded_packs",
     "define_generator", "fold_generator", "generator_packs", "generate_dataset",
 ]

@@ -4,12 +4,14 @@ Every estimator that leaves this module is a genuine scikit-learn one (``SVC``, 
 what the reference does with it afterwards (the pickle, predict.py, ``from_sklearn``) works unchanged.  In file order:
 
 * Device hooks: ``_gram`` (``rml_gram``: every kernel matrix of a grid from one upload), ``_smo`` (``smo_device``: libsvm's duals and
-  their held-out scores, batched, on matrices that stay on the device), ``_sgd`` (``sgd_device``: scikit-learn's SGD problems, batched)
+  their held-out scores, batched, on matrices that stay on the device), their twins for the projection-mask search ``_gram_masks`` /
+  ``_smo_masks`` (``rml_gram_segments`` once, ``rml_gram_compose`` per group of mask x kernel matrices), ``_sgd`` (``sgd_device``: scikit-learn's SGD problems, batched)
   and ``_sgd_online`` (``sgd_online_device``: a chain of partial_fit steps in one call).  All device work of the rest of the module
-  goes through these four names, looked up in the module at call time (tests replace them with NumPy twins).
+  goes through these six names, looked up in the module at call time (tests replace them with NumPy twins).
 * Fits: ``fit_svc`` (``SVC.fit``, Platt step included), ``fit_sgd`` / ``partial_fit_sgd`` and the chain ``partial_fit_sgd_steps``.
-* Searches: ``GridSearchSVC`` and ``GridSearchSGD`` on one ``GridSearchCV`` scaffold, inside the reference's ``find_best_*``.
-* Flows: ``sgd_fit`` / ``svc_fit`` of the reference (features, ``balance_classes``, augment epochs, search or online chain).
+* Searches: ``GridSearchSVC`` (and ``ProjMaskSearchSVC``, which adds the projection mask to its candidates) and ``GridSearchSGD``
+  on one ``GridSearchCV`` scaffold, inside the reference's ``find_best_*``.
+* Flows: ``sgd_fit`` / ``svc_fit`` (``svc_fit_masks``: the mask chosen by the search) of the reference (features, ``balance_classes``, augment epochs, search or online chain).
 * Calibration and evaluation: ``calibrate_prefit`` and ``evaluate_model``.
 """
 import logging
@@ -131,6 +133,99 @@ def _smo(X, kernels, plan, device=None):
     dev = _lib.device_of(device)
     with torch.cuda.device(dev):
         Kd = _gram_device(X, kernels, dev)
+        out = smo_device(Kd, plan, dev)
+    out["matrix"] = lambda k: Kd[k].cpu().numpy()
+    out["solve"] = lambda plan2: smo_device(Kd, plan2, dev)
+    return out
+
+
+# ---- device hooks of the projection-mask search: per-segment inner products once, mask x kernel matrices composed from them --------
+# A mask key is (bits, 'linear', None) / (bits, 'rbf', gamma): bit s selects segment s of the rows (common._mask_bits' order).
+_segment_cache = {}                     # the resident products of ONE set of rows (ProjMaskSearchSVC.fit releases them)
+
+
+def _release_segments():
+    _segment_cache.clear()
+
+
+def segment_products_device(Xd, segments, device=None):
+    """``rml_gram_segments`` on the DEVICE rows ``Xd`` ((N, sum(segments)) float32): the DEVICE tensors ``G`` (nseg, N, N) and ``nsq``
+    (nseg, N), float64, of the inner products and squared row norms of every segment (all lengths positive)."""
+    import torch
+    lib = _lib.load()
+    dev, ctx, N, D, ld = _device_rows("segment_products_device", Xd, device)
+    seg = np.array([int(v) for v in segments], dtype=np.int64)
+    if len(seg) < 1 or (seg < 1).any() or int(seg.sum()) != D:
+        raise ValueError("segment_products_device: %r are not positive lengths that add up to the %d columns" % (list(segments), D))
+    with torch.cuda.device(dev):
+        G = torch.empty((len(seg), N, N), dtype=torch.float64, device=dev)
+        nsq = torch.empty((len(seg), N), dtype=torch.float64, device=dev)
+        _lib.check(lib.rml_gram_segments(ctx, _lib.ptr(Xd), ld, N, len(seg), seg.ctypes.data, _lib.ptr(G), N, N * N, _lib.ptr(nsq),
+                                         _lib.stream_ptr(dev)), "rml_gram_segments")
+    return G, nsq
+
+
+def compose_device(G, nsq, keys, device=None):
+    """``rml_gram_compose``: the kernel matrices of the mask keys ``keys`` (bits over the segments of ``G`` / ``nsq``, as
+    ``segment_products_device`` returns them) as a DEVICE (len(keys), N, N) float64 tensor, each bit-exactly symmetric."""
+    import torch
+    lib = _lib.load()
+    dev = _lib.device_of(device if device is not None else G.device)
+    nseg, N = int(G.shape[0]), int(G.shape[1])
+    bits = np.array([b for b, _, _ in keys], dtype=np.int32)
+    kinds = np.array([_lib.GRAM_LINEAR if k == "linear" else _lib.GRAM_RBF for _, k, _ in keys], dtype=np.int32)
+    gammas = np.array([0.0 if g is None else float(g) for _, _, g in keys], dtype=np.float64)
+    with torch.cuda.device(dev):
+        out = torch.empty((len(keys), N, N), dtype=torch.float64, device=dev)
+        _lib.check(lib.rml_gram_compose(_lib.context(dev), _lib.ptr(G), N, N * N, _lib.ptr(nsq), N, nseg, len(keys), bits.ctypes.data,
+                                        kinds.ctypes.data, gammas.ctypes.data, _lib.ptr(out), N, N * N, _lib.stream_ptr(dev)),
+                   "rml_gram_compose")
+    return out
+
+
+def _mask_matrices_device(X, segments, keys, dev):
+    """The DEVICE (len(keys), N, N) matrices of the mask keys of the float32 host rows ``X``: the rows uploaded and their segment
+    products formed on the first call for these rows, and kept resident for the following ones."""
+    import torch
+    segments = tuple(int(v) for v in segments)
+    used = [i for i, n in enumerate(segments) if n > 0]          # rml_gram_segments takes positive lengths
+    tag = (id(X), X.shape, segments, str(dev))
+    entry = _segment_cache.get("entry")
+    if entry is None or entry[0] != tag:
+        _release_segments()
+        Xd = torch.from_numpy(np.ascontiguousarray(X, dtype=np.float32)).to(dev)
+        entry = (tag, X) + segment_products_device(Xd, [segments[i] for i in used], dev)     # X: keeps id(X) from being reused
+        _segment_cache["entry"] = entry
+    dense = []
+    for bits, kernel, gamma in keys:
+        if bits < 1 or bits >> len(segments) or any(bits >> i & 1 and segments[i] == 0 for i in range(len(segments))):
+            raise ValueError("mask bits %d select no segment or an empty one of %r" % (bits, segments))
+        dense.append((sum(1 << j for j, i in enumerate(used) if bits >> i & 1), kernel, gamma))
+    return compose_device(entry[2], entry[3], dense, dev)
+
+
+def _gram_masks(X, segments, keys, device=None):
+    """Every kernel matrix of the mask keys ``keys`` of the float32 rows ``X`` (full rows: the concatenation of ``segments``
+    columns each): one upload and one ``rml_gram_segments`` pass per set of rows, one ``rml_gram_compose`` call, one copy back.
+    Returns a list of host (N, N) float64 matrices.
+
+    All device work of the host mask search goes through this function (tests replace it to run the search logic without a GPU)."""
+    import torch
+    dev = _lib.device_of(device)
+    with torch.cuda.device(dev):
+        host = _mask_matrices_device(X, segments, keys, dev).cpu().numpy()
+    return [host[k] for k in range(len(keys))]
+
+
+def _smo_masks(X, segments, keys, plan, device=None):
+    """``_smo`` for mask keys: the matrices composed from the resident segment products stay ON THE DEVICE, every dual of ``plan``
+    is solved and every held-out row scored there (``smo_device``).  Returns ``smo_device``'s dict plus ``matrix`` and ``solve``.
+
+    All device work of the device mask search goes through this function (tests replace it to run the search logic without a GPU)."""
+    import torch
+    dev = _lib.device_of(device)
+    with torch.cuda.device(dev):
+        Kd = _mask_matrices_device(X, segments, keys, dev)
         out = smo_device(Kd, plan, dev)
     out["matrix"] = lambda k: Kd[k].cpu().numpy()
     out["solve"] = lambda plan2: smo_device(Kd, plan2, dev)
@@ -1117,13 +1212,14 @@ class GridSearchSVC(_GridSearch):
     # ---- argument checks (before any work) ----
     def _check(self):
         from sklearn.svm import SVC
+        who = type(self).__name__
         if self.solver not in ("host", "device"):
-            raise ValueError("GridSearchSVC: solver must be 'host' or 'device', got %r" % (self.solver,))
+            raise ValueError("%s: solver must be 'host' or 'device', got %r" % (who, self.solver))
         if self.refit_solver not in ("host", "device"):
-            raise ValueError("GridSearchSVC: refit_solver must be 'host' or 'device', got %r" % (self.refit_solver,))
-        candidates, base = self._check_search("GridSearchSVC", SVC, "SVC.score, GridSearchCV's default", _GRID_KEYS)
+            raise ValueError("%s: refit_solver must be 'host' or 'device', got %r" % (who, self.refit_solver))
+        candidates, base = self._check_search(who, SVC, "SVC.score, GridSearchCV's default", _GRID_KEYS)
         for p in candidates:
-            _check_kernel("GridSearchSVC", p.get("kernel", base["kernel"]), p.get("gamma", base["gamma"]), p.get("C", base["C"]))
+            _check_kernel(who, p.get("kernel", base["kernel"]), p.get("gamma", base["gamma"]), p.get("C", base["C"]))
         return candidates, base
 
     def _check_data(self, X32, y):
@@ -1132,6 +1228,20 @@ class GridSearchSVC(_GridSearch):
 
     def _key(self, p, base):
         return _kernel_key(p.get("kernel", base["kernel"]), p.get("gamma", base["gamma"]))
+
+    # the device entry points of the search and what turns the winner's fitted attributes into best_estimator_ (ProjMaskSearchSVC
+    # has its own)
+    _MAX_KEYS = 8                           # matrices per _gram / _smo call
+
+    def _gram_of(self, s, keys):
+        return _gram(s.X32, keys, self.device)
+
+    def _smo_of(self, s, keys, plan):
+        return _smo(s.X32, keys, plan, self.device)
+
+    def _adopted(self, s, best, fitted, key):
+        from sklearn.base import clone
+        return _adopt(clone(self.estimator).set_params(**best), fitted, s.X32, key)
 
     def _svc(self, p, base, kernel, probability=None):
         from sklearn.svm import SVC
@@ -1199,9 +1309,9 @@ class GridSearchSVC(_GridSearch):
     def _groups(self, candidates, base, N):
         """The distinct kernels of the grid in candidate order, in groups of at most 8 whose host copies stay under ``max_gram_bytes``."""
         mat_bytes = N * N * 8
-        per = min(8, int(self.max_gram_bytes // mat_bytes))
+        per = min(self._MAX_KEYS, int(self.max_gram_bytes // mat_bytes))
         if per < 1:
-            raise ValueError("GridSearchSVC: one %d x %d kernel matrix takes %d bytes, more than max_gram_bytes=%d"
+            raise ValueError(type(self).__name__ + ": one %d x %d kernel matrix takes %d bytes, more than max_gram_bytes=%d"
                              % (N, N, mat_bytes, self.max_gram_bytes))
         keys = []
         for p in candidates:
@@ -1235,14 +1345,14 @@ class GridSearchSVC(_GridSearch):
     def _search_host(self, s, grp, pool):
         """One group of kernels searched on the host: its matrices by ``_gram``, every fit of its candidates on the pool."""
         todo = [(ci, si) for ci, p in enumerate(s.candidates) if self._key(p, s.base) in grp for si in range(len(s.splits))]
-        mats = dict(zip(grp, _gram(s.X32, grp, self.device)))
+        mats = dict(zip(grp, self._gram_of(s, grp)))
         self._fit_on_host(s, pool, mats, todo)
         return _Matrices(mats, {}, {})
 
     def _search_device(self, s, grp, pool):
         """One group of kernels searched on the device: ``_smo_plan``'s batch by ``_smo``; what it leaves to the host is fitted there."""
         plan, on_device, todo = self._smo_plan(s.candidates, s.base, grp, s.splits, s.y)
-        out = _smo(s.X32, grp, plan, self.device)
+        out = self._smo_of(s, grp, plan)
         fetch = {k: (lambda i=i, m=out["matrix"]: m(i)) for i, k in enumerate(grp)}
         resident = {k: (i, out["solve"]) for i, k in enumerate(grp)} if "solve" in out else {}
         for f, (ci, si) in enumerate(on_device):
@@ -1256,12 +1366,11 @@ class GridSearchSVC(_GridSearch):
 
     def _refit(self, s, where):
         """The winner refitted on all rows, on its kernel matrix from ``where`` (the ``_Matrices`` of the last group) or computed again."""
-        from sklearn.base import clone
-        best = self.best_params_
+        best = s.candidates[self.best_index_]
         key = self._key(best, s.base)
         if self.refit_solver == "device":
             # the winner's matrix where the search left it, or (host search, or a winner of an earlier group) computed again
-            matrix, run = where.resident.get(key, (0, lambda plan: _smo(s.X32, [key], plan, self.device)))
+            matrix, run = where.resident.get(key, (0, lambda plan: self._smo_of(s, [key], plan)))
             params = {k: s.base[k] for k in _FIT_CARRY}
             params["C"] = best.get("C", s.base["C"])
             t0 = time.perf_counter()
@@ -1269,13 +1378,13 @@ class GridSearchSVC(_GridSearch):
             self.refit_time_ = time.perf_counter() - t0
         else:
             K = (where.host[key] if key in where.host else where.fetch[key]() if key in where.fetch
-                 else _gram(s.X32, [key], self.device)[0])
+                 else self._gram_of(s, [key])[0])
             t0 = time.perf_counter()
             pre = self._svc(best, s.base, "precomputed").fit(K, s.y)
             self.refit_time_ = time.perf_counter() - t0
             params = pre.get_params()
             fitted = {k: v for k, v in vars(pre).items() if k not in params}
-        self.best_estimator_ = _adopt(clone(self.estimator).set_params(**best), fitted, s.X32, key)
+        self.best_estimator_ = self._adopted(s, best, fitted, key)
 
     def fit(self, X, y):
         candidates, base = self._check()
@@ -1320,6 +1429,139 @@ def find_best_svm_estimator(X, y, cv, random_seed, solver="host", refit_solver="
                                 refit_solver=refit_solver)
     grid_search.fit(X, y)
     return _log_best(grid_search)
+
+
+# ---- ProjMaskSearchSVC: the projection mask searched with the grid, and the reference's search with it -----------------------------
+def _all_proj_masks():
+    from .common import ProjMask
+    return [ProjMask(bool(b & 1), bool(b & 2), bool(b & 4)) for b in range(1, 8)]
+
+
+class ProjMaskSearchSVC(GridSearchSVC):
+    """``GridSearchSVC`` over projection masks x ``param_grid``: the reference's "which projections" hyperparameter searched in one
+    fit instead of one ``GridSearchSVC`` per mask on a column subset.
+
+    ``fit(X, y)`` takes the FULL rows, the concatenation of ``segments`` = (xz, yz, xy) feature counts.  They are uploaded once, one
+    ``rml_gram_segments`` pass forms the inner products and squared norms of every projection, and every mask x kernel matrix is
+    composed from those (``rml_gram_compose``: the products of a mask are the sums of its projections') in groups that stay under
+    ``max_gram_bytes``; each group is searched as ``GridSearchSVC`` searches a group of kernels (``solver`` / ``refit_solver`` as
+    there).  Candidates are ``proj_masks`` (outer, in the given order; default: the seven non-empty masks by ``common._mask_bits``)
+    x ``ParameterGrid(param_grid)`` (inner); ``cv_results_`` has ``param_proj_mask`` and ``"proj_mask"`` in every ``params`` dict,
+    ranks run over all candidates and the first best wins.  ``best_proj_mask_`` is the winner's mask, ``best_params_`` its grid
+    point without the mask, and ``best_estimator_`` a genuine ``SVC`` fitted on the winning mask's columns.  ``predict``,
+    ``decision_function``, ``predict_proba`` and ``score`` take full rows and select those columns."""
+
+    _MAX_KEYS = 1 << 30                     # rml_gram_compose has no cap: max_gram_bytes alone sizes a group
+
+    def __init__(self, estimator, param_grid, segments, proj_masks=None, cv=5, n_jobs=4, refit=True, device=None,
+                 max_gram_bytes=8 << 30, scoring=None, verbose=0, solver="host", refit_solver="host"):
+        super().__init__(estimator, param_grid, cv, n_jobs, refit, device, max_gram_bytes, scoring, verbose, solver, refit_solver)
+        self.segments = segments
+        self.proj_masks = proj_masks
+
+    def _segments(self):
+        seg = tuple(int(v) for v in self.segments)
+        if len(seg) != 3 or any(v < 0 for v in seg):
+            raise ValueError("ProjMaskSearchSVC: segments are the three feature counts (xz, yz, xy), got %r" % (self.segments,))
+        return seg
+
+    def _masks(self):
+        from .common import ProjMask, _mask_bits
+        seg = self._segments()
+        masks = _all_proj_masks() if self.proj_masks is None else [ProjMask(*(bool(v) for v in m)) for m in self.proj_masks]
+        for m in masks:
+            _mask_bits(m)                   # raises on a mask that selects no projection
+            if any(m[i] and seg[i] == 0 for i in range(3)):
+                raise ValueError("ProjMaskSearchSVC: %r selects a projection of zero length (segments %r)" % (m, seg))
+        return masks
+
+    def _cols(self, mask):
+        start = np.concatenate([[0], np.cumsum(self._segments())])
+        return np.concatenate([np.arange(start[i], start[i + 1]) for i in range(3) if mask[i]])
+
+    def _check(self):
+        grid, base = super()._check()
+        return [dict(p, proj_mask=m) for m in self._masks() for p in grid], base
+
+    def _check_data(self, X32, y):
+        if X32.shape[1] != sum(self._segments()):
+            raise ValueError("ProjMaskSearchSVC: X has %d features, segments %r add up to %d" % (X32.shape[1], self._segments(),
+                                                                                               sum(self._segments())))
+        super()._check_data(X32, y)
+
+    def _key(self, p, base):
+        from .common import _mask_bits
+        return (_mask_bits(p["proj_mask"]),) + super()._key(p, base)
+
+    def _gram_of(self, s, keys):
+        return _gram_masks(s.X32, self._segments(), keys, self.device)
+
+    def _smo_of(self, s, keys, plan):
+        return _smo_masks(s.X32, self._segments(), keys, plan, self.device)
+
+    def _adopted(self, s, best, fitted, key):
+        from sklearn.base import clone
+        params = {k: v for k, v in best.items() if k != "proj_mask"}
+        rows = np.ascontiguousarray(s.X32[:, self._cols(best["proj_mask"])])
+        return _adopt(clone(self.estimator).set_params(**params), fitted, rows, key[1:])
+
+    def _finish(self, candidates, n_splits, fit_t, score_t, scores):
+        super()._finish(candidates, n_splits, fit_t, score_t, scores)
+        best = candidates[self.best_index_]
+        self.best_proj_mask_ = best["proj_mask"]
+        self.best_params_ = {k: v for k, v in best.items() if k != "proj_mask"}
+
+    def fit(self, X, y):
+        try:
+            return super().fit(X, y)
+        finally:
+            _release_segments()             # the segment products were resident for the whole fit, and no longer
+
+    def _best_rows(self, X):
+        X = np.asarray(X)
+        if X.ndim != 2 or X.shape[1] != sum(self._segments()):
+            raise ValueError("ProjMaskSearchSVC: expected full rows of %d features, got an array of shape %r"
+                             % (sum(self._segments()), X.shape))
+        return X[:, self._cols(self.best_proj_mask_)]
+
+    def predict(self, X):
+        return self.best_estimator_.predict(self._best_rows(X))
+
+    def decision_function(self, X):
+        return self.best_estimator_.decision_function(self._best_rows(X))
+
+    def predict_proba(self, X):
+        return self.best_estimator_.predict_proba(self._best_rows(X))
+
+    def score(self, X, y):
+        return self.best_estimator_.score(self._best_rows(X), y)
+
+
+def find_best_proj_mask_svm_estimator(X, y, cv, random_seed, segments, proj_masks=None, solver="host", refit_solver="host"):
+    """``find_best_svm_estimator`` with the projection mask searched as well (the reference's README: "choosing the optimal
+    combination as a training hyperparameter"): the same grid, base estimator and log lines over ``proj_masks`` (default: all
+    seven) of the full rows ``X`` = concat of ``segments`` (xz, yz, xy) columns (ProjMaskSearchSVC).
+
+    Returns:
+        (optimized svm estimator, fitted on the winning mask's columns; that ProjMask).
+    """
+    from sklearn import svm
+    print('\n Finding best svm estimator and projection mask...')
+    Cs = [0.01, 0.1, 1, 10, 100]
+    gammas = [0.001, 0.01, 0.1, 1, 10]
+    param_grid = [
+        {'C': Cs, 'kernel': ['linear']},
+        {'C': Cs, 'gamma': gammas, 'kernel': ['rbf']}
+    ]
+    init_est = svm.SVC(probability=True, class_weight='balanced',
+                       random_state=random_seed, cache_size=1000, verbose=False)
+    grid_search = ProjMaskSearchSVC(estimator=init_est, param_grid=param_grid, segments=segments, proj_masks=proj_masks, verbose=2,
+                                    n_jobs=4, cv=cv, solver=solver, refit_solver=refit_solver)
+    grid_search.fit(X, y)
+    estimator = _log_best(grid_search)
+    logger.info('\n Best projection mask:')
+    logger.info(grid_search.best_proj_mask_)
+    return estimator, grid_search.best_proj_mask_
 
 
 # ---- GridSearchSGD and the reference's find_best_sgd_svm_estimator -----------------------------------------------------------------
@@ -1611,17 +1853,10 @@ def sgd_fit(train, test, proj_mask, online_learn, svm_model, epochs, folds=5, ba
     return clf
 
 
-def svc_fit(train, proj_mask, epochs, folds=5, batch_size=32, solver="host", refit_solver="host", device=None):
-    """Fit SVM using SVC on data set (train.py:442-545): the training set augmented ``epochs`` times on the GPU (one
-    ``DataGenerator.augment_dataset`` call per epoch; ``batch_size`` only sliced the reference's loop, the draws are the same
-    stream), the 1e-6 scale check, the features to device rows, ``balance_classes`` and ``find_best_svm_estimator``
-    (``solver`` / ``refit_solver`` as there).
-
-    Returns:
-        estimator: Estimator that was chosen by grid search.
-    """
+def _svc_training_set(train, epochs, device):
+    """The projection tuples and labels ``svc_fit`` searches on (train.py:442-520): the training set augmented ``epochs`` times on the
+    GPU, with the reference's 1e-6 scale check.  Nothing here depends on the projection mask."""
     import torch
-    from sklearn import model_selection
     from .augment import DataGenerator
     X_train, y_train = train
     X_train = list(X_train)
@@ -1642,6 +1877,20 @@ def svc_fit(train, proj_mask, epochs, folds=5, batch_size=32, solver="host", ref
         assert abs(top - 1.0) < 1e-6, 'scale error'
         y_train = np.concatenate(y_parts).astype(np.int8)
         logger.info(f'Augmented number of training samples: {y_train.shape[0]}')
+    return X_train, y_train
+
+
+def svc_fit(train, proj_mask, epochs, folds=5, batch_size=32, solver="host", refit_solver="host", device=None):
+    """Fit SVM using SVC on data set (train.py:442-545): the training set augmented ``epochs`` times on the GPU (one
+    ``DataGenerator.augment_dataset`` call per epoch; ``batch_size`` only sliced the reference's loop, the draws are the same
+    stream), the 1e-6 scale check, the features to device rows, ``balance_classes`` and ``find_best_svm_estimator``
+    (``solver`` / ``refit_solver`` as there).
+
+    Returns:
+        estimator: Estimator that was chosen by grid search.
+    """
+    from sklearn import model_selection
+    X_train, y_train = _svc_training_set(train, epochs, device)
     logger.info('Generating feature vectors from radar projections.')
     Xd = _feature_rows(X_train, proj_mask, device)
     logger.info(f'Feature vector length: {Xd.shape[1]}')
@@ -1651,6 +1900,31 @@ def svc_fit(train, proj_mask, epochs, folds=5, batch_size=32, solver="host", ref
     logger.info('Finding best classifier.')
     Xh = Xd.cpu().numpy()
     return find_best_svm_estimator(Xh, y_train, list(skf.split(Xh, y_train)), RANDOM_SEED, solver=solver, refit_solver=refit_solver)
+
+
+def svc_fit_masks(train, epochs, proj_masks=None, folds=5, batch_size=32, solver="host", refit_solver="host", device=None):
+    """``svc_fit`` with the projection mask chosen by the search: the same augmentation, scale check, ``balance_classes`` and
+    ``StratifiedKFold`` (none depends on the mask) on rows assembled ONCE from all three projections, then
+    ``find_best_proj_mask_svm_estimator`` over ``proj_masks`` (default: all seven) with the segments taken from the samples' plane
+    shapes.
+
+    Returns:
+        (estimator chosen by the search, fitted on its mask's columns; that ProjMask).
+    """
+    from sklearn import model_selection
+    from .common import ProjMask
+    X_train, y_train = _svc_training_set(train, epochs, device)
+    segments = tuple(int(np.prod(tuple(X_train[0][i].shape))) for i in range(3))
+    logger.info('Generating feature vectors from radar projections.')
+    Xd = _feature_rows(X_train, ProjMask(True, True, True), device)
+    logger.info(f'Feature vector length: {Xd.shape[1]}')
+    logger.info('Balancing classes.')
+    y_train, Xd = balance_classes(y_train, Xd)
+    skf = model_selection.StratifiedKFold(n_splits=folds)
+    logger.info('Finding best classifier and projection mask.')
+    Xh = Xd.cpu().numpy()
+    return find_best_proj_mask_svm_estimator(Xh, y_train, list(skf.split(Xh, y_train)), RANDOM_SEED, segments, proj_masks=proj_masks,
+                                             solver=solver, refit_solver=refit_solver)
 
 
 # ---- calibration and evaluation ----------------------------------------------------------------------------------------------------

@@ -19,6 +19,14 @@ and the reference's grid (5 linear + 25 RBF points, 5 stratified folds).  Per se
                  (GridSearchSVC(refit_solver="device")); refit_solver names which one the line timed
 --sklearn also runs scikit-learn's GridSearchCV on the raw rows of the 1458 set, on the sub-grid stated in the output (the full grid
 runs for about an hour), and reports its time and whether best_params_ agree with GridSearchSVC on the same sub-grid.
+
+--masks [--segments 3872,5457,682] [--reps 5] times the projection-mask search instead (ProjMaskSearchSVC: the seven masks x the
+reference's grid from one rml_gram_segments pass) on the first of --sets, against the loop it replaces -- the seven masks through
+GridSearchSVC on column subsets, same --solver / --refit / n_jobs -- in the same process, the two alternating, --reps times each:
+  mask_search_s / loop_s          medians of the end-to-end wall times (each list is in the line too)
+  gram_segments_ms, compose_ms    rml_gram_segments of the rows and rml_gram_compose of the 42 matrices, HIP events, medians
+  solve_ms, score_ms, refit_s     of the last mask search: the batched solve / score calls (--solver device; the sum of the host
+                                  fits' times otherwise) and the refit of the winner
 """
 import argparse
 import json
@@ -39,7 +47,7 @@ GRID = [{"C": CS, "kernel": ["linear"]}, {"C": CS, "gamma": GAMMAS, "kernel": ["
 SUB_GRID = [{"C": [1, 10], "kernel": ["linear"]}, {"C": [1, 10], "gamma": [0.001, 0.01], "kernel": ["rbf"]}]
 
 
-def synth(N, on_grid, seed):
+def synth(N, on_grid, seed, D=D):
     """three balanced, overlapping classes of sparse radar-like rows: a shared blob pattern, a weak per-class one, per-row noise"""
     rng = np.random.default_rng(seed)
     y = np.arange(N) % 3
@@ -182,6 +190,102 @@ def run_set(rml, N, on_grid, jobs, seed, refit="host"):
     return res, X, y
 
 
+def event_ms(call, reps):
+    """HIP-event times of ``call`` after one warm-up"""
+    import torch
+    call()
+    torch.cuda.synchronize()
+    ms = []
+    for _ in range(reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        call()
+        e1.record()
+        e1.synchronize()
+        ms.append(e0.elapsed_time(e1))
+    return ms
+
+
+def run_masks(rml, N, segments, jobs, solver, refit, reps, seed):
+    """ProjMaskSearchSVC against the seven GridSearchSVC fits on column subsets that it replaces, alternating, same options"""
+    import torch
+    from sklearn.model_selection import StratifiedKFold
+    import radar_ml_amd.train as T
+    Dm = sum(segments)
+    X, y = synth(N, True, seed, Dm)
+    masks = T._all_proj_masks()
+    start = np.concatenate([[0], np.cumsum(segments)])
+    cols = [np.concatenate([np.arange(start[i], start[i + 1]) for i in range(3) if m[i]]) for m in masks]
+    subsets = [np.ascontiguousarray(X[:, c]) for c in cols]          # the loop's inputs, made outside its clock
+    kw = dict(n_jobs=max(jobs), solver=solver, refit_solver=refit)
+    cv = lambda: StratifiedKFold(5).split(X, y)
+
+    def mask_search():
+        return T.ProjMaskSearchSVC(base_svc(), GRID, segments, cv=cv(), **kw).fit(X, y)
+
+    def loop():
+        fits = [T.GridSearchSVC(base_svc(), GRID, cv=cv(), **kw).fit(Xs, y) for Xs in subsets]
+        return max(enumerate(fits), key=lambda f: (f[1].best_score_, -f[0]))
+
+    seen = []
+    real = T._smo_masks
+
+    def watched(Xh, seg, keys, plan, device=None):
+        out = real(Xh, seg, keys, plan, device)
+        seen.append((len(plan["problems"]), out["solve_s"], out["score_s"]))
+        return out
+    T._smo_masks = watched
+    try:
+        ms, (wi, w) = mask_search(), loop()                           # warm-up of both (code load, workspace growth)
+        t_mask, t_loop = [], []
+        for r in range(reps):
+            del seen[:]
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            ms = mask_search()
+            torch.cuda.synchronize()
+            t1 = time.perf_counter()
+            wi, w = loop()
+            torch.cuda.synchronize()
+            t2 = time.perf_counter()
+            t_mask.append(t1 - t0)
+            t_loop.append(t2 - t1)
+            progress("rep %d: mask search %.3f s, seven-search loop %.3f s" % (r, t1 - t0, t2 - t1))
+    finally:
+        T._smo_masks = real
+    if solver == "device":
+        solve_ms, score_ms = 1e3 * sum(s[1] for s in seen), 1e3 * sum(s[2] for s in seen)
+    else:
+        n_splits = ms.n_splits_
+        solve_ms = 1e3 * float(ms.cv_results_["mean_fit_time"].sum()) * n_splits
+        score_ms = 1e3 * float(ms.cv_results_["mean_score_time"].sum()) * n_splits
+    # the two kernels' own time: HIP events around the calls on resident rows
+    Xd = torch.from_numpy(X).cuda()
+    keys = [(b,) + k for b in range(1, 8) for k in [("linear", None)] + [("rbf", float(g)) for g in GAMMAS]]
+    G, nsq = T.segment_products_device(Xd, segments)
+    seg_ms = event_ms(lambda: T.segment_products_device(Xd, segments), reps)
+    cmp_ms = event_ms(lambda: T.compose_device(G, nsq, keys), reps)
+    # ... beside rml_gram of ONE mask (all columns, the six kernels), what each of the loop's seven searches starts with
+    from radar_ml_amd import _lib
+    kinds = np.array([_lib.GRAM_LINEAR] + [_lib.GRAM_RBF] * len(GAMMAS), dtype=np.int32)
+    gammas = np.array([0.0] + [float(g) for g in GAMMAS], dtype=np.float64)
+    out6 = torch.empty((6, N, N), dtype=torch.float64, device="cuda")
+    one_ms = event_ms(lambda: _lib.check(_lib.load().rml_gram(_lib.context(), _lib.ptr(Xd), Dm, N, Dm, 6, kinds.ctypes.data,
+                                                              gammas.ctypes.data, _lib.ptr(out6), N, N * N, _lib.stream_ptr()),
+                                         "rml_gram"), reps)
+    res = {"rows": N, "segments": list(segments), "D": Dm, "masks": 7, "matrices": len(keys), "solver": solver, "refit_solver": refit,
+           "n_jobs": max(jobs), "reps": reps,
+           "mask_search_s": round(float(np.median(t_mask)), 4), "loop_s": round(float(np.median(t_loop)), 4),
+           "mask_search_s_all": [round(t, 4) for t in t_mask], "loop_s_all": [round(t, 4) for t in t_loop],
+           "gram_segments_ms": round(float(np.median(seg_ms)), 3), "compose_ms": round(float(np.median(cmp_ms)), 3),
+           "gram_segments_ms_all": [round(t, 3) for t in seg_ms], "compose_ms_all": [round(t, 3) for t in cmp_ms],
+           "rml_gram_one_mask_ms": round(float(np.median(one_ms)), 3),
+           "solve_ms": round(solve_ms, 2), "score_ms": round(score_ms, 2), "refit_s": round(ms.refit_time_, 4),
+           "best_proj_mask": list(ms.best_proj_mask_), "best_params": ms.best_params_, "best_score": round(ms.best_score_, 4),
+           "loop_best_proj_mask": list(masks[wi]), "loop_best_params": w.best_params_, "loop_best_score": round(w.best_score_, 4)}
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sets", default="1458,7290", help="training set sizes to run (1458: code grid, 7290: off-grid)")
@@ -189,12 +293,22 @@ def main():
     ap.add_argument("--solver", default="host", choices=["host", "device"], help="where the search's SVC duals are solved")
     ap.add_argument("--refit", default="host", choices=["host", "device"], help="where the winner is refitted (refit_s)")
     ap.add_argument("--sklearn", action="store_true", help="also time scikit-learn's GridSearchCV on the 1458 set (sub-grid)")
+    ap.add_argument("--masks", action="store_true", help="time the projection-mask search against the seven-search loop it replaces")
+    ap.add_argument("--segments", default="3872,5457,682", help="--masks: the xz, yz, xy feature counts of the synthetic rows")
+    ap.add_argument("--reps", type=int, default=5, help="--masks: repeats of each side (medians are reported)")
     args = ap.parse_args()
     import torch
     import radar_ml_amd as rml
     assert torch.cuda.is_available(), "needs a GPU"
     jobs = [int(j) for j in args.jobs.split(",")]
     t_all = time.perf_counter()
+    if args.masks:
+        n = int(args.sets.split(",")[0])
+        out = {"metric": "svc_proj_mask_search", "grid": "7 masks x (5 linear + 25 rbf), 5 folds"}
+        out.update(run_masks(rml, n, tuple(int(v) for v in args.segments.split(",")), jobs, args.solver, args.refit, args.reps, seed=n))
+        out["wall_s"] = round(time.perf_counter() - t_all, 1)
+        print(json.dumps(out))
+        return
     out = {"metric": "svc_grid_search", "grid": "5 linear + 25 rbf, 5 folds", "f64_peak_tflops": F64_PEAK / 1e12, "sets": []}
     keep = None
     for n in [int(s) for s in args.sets.split(",")]:
