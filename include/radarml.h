@@ -126,7 +126,13 @@ int rml_ctx_device(const rml_ctx* ctx);
  *     The entry points themselves always run the kernels: the option is the caller's switch, kept here so that A/B runs share one knob.
  *   RML_OPT_ZOOM_ROWS (default 0): how the workgroups of k_zoom_rows (rml_project_zoom, rml_project_zoom_svm) share a row.  0: one
  *     workgroup per (row, plane) -- the measured choice; 1: one workgroup per row, the float64 images of its planes together in LDS
- *     (where they fit 150 KB); 2: one workgroup per row, one plane after the other.  The rows are the same bits in every mode. */
+ *     (where they fit 150 KB); 2: one workgroup per row, one plane after the other.  The rows are the same bits in every mode.
+ *   RML_OPT_SPARSE_ROWS (default -1): the 128 x 128 int8 GEMM of the fused pipelines stages operand lines (128 bytes of a code row)
+ *     that hold nothing but the background code from one constant line instead of from the row, by the occupancy words the projection's
+ *     code stage and rml_svm_load write.  -1: where the chunk's producer is a wave-per-frame max / sum projection of float32 volumes
+ *     and the grid's z-rows fill whole 128-byte lines (Z a multiple or a divisor of 128: where it was measured to pay); 0: dense
+ *     staging everywhere; 1: wherever the 128 x 128 kernel runs in rml_project_svm, and in place of the split-K kernel of small chunks
+ *     (producers without the code stage get words of all ones).  The same bits either way: the operands that reach the matrix cores are identical. */
 #define RML_OPT_PROJECT_SHARE_CU 1
 #define RML_OPT_WAVEFRAME 2
 #define RML_OPT_LINPLANE 3
@@ -144,6 +150,7 @@ int rml_ctx_device(const rml_ctx* ctx);
 #define RML_OPT_CONV7 13
 #define RML_CONV7_DEFAULT 3
 #define RML_OPT_ZOOM_ROWS 14
+#define RML_OPT_SPARSE_ROWS 15
 int rml_ctx_set_option(rml_ctx* ctx, int option, int value);
 int rml_ctx_get_option(const rml_ctx* ctx, int option, int* value);
 
@@ -176,6 +183,18 @@ int rml_probe_stream(rml_ctx* ctx, const void* buf, int64_t bytes, int reps, dou
  * frame_bytes volume bytes and D codes, 0 for plain stores (the rule and its measurements: csrc/rml_internal.h rml_code_rmw;
  * RML_OPT_CODE_RMW overrides it per context).  Reporting only: bench.py prints it beside the with/without pair. */
 int rml_code_rmw_default(int64_t D, int64_t frame_bytes, int derive, int u8);
+
+/* Test hooks of RML_OPT_SPARSE_ROWS.  Occupancy words: one bit per 128-byte line of a code row, bit k & 31 of dword k >> 5, 1 unless
+ * all 128 bytes are the background code (0x80) and the line lies wholly inside the D codes; ceil(ceil(D / 128) / 32) dwords per row.
+ * rml_svm_sv_occupancy copies the model's words (M rounded up to 128 rows; the added rows are all occupied) to the HOST array `out`
+ * (synchronises).  rml_project_occupancy is rml_project's code-row output (128-byte aligned rows, ld_q a multiple of 128) with the
+ * rows' words into the device array occ[B][occ_words]: from the projection's own code stage where the kernel has one, all ones
+ * elsewhere.  rml_ctx_sparse_gemm_launches: how many sparse GEMM launches the context has issued so far. */
+int rml_svm_sv_occupancy(rml_ctx* ctx, const rml_svm* m, uint32_t* out, int64_t n_words);
+int rml_project_occupancy(rml_ctx* ctx, const void* V, int vdtype, int64_t B, int X, int Y, int Z, int mode, float scale_div,
+                          uint32_t mask, uint8_t* feat_q, int64_t ld_q, int32_t* row_isum, int64_t* row_isq, int32_t* row_flags,
+                          uint32_t* occ, int occ_words, void* stream);
+int64_t rml_ctx_sparse_gemm_launches(const rml_ctx* ctx);
 
 /* Feature-row length for a grid and mask: X*Z + Y*Z + X*Y over the selected planes
  * (train_svc.log:19 "Feature vector length: 10010" at (22,31,176)). */

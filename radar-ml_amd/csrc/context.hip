@@ -167,7 +167,11 @@ extern "C" int rml_ctx_create(int device, rml_ctx** out) {
         e = hipEventCreateWithFlags(&c->ev_proj[i], hipEventDisableTiming);
         if (e == hipSuccess) e = hipEventCreateWithFlags(&c->ev_done[i], hipEventDisableTiming);
     }
+    // the line of background codes the sparse GEMM stager fetches in place of an all-background operand line (mfma_tile.h)
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&c->bg_line), 128);
+    if (e == hipSuccess) e = hipMemset(c->bg_line, 0x80, 128);
     if (e != hipSuccess) {
+        if (c->bg_line) (void)hipFree(c->bg_line);
         delete c;
         return rml_hip_fail(e, "stream/event creation", __FILE__, __LINE__);
     }
@@ -197,6 +201,7 @@ extern "C" int rml_ctx_destroy(rml_ctx* ctx) {
     for (const rml_resize_tab& t : ctx->resize_tabs) (void)hipFree(const_cast<double*>(t.kk));
     for (const rml_pre_tab& t : ctx->pre_tabs) (void)hipFree(t.dev);
     if (ctx->aux_stream) (void)hipStreamDestroy(ctx->aux_stream);
+    if (ctx->bg_line) (void)hipFree(ctx->bg_line);
     delete ctx;
     if (prev >= 0) (void)hipSetDevice(prev);
     return RML_OK;
@@ -295,6 +300,7 @@ static int* opt_slot(rml_opts& o, int option) {
         case RML_OPT_CODE_RMW: return &o.code_rmw;
         case RML_OPT_GEMM_BIG: return &o.gemm_big;
         case RML_OPT_C1_PK: return &o.c1_pk;
+        case RML_OPT_SPARSE_ROWS: return &o.sparse_rows;
         default: return nullptr;
     }
 }
@@ -333,7 +339,7 @@ extern "C" int rml_ctx_set_option(rml_ctx* ctx, int option, int value) {
     RML_REQUIRE(slot != nullptr, RML_ERR_INVALID, "rml_ctx_set_option: unknown option %d", option);
     switch (option) {
         case RML_OPT_WAVEFRAME: RML_REQUIRE(value >= 0 && value <= 3, RML_ERR_INVALID, "rml_ctx_set_option: RML_OPT_WAVEFRAME is 0..3"); *slot = value; break;
-        case RML_OPT_CODE_RMW: case RML_OPT_GEMM_BIG: *slot = value < 0 ? -1 : (value ? 1 : 0); break;
+        case RML_OPT_CODE_RMW: case RML_OPT_GEMM_BIG: case RML_OPT_SPARSE_ROWS: *slot = value < 0 ? -1 : (value ? 1 : 0); break;
         default: *slot = value ? 1 : 0;
     }
     return RML_OK;

@@ -78,6 +78,81 @@ __device__ __forceinline__ void tile_k_loop(const TileStager& sg, unsigned char*
     }
 }
 
+// Staging that honours occupancy words (k_svm_gemm<PATH_I8, PT, false, true> only).  Radar code rows are mostly the background code:
+// about two thirds of the 128-byte lines of a 64x64x128 row hold nothing else (tools/exp/README.md, "sparse code rows").  Every row
+// has one bit per K-step (= one line), packed into `ow` dwords: 1 unless the line is all 0x80 and wholly inside D.  For a clear bit
+// the lane issues the SAME global_load_lds from a 128-byte line of 0x80 that stays in L1 / L2 (rml_ctx::bg_line) instead of from its
+// row: the same bytes reach LDS, so the MFMAs run on identical operands -- every accumulator is bit-identical to the dense stager's --
+// and the instruction count, the LDS addresses, the swizzle and the vmcnt accounting are unchanged; nothing is exec-masked.
+// The eight lanes of a row share its bit.  The words of the tile's 256 rows wait in LDS ([256][ow] dwords behind the epilogue
+// tables, filled once per tile); a lane takes the words of its eight rows from there once per 32 K-steps.  (Words kept in registers
+// one block ahead: hipcc loads them into temporaries and copies them into the loop-carried set behind a vmcnt wait at every block
+// boundary -- a memory latency per 32 steps with the DMA queue drained.)
+constexpr int kSparseMaxWords = 8;                  // ow <= 8 (K <= 32 768 codes): 8 KiB of LDS for the words
+struct SparseStager {
+    const uint8_t* ga[4];
+    const uint8_t* gb[4];
+    const uint8_t* bg;                              // this lane's 16 bytes of the background line (every chunk of it is the same)
+    const uint32_t* la;                             // LDS: the words of the lane's first A row; row q is 8 rows on, B rows 128 rows on
+    uint32_t ca[4], cb[4];                          // the words in use, shifted so that bit 0 is the next step's
+    int wave, ow;
+    // the tile's words into LDS: thread t < 128 owns A row a0 + t, thread t >= 128 B row b0 + t - 128 (clamped like the row itself);
+    // the caller's barrier makes them visible
+    static __device__ __forceinline__ void fill(uint32_t* occ_l, const uint32_t* a_occ, int64_t a0, const uint32_t* b_occ, int64_t b0,
+                                                int64_t b_rows, int ow, int tid) {
+        int64_t gr = b0 + (tid - kTile);
+        gr = gr < b_rows ? gr : b_rows - 1;
+        const uint32_t* src = tid < kTile ? a_occ + (a0 + tid) * ow : b_occ + gr * ow;
+        for (int w = 0; w < ow; ++w) occ_l[tid * ow + w] = src[w];
+    }
+    __device__ __forceinline__ void init(const uint8_t* a, int64_t lda, int64_t a0, const uint8_t* b, int64_t ldb, int64_t b0, int64_t b_rows,
+                                         const uint32_t* occ_l, int ow_, const uint8_t* bg_line, int wave_, int lane) {
+        wave = wave_; ow = ow_;
+        bg = bg_line + (lane & 7) * 16;
+        la = occ_l + (((wave * 4) * 64 + lane) >> 3) * ow;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            ga[q] = stage_src<false>(a, lda, a0, 0, wave, q, lane);
+            gb[q] = stage_src<true>(b, ldb, b0, b_rows, wave, q, lane);
+        }
+    }
+    // the words of K-steps [32 blk, 32 blk + 32)
+    __device__ __forceinline__ void take(int blk) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            ca[q] = la[q * 8 * ow + blk];
+            cb[q] = la[(kTile + q * 8) * ow + blk];
+        }
+    }
+    // stage K-step kt (bit 0 of the words in use) and move on to the next bit
+    __device__ __forceinline__ void stage(unsigned char* smem, int kt, int buf) {
+        unsigned char* base = smem + buf * 2 * kTileBytes;
+        const int64_t ko = (int64_t)kt * kStepBytes;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            glds16((ca[q] & 1u) ? ga[q] + ko : bg, base + (wave * 4 + q) * 1024);
+            glds16((cb[q] & 1u) ? gb[q] + ko : bg, base + kTileBytes + (wave * 4 + q) * 1024);
+            ca[q] >>= 1; cb[q] >>= 1;
+        }
+    }
+};
+
+// tile_k_loop over steps [0, KT) with the sparse stager: the same barriers and the same stage / K-step order
+template <class KStep>
+__device__ __forceinline__ void tile_k_loop_sparse(SparseStager& sg, unsigned char* smem, int KT, KStep kstep) {
+    sg.take(0);
+    sg.stage(smem, 0, 0);
+    for (int kt = 0; kt < KT; ++kt) {
+        __syncthreads();                            // DMA of step kt landed (vmcnt(0)) and visible; step kt-1's buffer is free
+        if (kt + 1 < KT) {
+            if (((kt + 1) & 31) == 0) sg.take((kt + 1) >> 5);      // the next step opens a block of 32
+            sg.stage(smem, kt + 1, (kt + 1) & 1);
+        }
+        const unsigned char* sA = smem + (kt & 1) * 2 * kTileBytes;
+        kstep(sA, sA + kTileBytes);
+    }
+}
+
 // fragment read offsets (bytes within a tile image) of the 32-row MFMAs; lane = row, swizzled chunk; T tiles of 32 rows from row0
 template <int T>
 struct Frag32 {

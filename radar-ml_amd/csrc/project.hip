@@ -404,6 +404,8 @@ void launch_wave(const ProjParams& pp_in, int num_cu, hipStream_t st) {
     pp.stage_bytes = code_stage_bytes(pp, sizeof(VT));
     // `mine` is the kernel's STATIC xy stage; the dynamic part (code stage / pad) may take what is left of the CU's 160 KB
     if (mine + (size_t)4 * pp.stage_bytes > 160 * 1024) pp.stage_bytes = 0;      // no room: direct stores
+    if (!pp.stage_bytes) pp.o.occ = nullptr;            // the occupancy words live in the code stage
+    else if (pp.o.occ && pp.occ_done) *pp.occ_done = 1;
     const size_t stage = (size_t)4 * pp.stage_bytes;
     int per_cu = pp.o.share_cu ? 1 : per_cu_max;
     if (per_cu * (mine + stage) > 160 * 1024) per_cu = 1;      // (measured: one or two of these workgroups per CU stream equally fast)
@@ -686,7 +688,7 @@ int launch_mode(const ProjParams& pp, int num_cu, hipStream_t st, bool* used_fas
 
 void fill_params(ProjParams& pp, const rml_ctx* ctx, const void* V, int64_t B, int X, int Y, int Z, const int32_t* ijk, const ProjOut& o) {
     pp.V = V; pp.B = B; pp.X = X; pp.Y = Y; pp.Z = Z; pp.ZQ = Z / 4; pp.ijk = ijk; pp.tpf = 1; pp.rpl = 1; pp.o = o;
-    pp.ntgt = 1; pp.ijk_out = nullptr; pp.profiles = nullptr; pp.wave_lds = 0; pp.stage_bytes = 0;
+    pp.ntgt = 1; pp.ijk_out = nullptr; pp.profiles = nullptr; pp.wave_lds = 0; pp.stage_bytes = 0; pp.occ_done = nullptr;
     const rml_opts def;
     const rml_opts& op = ctx ? ctx->opt : def;
     pp.k_waveframe = op.waveframe; pp.k_linplane = op.linplane; pp.k_stage_codes = op.stage_codes; pp.k_slice_wave = op.slice_wave;
@@ -715,6 +717,14 @@ int launch_project_t(const ProjParams& pp, int mode, int num_cu, hipStream_t st)
 }
 }  // namespace
 
+namespace {
+// occupancy words of a launch whose kernel has no code stage: every line counts as occupied (always right: the GEMM then fetches it)
+__global__ __launch_bounds__(256) void k_fill_u32(uint32_t* p, int64_t n, uint32_t v) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) p[i] = v;
+}
+}  // namespace
+
 bool rml_project_uses_wave_kernel(const rml_ctx* ctx, int vdtype, int mode, int X, int Y, int Z, bool share_cu, int64_t B) {
     (void)X;
     const int num_cu = ctx ? ctx->num_cu : 256, knob = ctx ? ctx->opt.waveframe : 1;
@@ -729,12 +739,20 @@ int rml_launch_project(rml_ctx* ctx, const void* V, int vdtype, int64_t B, int X
     RML_REQUIRE(vdtype == RML_VOL_F32 || vdtype == RML_VOL_U8, RML_ERR_INVALID, "rml_project: unknown volume dtype %d", vdtype);
     if (mode == RML_MODE_MAX_NAN) mode = RML_MODE_MAX;         // round 6: mode MAX itself has NumPy's NaN policy (the old name stays valid)
     RML_REQUIRE(targets_per_frame == 1 || mode == RML_MODE_SLICE, RML_ERR_INVALID, "rml_project: several targets per frame only in mode SLICE");
+    RML_REQUIRE(!o.occ || (o.qrow && (int64_t)o.occ_words * 32 >= (o.qD + 127) / 128), RML_ERR_INVALID,
+                "rml_project: occupancy words need code rows and a bit per 128-byte line");
     ProjParams pp;
     fill_params(pp, ctx, V, B, X, Y, Z, ijk, o);       // B counts output rows
     pp.tpf = targets_per_frame;
+    int occ_done = 0;
+    pp.occ_done = &occ_done;
     const int num_cu = !ctx ? 256 : ctx->num_cu;
     const int rc = vdtype == RML_VOL_U8 ? launch_project_t<uint8_t>(pp, mode, num_cu, st) : launch_project_t<float>(pp, mode, num_cu, st);
     if (rc) return rc;
+    if (o.occ && !occ_done) {
+        const int64_t n = B * o.occ_words;
+        hipLaunchKernelGGL(k_fill_u32, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, o.occ, n, 0xFFFFFFFFu);
+    }
     RML_HIP(hipGetLastError());
     return RML_OK;
 }
@@ -991,6 +1009,27 @@ static int project_rows(rml_ctx* ctx, const void* V, int vdtype, int64_t B, int 
     o.row_isum = row_isum; o.row_isq = row_isq; o.row_flags = row_flags;
     o.scale_div = scale_div;
     return rml_launch_project(ctx, V, vdtype, B, X, Y, Z, mode, ijk, o, static_cast<hipStream_t>(stream), tpf);
+}
+
+// rml_project's code rows (no float rows) together with their occupancy words
+extern "C" int rml_project_occupancy(rml_ctx* ctx, const void* V, int vdtype, int64_t B, int X, int Y, int Z, int mode, float scale_div,
+                                     uint32_t mask, uint8_t* feat_q, int64_t ld_q, int32_t* row_isum, int64_t* row_isq, int32_t* row_flags,
+                                     uint32_t* occ, int occ_words, void* stream) {
+    RML_REQUIRE(ctx && B >= 0 && X > 0 && Y > 0 && Z > 0, RML_ERR_INVALID, "rml_project_occupancy: bad arguments");
+    if (B == 0) return RML_OK;
+    RML_REQUIRE(V && feat_q && occ, RML_ERR_INVALID, "rml_project_occupancy: NULL argument");
+    RML_REQUIRE(mode == RML_MODE_MAX || mode == RML_MODE_SUM || mode == RML_MODE_MAX_NAN, RML_ERR_INVALID, "rml_project_occupancy: mode MAX or SUM");
+    RML_REQUIRE((mask & RML_MASK_ALL) != 0, RML_ERR_INVALID, "rml_project_occupancy: empty projection mask");
+    RML_REQUIRE(B < (int64_t)1 << 31, RML_ERR_UNSUPPORTED, "rml_project_occupancy: B too large for one launch");
+    const int64_t D = rml_feature_len(X, Y, Z, mask);
+    RML_REQUIRE(ld_q >= D && ld_q % 128 == 0 && (reinterpret_cast<uintptr_t>(feat_q) & 127) == 0, RML_ERR_INVALID,
+                "rml_project_occupancy: code rows need ld_q >= D, ld_q %% 128 == 0 and 128-byte alignment");
+    RML_REQUIRE(occ_words == (int)(((D + 127) / 128 + 31) / 32), RML_ERR_INVALID, "rml_project_occupancy: occ_words must be ceil(ceil(D / 128) / 32)");
+    RML_HIP(hipSetDevice(ctx->device));
+    ProjOut o{};
+    rows_out(o, X, Y, Z, mask, scale_div, nullptr, 0, feat_q, ld_q, row_isum, row_isq, row_flags);
+    o.occ = occ; o.occ_words = occ_words;
+    return rml_launch_project(ctx, V, vdtype, B, X, Y, Z, mode, nullptr, o, static_cast<hipStream_t>(stream));
 }
 
 extern "C" int rml_project_planes(rml_ctx* ctx, const void* V, int vdtype, int64_t B, int X, int Y, int Z, int mode,

@@ -166,6 +166,8 @@ void launch_lin(const ProjParams& pp_in, int num_cu, hipStream_t st) {
     constexpr size_t kMaxLds = 160 * 1024;              // the attribute set below: a CU's whole LDS (as k_derive_slice does)
     const size_t images = (size_t)4 * (NI * 64 * 16 + NI * NGRP * 64 * 4);
     if (images + (size_t)4 * pp.stage_bytes > kMaxLds) pp.stage_bytes = 0;      // no room for the code stage: direct stores
+    if (!pp.stage_bytes) pp.o.occ = nullptr;            // the occupancy words live in the code stage
+    else if (pp.o.occ && pp.occ_done) *pp.occ_done = 1;
     const size_t mine = images + (size_t)4 * pp.stage_bytes;
     int per_cu = pp.o.share_cu ? 1 : 2;
     if (per_cu * mine > 160 * 1024) per_cu = 1;         // (measured: one or two of these workgroups per CU stream equally fast)

@@ -29,6 +29,8 @@ struct ProjParams {
     int stage_bytes;
     // host side only: the context's kernel-family options (rml_opts; fill_params copies them) for the launchers below
     int k_waveframe, k_linplane, k_stage_codes, k_slice_wave, k_derive_fused;
+    // host side only: set to 1 by the launcher of a kernel that writes ProjOut::occ itself (rml_launch_project fills the words otherwise)
+    int* occ_done;
 };
 
 template <int MODE> struct Op;
@@ -101,7 +103,25 @@ struct Emitter {
     lds_u8* stage = nullptr;    // an LDS pointer, and a separate flag: a null test on a generic pointer into LDS does not compile here
     int staged = 0;
     int stage_xy = 0;           // byte offset of the xy codes in the stage
-    __device__ __forceinline__ void set_stage(unsigned char* p, int xy_off) { stage = (lds_u8*)p; staged = 1; stage_xy = xy_off; }
+    // Occupancy words of the frame's code row (ProjOut::occ), gathered in the stage behind the xy codes: a store path that meets a
+    // dword / chunk / byte that is not background ORs the bit of its 128-byte line in (LDS atomics of one wave, ~160 wave instructions
+    // per frame: the yz stores of the frame's end and the flush), flush_wave adds the lines that hold padding, stores the words and
+    // clears them for the next frame.
+    int occ_on = 0;
+    int occ_off = 0;            // byte offset of the words in the stage
+    __device__ __forceinline__ void set_stage(unsigned char* p, int xy_off) {
+        stage = (lds_u8*)p; staged = 1; stage_xy = xy_off;
+        if (a.o.occ) {
+            occ_on = 1; occ_off = xy_off + ((a.X * a.Y + 15) & ~15);
+            for (int w = threadIdx.x & 63; w < a.o.occ_words; w += 64) *(lds_u32*)(stage + occ_off + 4 * w) = 0u;
+        }
+    }
+    // the line of byte `at` of the code row is occupied
+    __device__ __forceinline__ void occ_mark(int at) {
+        const int k = at >> 7;
+        __hip_atomic_fetch_or((lds_u32*)(stage + occ_off + 4 * (k >> 5)), 1u << (k & 31), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+    }
+    __device__ __forceinline__ int plane_at(int pl) const { return (int)(a.o.q[pl] - a.o.qrow); }    // byte offset of plane pl in the code row
 
     __device__ Emitter(const ProjParams& a_, int64_t b_) : a(a_), b(b_) {
         want_stats = a.o.row_isum || a.o.row_isq || a.o.row_flags || a.o.q[0] || a.o.q[1] || a.o.q[2];
@@ -136,7 +156,10 @@ struct Emitter {
             uint32_t c = code(v);
             if (a.o.q[pl]) {
                 if (staged && pl != 1) stage[(pl == 2 ? stage_xy : 0) + idx] = (uint8_t)c;
-                else a.o.q[pl][b * a.o.qstride + idx] = (uint8_t)c;
+                else {
+                    a.o.q[pl][b * a.o.qstride + idx] = (uint8_t)c;
+                    if (occ_on && c != 0x80u) occ_mark(plane_at(pl) + (int)idx);
+                }
             }
         }
     }
@@ -192,6 +215,7 @@ struct Emitter {
                 else {
                     uint32_t* dq = reinterpret_cast<uint32_t*>(a.o.q[pl] + qb() * a.o.qstride + idx);
                     if (!rmw || (have_old ? old : *dq) != packed) *dq = packed;
+                    if (occ_on && packed != 0x80808080u) occ_mark(plane_at(pl) + (int)idx);
                 }
             }
         }
@@ -206,20 +230,43 @@ struct Emitter {
         const int len[2] = {a.X * a.Z, a.X * a.Y};
         lds_u8* src[2] = {stage, stage + stage_xy};
         uint8_t* dst[2] = {a.o.q[0] + qb() * a.o.qstride, a.o.q[2] + qb() * a.o.qstride};
+        const int at[2] = {occ_on ? plane_at(0) : 0, occ_on ? plane_at(2) : 0};
 #pragma unroll
         for (int r = 0; r < 2; ++r) {
             int done = 0;
             if ((reinterpret_cast<uintptr_t>(dst[r]) & 15) == 0) {
                 for (int i = lane; i < (len[r] >> 4); i += 64) {
-                    reinterpret_cast<u32x4*>(dst[r])[i] = ((lds_u128*)src[r])[i];
+                    const u32x4 v = ((lds_u128*)src[r])[i];
+                    reinterpret_cast<u32x4*>(dst[r])[i] = v;
+                    // (a 16-byte chunk at a 16-byte aligned offset of the row lies in one line)
+                    if (occ_on && ((v.x ^ 0x80808080u) | (v.y ^ 0x80808080u) | (v.z ^ 0x80808080u) | (v.w ^ 0x80808080u))) occ_mark(at[r] + 16 * i);
                 }
                 done = len[r] & ~15;
             }
-            for (int i = done + 4 * lane; i + 4 <= len[r]; i += 256)       // rows are 4-byte aligned (rml_project's contract)
-                *reinterpret_cast<uint32_t*>(dst[r] + i) = *(lds_u32*)(src[r] + i);
-            for (int i = (len[r] & ~3) + lane; i < len[r]; i += 64) dst[r][i] = src[r][i];
+            for (int i = done + 4 * lane; i + 4 <= len[r]; i += 256) {     // rows are 4-byte aligned (rml_project's contract)
+                const uint32_t v = *(lds_u32*)(src[r] + i);
+                *reinterpret_cast<uint32_t*>(dst[r] + i) = v;
+                if (occ_on && v != 0x80808080u) occ_mark(at[r] + i);
+            }
+            for (int i = (len[r] & ~3) + lane; i < len[r]; i += 64) {
+                const uint8_t v = src[r][i];
+                dst[r][i] = v;
+                if (occ_on && v != 0x80u) occ_mark(at[r] + i);
+            }
         }
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        if (occ_on) {
+            // a line that is not wholly inside the row's qD codes holds padding (0x00): always occupied
+            const int kpad = (int)(a.o.qD >> 7);
+            for (int w = lane; w < a.o.occ_words; w += 64) {
+                lds_u32* lw = (lds_u32*)(stage + occ_off + 4 * w);
+                uint32_t v = *lw;
+                if ((a.o.qD & 127) && (kpad >> 5) == w) v |= 1u << (kpad & 31);
+                a.o.occ[qb() * a.o.occ_words + w] = v;
+                *lw = 0u;
+            }
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        }
     }
     // the same as finish() for kernels in which ONE WAVE owns the frame: no LDS, no barrier
     __device__ void finish_wave(int lane) {
@@ -360,7 +407,7 @@ inline int code_stage_bytes(const ProjParams& pp, size_t voxel_bytes) {
     const ProjOut& o = pp.o;
     if (voxel_bytes != 4 || o.p[0] || o.p[1] || o.p[2] || o.row_nsq || !o.q[0] || !o.q[2] || o.skip_if_set) return 0;
     if (!pp.k_stage_codes) return 0;
-    const int bytes = ((pp.X * pp.Z + 15) & ~15) + ((pp.X * pp.Y + 15) & ~15);
+    const int bytes = ((pp.X * pp.Z + 15) & ~15) + ((pp.X * pp.Y + 15) & ~15) + (o.occ ? (4 * o.occ_words + 15) & ~15 : 0);
     return bytes <= 16 * 1024 ? bytes : 0;
 }
 

@@ -40,6 +40,7 @@ struct rml_opts {
     int smo_lds_rows = RML_SMO_LDS_ROWS_MAX;   // RML_OPT_SMO_LDS_ROWS: duals of more rows run on the workspace variant of k_smo
     int conv7 = RML_CONV7_DEFAULT;  // RML_OPT_CONV7: bit 0 forward, bit 1 backward of the generator's output layer on csrc/gen.hip
     int sgd_resident_d = RML_SGD_RESIDENT_D_MAX;   // RML_OPT_SGD_RESIDENT_D: wider problems run on the workspace variant of k_sgd
+    int sparse_rows = -1;       // RML_OPT_SPARSE_ROWS: -1 = the measured grid rule (rml_sparse_rows), 0 dense, 1 wherever occupancy words can be had (also in place of split-K)
     int zoom_rows = 0;          // RML_OPT_ZOOM_ROWS: k_zoom_rows 0 = one workgroup per (row, plane), 1 / 2 one per row: planes together / in turn
 };
 
@@ -59,6 +60,8 @@ struct rml_ctx {
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     hipEvent_t ev_proj[2] = {nullptr, nullptr}, ev_done[2] = {nullptr, nullptr};   // chunk pipeline of rml_project_svm (two workspaces)
     hipStream_t aux_stream = nullptr;   // second stream for overlapping GEMM with projection
+    mutable int64_t sparse_gemm_launches = 0;   // launches of k_svm_gemm<I8, PT, false, true> issued so far (rml_ctx_sparse_gemm_launches: the tests' witness)
+    uint8_t* bg_line = nullptr;         // 128 bytes of 0x80 (a line of background codes): what the sparse GEMM stager fetches for a clear occupancy bit
     // optional in-situ timing of the projection launches issued by rml_project_svm
     bool profiling = false;
     std::vector<hipEvent_t> prof_ev;    // start/stop pairs
@@ -187,6 +190,12 @@ struct ProjOut {
     // of the fused pipelines, a caller's code buffer), so most of a row's HBM WRITE traffic -- what the streaming kernels pay
     // 3-15 % for, DESIGN.md 3.1b' -- becomes reads.  The kernels put the old words of a region in flight together (Emitter::old_word).
     int q_rmw;
+    // Occupancy words of the code rows (the int8 GEMM's sparse stager, mfma_tile.h): row b has one bit per 128-byte line of its code
+    // row at occ + b * occ_words (bit k & 31 of word k >> 5), 1 unless all 128 bytes are the background code (0x80) and the line
+    // lies wholly inside qD.  NULL: none wanted.  Written by the wave-per-frame kernels with the code stage (Emitter::flush_wave);
+    // a launch of any other kernel fills the words with ones (rml_launch_project), which is always right.
+    uint32_t* occ;
+    int occ_words;
 };
 // rml_code_rmw: the default of ProjOut::q_rmw in the fused pipelines, for frames of frame_bytes volume bytes and D codes.  The
 // read-back costs its bytes (and, in a per-frame epilogue, its latency) whatever the rows hold; the stores it saves depend on the
@@ -209,6 +218,16 @@ inline int rml_code_rmw(int64_t D, int64_t frame_bytes, bool derive, bool u8) {
     // 2 % bar: the derive pipelines store plainly
     if (derive) return 0;
     return u8 && D * 64 >= frame_bytes && D * 16 <= frame_bytes;
+}
+
+// rml_sparse_rows: the default of RML_OPT_SPARSE_ROWS (-1) for a grid.  What was measured (same library, option 0 against -1, three
+// interleaved rounds of the fused float32 pipeline on one box, tools/exp/README.md): 64x64x128 -- 69 % of the sample lines and 63 %
+// of the SV lines are background -- 22.45 / 22.81 / 22.85 -> 21.77 / 21.49 / 21.47 ms per 65 536 frames (+3 ... +6 %); the Walabot
+// grid 22x31x176 -- 45 % / 37 %, rows of 176 codes that straddle the 128-byte lines -- 12.45 / 13.11 / 12.28 -> 12.85 / 12.71 /
+// 12.72 ms (-3 / +3 / -3.5 %: no gain).  So: on where a line is a whole number of z-rows (or a whole fraction of one) and every
+// plane starts on a line -- background then comes in whole lines --, off elsewhere.
+inline int rml_sparse_rows(int X, int Y, int Z) {
+    return (Z % 128 == 0 || 128 % Z == 0) && ((int64_t)X * Z) % 128 == 0 && ((int64_t)Y * Z) % 128 == 0;
 }
 
 // true when rml_launch_project would use the persistent wave-per-frame kernel for this shape (the fused pipeline then
@@ -284,6 +303,8 @@ struct rml_svm {
     int8_t* sv_dig = nullptr;     // 4 x Mpad x Dq
     double* sv_dig_nsq = nullptr; // Mpad  ||u_sv||^2 of the quantised values
     uint32_t mask_hint = 0;
+    uint32_t* sv_occ = nullptr;   // Mpad x occ_words occupancy words of sv_q (ProjOut::occ's rule; rows M..Mpad hold 0x00: occupied)
+    int occ_words = 0;            // (Kq / 128 + 31) / 32
 };
 
 // host-side packed operands of a model (rml_svm_pack_host fills them, rml_svm_load uploads them)
@@ -292,6 +313,7 @@ struct rml_svm_pack {
     std::vector<float> svf;
     std::vector<uint8_t> svq;
     std::vector<int8_t> svd;
+    std::vector<uint32_t> occ;
 };
 int rml_svm_pack_host(const double* sv, int64_t M, int64_t D, const double* dual_coef, const int32_t* n_support,
                       int n_classes, int kernel, double gamma, double code_scale, bool has_calib, rml_svm* m, rml_svm_pack* pk);

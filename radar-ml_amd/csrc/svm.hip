@@ -106,12 +106,14 @@ struct ChunkWs {
     int32_t* ijk;                                                       // derived (i,j,k) of the chunk's frames (fused derive -> slice), or NULL
     int32_t* gsmall;                                                    // [RML_SMALL_FRAMES][Mpad] dot products of the single-observation path
     int32_t* gsplit;                                                    // [Mpad][CH] of the split-K path (chunks of at most kSplitRows rows), or NULL
+    uint32_t* occ;                                                      // [CH][occ_words] occupancy words of the code rows (ProjOut::occ), or NULL
     size_t bytes;
 };
 
 // what an entry point wants in a chunk workspace beside statistics, tile predicate and partial sums: code rows (+ the scratch of the
-// small / split-K kernels), float rows, their digit planes (+ the ring kernel's scratch tiles), derived (i,j,k) per frame
-struct ChunkNeeds { bool q, f32, dig, ijk; };
+// small / split-K kernels), float rows, their digit planes (+ the ring kernel's scratch tiles), derived (i,j,k) per frame, occupancy
+// words of the code rows
+struct ChunkNeeds { bool q, f32, dig, ijk, occ; };
 constexpr int64_t kSplitRows = 2048;        // the split-K path serves chunks of at most this many rows
 
 // base == NULL: the size only (every pointer NULL).  A part that is not needed takes no bytes and is NULL.
@@ -131,6 +133,7 @@ ChunkWs carve(const rml_svm* m, int64_t CH, unsigned char* base, const ChunkNeed
     w.ijk = (int32_t*)take(need.ijk ? (size_t)CH * 12 : 0);
     w.gsmall = (int32_t*)take(need.q ? (size_t)RML_SMALL_FRAMES * m->Mpad * 4 : 0);
     w.gsplit = (int32_t*)take(need.q && CH <= kSplitRows ? (size_t)m->Mpad * CH * 4 : 0);
+    w.occ = (uint32_t*)take(need.q && need.occ ? (size_t)CH * m->occ_words * 4 : 0);
     w.bytes = off;
     return w;
 }
@@ -157,8 +160,10 @@ struct DecisionOut {
 
 // The n rows of one chunk, already in place: code rows + their statistics (q NULL: none), per row "on the code grid?" (NULL: not
 // known per row), float rows of stride m->Df + squared norms (f32 NULL: none).  ws_rows: the first n rows of a chunk workspace.
-struct ChunkOps { int64_t n; const uint8_t* q; int64_t ld_q; const int32_t* isum; const int64_t* isq; const int32_t* flags; const float* f32; const double* nsq; };
-ChunkOps ws_rows(const rml_svm* m, const ChunkWs& w, int64_t n) { return ChunkOps{n, w.q, m->Dq, w.isum, w.isq, w.flags, w.f32, w.nsq}; }
+// occ: the occupancy words of the code rows (m->occ_words per row) when the chunk's producer wrote them, else NULL.
+struct ChunkOps { int64_t n; const uint8_t* q; int64_t ld_q; const int32_t* isum; const int64_t* isq; const int32_t* flags; const float* f32; const double* nsq;
+                  const uint32_t* occ; };
+ChunkOps ws_rows(const rml_svm* m, const ChunkWs& w, int64_t n) { return ChunkOps{n, w.q, m->Dq, w.isum, w.isq, w.flags, w.f32, w.nsq, nullptr}; }
 
 // What to do with a chunk.  The entry point fills the first group (a ChunkPlan{} asks for nothing: set what is meant, by name);
 // plan_chunk derives the second from it, and is the only place that does.
@@ -169,7 +174,7 @@ struct ChunkPlan {
     bool allow_big;         // the 256x256 ring kernel may take the exact tiles (not beside a persistent projection: it fills a CU)
     bool dig_ready;         // the digit planes of the float rows are in w.dig
     double* kmat; int64_t ld_k;     // kernel values K[n][m] of the chunk's rows instead of decisions (rml_svm_kernel_matrix), or NULL
-    int FT, ST, group; bool run_i8, run_gen, gen_f32, big, run_dig, small, split;      // derived: see plan_chunk
+    int FT, ST, group; bool run_i8, run_gen, gen_f32, big, run_dig, small, split, sparse;      // derived: see plan_chunk
 };
 
 // No allocation, no lock, no HIP call: run_chunk is entered with a const ctx and from inside a stream capture.
@@ -187,6 +192,14 @@ ChunkPlan plan_chunk(const rml_ctx* ctx, const rml_svm* m, ChunkPlan p, const Ch
     // ... and batches whose 128 x 128 tiles are fewer than the CUs: the same tiles cut along K (exact: any order)
     p.split = p.run_i8 && !p.kmat && !p.small && !p.big && w.gsplit && x.n <= kSplitRows && (int64_t)p.FT * p.ST < ctx->num_cu &&
               m->Kq / kStepBytes >= 8;
+    // the 128 x 128 kernel stages all-background lines from the context's constant line when the chunk's producer wrote occupancy
+    // words (the model's come from rml_svm_load).  The ring, split-K and small kernels, the kernel matrix and the float paths are dense.
+    // Forced (RML_OPT_SPARSE_ROWS = 1) it also takes the chunks split-K would: the same bits (both are exact), and the tests reach it
+    // with a few hundred rows.
+    const bool can_sparse = p.run_i8 && !p.kmat && !p.small && !p.big && x.occ && m->sv_occ && ctx->bg_line && ctx->opt.sparse_rows != 0 &&
+                            m->occ_words <= kSparseMaxWords;
+    if (can_sparse && ctx->opt.sparse_rows > 0) p.split = false;
+    p.sparse = can_sparse && !p.split;
     return p;
 }
 
@@ -297,7 +310,11 @@ int run_chunk(const rml_ctx* ctx, const rml_svm* m, const ChunkOps& x, const Chu
         else if (p.small) rc = launch_small(m, ga, w.gsmall, st);
         else if (p.split) rc = launch_split(m, ga, w.gsplit, ctx->num_cu, st);
         else if (p.big) rc = launch_gemm_big(m, ga, st);
-        else rc = launch_gemm<PATH_I8>(m, ga, st);
+        else if (p.sparse) {
+            ga.sv_occ = m->sv_occ; ga.x_occ = x.occ; ga.ow = m->occ_words; ga.bg_line = ctx->bg_line;
+            ++ctx->sparse_gemm_launches;
+            rc = launch_gemm<PATH_I8, false, true>(m, ga, st);
+        } else rc = launch_gemm<PATH_I8>(m, ga, st);
         if (rc) return rc;
     }
     if (p.run_dig && (rc = launch_gemm_ring<1>(m, digit_args(m, x, p, w), st))) return rc;
@@ -383,6 +400,17 @@ int rml_svm_pack_host(const double* sv, int64_t M, int64_t D, const double* dual
         // linear: x.s = G' + 128 isum_x + [128 isum_s - 16384 D]
         term[r] = (kernel == RML_KERNEL_RBF) ? (double)(isq - 256 * isum + 32768 * D) : (double)(128 * isum - 16384 * D);
     }
+    // occupancy words of the code rows (ProjOut::occ's rule): a line is clear when all of its 128 bytes are the background code 0x80
+    // and it lies wholly inside D.  Rows M .. Mpad hold 0x00 (int8 0, not the background code) and stay occupied.
+    m->occ_words = (int)((m->Kq / kStepBytes + 31) / 32);
+    std::vector<uint32_t>& occ = pk->occ;
+    occ.assign((size_t)m->Mpad * m->occ_words, 0u);
+    for (int64_t r = 0; r < m->Mpad; ++r)
+        for (int64_t k = 0; k < m->Kq / kStepBytes; ++k) {
+            bool bg = r < M && (k + 1) * kStepBytes <= D;
+            for (int t = 0; bg && t < kStepBytes; ++t) bg = svq[(size_t)r * m->Dq + k * kStepBytes + t] == 0x80;
+            if (!bg) occ[(size_t)r * m->occ_words + (k >> 5)] |= 1u << (k & 31);
+        }
     // the int8 MFMA accumulates sum (a-128)(b-128) in int32: |.| <= 128^2 * K must stay below 2^31
     if (m->Kq >= 131072) exact = false;
     m->exact = exact;
@@ -452,6 +480,7 @@ extern "C" int rml_svm_load(rml_ctx* ctx, const double* sv, int64_t M, int64_t D
         if (exact) {
             if ((rc = dev_upload(&m->sv_q, pk.svq))) break;
             if ((rc = dev_upload(&m->sv_term_q, pk.term))) break;
+            if ((rc = dev_upload(&m->sv_occ, pk.occ))) break;
         }
         if (m->dig_ok) {
             if ((rc = dev_upload(&m->sv_dig, pk.svd))) break;
@@ -475,19 +504,30 @@ extern "C" int rml_svm_free(rml_ctx* ctx, rml_svm* m) {
     if (!m) return RML_OK;
     if (ctx) (void)hipSetDevice(ctx->device);
     (void)hipDeviceSynchronize();
-    void* bufs[] = {m->sv_f32, m->sv_nsq, m->sv_q, m->sv_term_q, m->W, m->intercept, m->calib, m->platt, m->sv_dig, m->sv_dig_nsq};
+    void* bufs[] = {m->sv_f32, m->sv_nsq, m->sv_q, m->sv_term_q, m->W, m->intercept, m->calib, m->platt, m->sv_dig, m->sv_dig_nsq, m->sv_occ};
     for (void* b : bufs) if (b) (void)hipFree(b);
     delete m;
     return RML_OK;
 }
 
+extern "C" int rml_svm_sv_occupancy(rml_ctx* ctx, const rml_svm* m, uint32_t* out, int64_t n_words) {
+    RML_REQUIRE(ctx && m && out, RML_ERR_INVALID, "rml_svm_sv_occupancy: NULL argument");
+    RML_REQUIRE(m->sv_occ != nullptr, RML_ERR_STATE, "rml_svm_sv_occupancy: the model is not on the code grid");
+    RML_REQUIRE(n_words == m->Mpad * m->occ_words, RML_ERR_INVALID, "rml_svm_sv_occupancy: out holds %lld words, the model has %lld",
+                (long long)n_words, (long long)(m->Mpad * m->occ_words));
+    RML_HIP(hipSetDevice(ctx->device));
+    RML_HIP(hipMemcpy(out, m->sv_occ, (size_t)n_words * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return RML_OK;
+}
+extern "C" int64_t rml_ctx_sparse_gemm_launches(const rml_ctx* ctx) { return ctx ? ctx->sparse_gemm_launches : 0; }
 extern "C" int rml_svm_is_exact(const rml_svm* m) { return m && m->exact ? 1 : 0; }
 extern "C" int64_t rml_svm_num_sv(const rml_svm* m) { return m ? m->M : 0; }
 extern "C" int64_t rml_svm_dim(const rml_svm* m) { return m ? m->D : 0; }
 
-// the size of one chunk workspace (tools/sanitize pins the layout with it).  needs: bit 0 code rows, 1 float rows, 2 digit planes, 3 ijk
+// the size of one chunk workspace (tools/sanitize pins the layout with it).  needs: bit 0 code rows, 1 float rows, 2 digit planes, 3 ijk,
+// 4 occupancy words
 size_t rml_svm_ws_bytes(const rml_svm* m, int64_t CH, unsigned needs) {
-    return carve(m, CH, nullptr, ChunkNeeds{(needs & 1u) != 0, (needs & 2u) != 0, (needs & 4u) != 0, (needs & 8u) != 0}).bytes;
+    return carve(m, CH, nullptr, ChunkNeeds{(needs & 1u) != 0, (needs & 2u) != 0, (needs & 4u) != 0, (needs & 8u) != 0, (needs & 16u) != 0}).bytes;
 }
 
 // ---- decision on caller-provided rows -----------------------------------------------------
@@ -588,6 +628,7 @@ struct FrontCall {
     float scale_div; uint32_t mask; DecisionOut out;
     bool grid_ok;           // the code grid of the features is the model's: codes are the unscaled values
     int share_cu, q_rmw;    // ProjOut's: a GEMM runs beside the projections; read-compare-write of the code rows
+    bool occ;               // the first projection pass also writes occupancy words (ChunkWs::occ) and the GEMM stage hands them on
     bool use_dig; ChunkPlan plan;   // rows off the code grid go to the multi-digit int8 kernel; the plan of every chunk
     bool u8() const { return vdtype == RML_VOL_U8; }
     int64_t frame_bytes() const { return (int64_t)X * Y * Z * (u8() ? 1 : 4); }
@@ -603,6 +644,7 @@ ProjOut code_rows_out(const FrontCall& f, const ChunkWs& w) {
     o.qstride = f.m->Dq; o.qrow = w.q; o.qD = f.m->D;
     o.row_isum = w.isum; o.row_isq = w.isq; o.row_flags = f.u8() ? nullptr : w.flags; o.scale_div = f.scale_div;
     o.share_cu = f.share_cu; o.q_rmw = f.q_rmw;
+    if (f.occ && w.occ) { o.occ = w.occ; o.occ_words = f.m->occ_words; }
     return o;
 }
 // projection pass 2: float rows + norms, for the rows that left the code grid (or for a model that is not on it)
@@ -669,7 +711,9 @@ int caller_stage(const FrontCall& f, const FrontChunk& ck, const ProjOut& po) {
 int gemm_stage(const FrontCall& f, const FrontChunk& ck) {
     hipStream_t aux = f.ctx->aux_stream;
     rml_prof_mark_gemm(f.ctx, aux);
-    const int rc = run_chunk(f.ctx, f.m, ws_rows(f.m, ck.w, ck.n), f.plan, ck.w, f.out.at(ck.r0, f.m->C, f.m->P), aux);
+    ChunkOps x = ws_rows(f.m, ck.w, ck.n);
+    if (f.occ) x.occ = ck.w.occ;
+    const int rc = run_chunk(f.ctx, f.m, x, f.plan, ck.w, f.out.at(ck.r0, f.m->C, f.m->P), aux);
     rml_prof_mark_gemm(f.ctx, aux);
     if (f.ctx->profiling) f.ctx->prof_ops_g += 2.0 * (double)ck.n * (double)f.m->M * (double)f.m->D;
     return rc;
@@ -754,7 +798,13 @@ int front_chunked(FrontCall f) {
                        : f.use_dig               ? pick_chunk(ctx, m, f.B, 8192, f.use_dig)
                                                  : std::min<int64_t>(round_up(f.B, kTile), f.grid_ok ? pick_chunk_opt(ctx, small_chunk) : 8192);
     ChunkNeeds need{};
-    need.q = f.grid_ok; need.f32 = true; need.dig = f.use_dig; need.ijk = f.derive && !f.ijk_out;     // the derived (i,j,k) stay in the chunk's workspace when the caller does not want them
+    // Occupancy words (RML_OPT_SPARSE_ROWS): by default where the first pass is a wave-per-frame max / sum projection of float32
+    // volumes, whose code stage writes them (Emitter::flush_wave), the 128 x 128 GEMM runs beside it and the grid is one where it
+    // was measured to pay (rml_sparse_rows); forced (1): for every chunk the 128 x 128 kernel may take (a producer without the
+    // code stage gets words of all ones: rml_launch_project).  The derive / slice emitters and the byte-native kernel never write them.
+    f.occ = f.grid_ok && !f.derive && f.mode != RML_MODE_SLICE && ctx->opt.sparse_rows != 0 &&
+            (ctx->opt.sparse_rows > 0 || (wave_proj && !f.u8() && rml_sparse_rows(f.X, f.Y, f.Z)));
+    need.q = f.grid_ok; need.f32 = true; need.dig = f.use_dig; need.ijk = f.derive && !f.ijk_out; need.occ = f.occ;     // the derived (i,j,k) stay in the chunk's workspace when the caller does not want them
     // workspaces in rotation: 2 (projection of chunk c+1 beside the GEMM of chunk c; a third one -- the projection two chunks
     // ahead -- changed nothing at 64x64x128 and cost 2 % at the Walabot grid: DESIGN.md 3.3)
     // (Three streams -- the small kernels either side of a chunk's GEMM on a third one, RML_PIPE_SPLIT in rounds 3-4 -- were

@@ -68,10 +68,14 @@ struct GemmArgs {
     double* partial; int64_t Npart;        // ST x Npart x PT
     double* kmat; int64_t ld_k; int64_t M; // KM instantiations: kernel values K[n][m] for m < M (rml_svm_kernel_matrix)
     int64_t sv_rows;                       // SV rows that exist in memory (Mpad); the 256-row kernel clamps to it
+    // SPARSE instantiation (mfma_tile.h SparseStager): occupancy words of the SV rows and of the sample rows, `ow` dwords per row, and
+    // the context's line of background codes
+    const uint32_t* sv_occ; const uint32_t* x_occ; int ow; const uint8_t* bg_line;
 };
 
-template <int PATH, int PT, bool KM = false>
+template <int PATH, int PT, bool KM = false, bool SPARSE = false>
 __global__ __launch_bounds__(256, 2) void k_svm_gemm(GemmArgs a) {
+    static_assert(!SPARSE || (PATH == PATH_I8 && !KM), "occupancy words exist for code rows only");
     extern __shared__ __align__(16) unsigned char smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wr = wave >> 1, wc = wave & 1;
@@ -217,15 +221,25 @@ __global__ __launch_bounds__(256, 2) void k_svm_gemm(GemmArgs a) {
     } else {
         // accumulators: 2x2 tiles of 32x32 (16 regs each)
         using acc_t = typename std::conditional<PATH == PATH_I8, v16i, v16f>::type;
-        TileStager sg;
-        sg.init<true>(a.sv, a.ld_sv, m0, a.x, a.ld_x, f0, a.N, wave, lane);
         Frag32<2> fa, fb;
         fa.init(wr * 64, lane); fb.init(wc * 64, lane);
         const int chalf = lane >> 5;
         acc_t acc[2][2];
         zero_acc(acc);
         auto ks32 = [&](const unsigned char* sA, const unsigned char* sB) { kstep_32<PATH>(acc, sA, sB, fa, fb, chalf); };
-        tile_k_loop(sg, smem, 0, a.KT, ks32);
+        if constexpr (SPARSE) {
+            // the tile's occupancy words behind the epilogue tables (launch_gemm asks for the bytes)
+            uint32_t* occ_l = reinterpret_cast<uint32_t*>(smem + 4 * kTileBytes + kTile * (1 + PT) * sizeof(double) + kExpTabBytes);
+            SparseStager::fill(occ_l, a.sv_occ, m0, a.x_occ, f0, a.N, a.ow, tid);
+            __syncthreads();
+            SparseStager sg;
+            sg.init(a.sv, a.ld_sv, m0, a.x, a.ld_x, f0, a.N, occ_l, a.ow, a.bg_line, wave, lane);
+            tile_k_loop_sparse(sg, smem, a.KT, ks32);
+        } else {
+            TileStager sg;
+            sg.init<true>(a.sv, a.ld_sv, m0, a.x, a.ld_x, f0, a.N, wave, lane);
+            tile_k_loop(sg, smem, 0, a.KT, ks32);
+        }
 
         const bool rbf = (a.kernel == RML_KERNEL_RBF);
         // ---- fused float64 epilogue ----------------------------------------------------------
@@ -335,15 +349,15 @@ __global__ __launch_bounds__(256, 2) void k_svm_gemm_splitk(SplitArgs a) {
             }
 }
 
-template <int PATH, bool KM = false>
+template <int PATH, bool KM = false, bool SPARSE = false>
 int launch_gemm(const rml_svm* m, const GemmArgs& ga, hipStream_t st) {
-    const size_t lds = 4 * kTileBytes + (size_t)kTile * (1 + m->PT) * sizeof(double) + kExpTabBytes;
+    const size_t lds = 4 * kTileBytes + (size_t)kTile * (1 + m->PT) * sizeof(double) + kExpTabBytes + (SPARSE ? (size_t)2 * kTile * ga.ow * 4 : 0);
     const int FT8 = (ga.FT + 7) / 8 * 8;
     dim3 grid((unsigned)(FT8 * ga.ST)), block(256);
 #define RML_GEMM_CASE(PTV)                                                                                         \
     case PTV: {                                                                                                    \
-        RML_MAX_DYN_LDS(144 * 1024, &k_svm_gemm<PATH, PTV, KM>);                                                   \
-        hipLaunchKernelGGL((k_svm_gemm<PATH, PTV, KM>), grid, block, lds, st, ga);                                 \
+        RML_MAX_DYN_LDS(144 * 1024, &k_svm_gemm<PATH, PTV, KM, SPARSE>);                                           \
+        hipLaunchKernelGGL((k_svm_gemm<PATH, PTV, KM, SPARSE>), grid, block, lds, st, ga);                         \
     } break;
     switch (m->PT) {
         RML_GEMM_CASE(1)
