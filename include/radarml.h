@@ -132,7 +132,13 @@ int rml_ctx_device(const rml_ctx* ctx);
  *     code stage and rml_svm_load write.  -1: where the chunk's producer is a wave-per-frame max / sum projection of float32 volumes
  *     and the grid's z-rows fill whole 128-byte lines (Z a multiple or a divisor of 128: where it was measured to pay); 0: dense
  *     staging everywhere; 1: wherever the 128 x 128 kernel runs in rml_project_svm, and in place of the split-K kernel of small chunks
- *     (producers without the code stage get words of all ones).  The same bits either way: the operands that reach the matrix cores are identical. */
+ *     (producers without the code stage get words of all ones).  The same bits either way: the operands that reach the matrix cores are identical.
+ *   RML_OPT_SPARSE_STORES (default -1): the projection in front of a chunk whose int8 GEMM is the sparse kernel does not store the
+ *     lines of a code row whose occupancy bit stays clear -- the GEMM never fetches them -- where the kernel writes the words itself
+ *     and the line is a whole line of one plane (a set bit's line is always fully stored; the line that holds padding always is).
+ *     Decided chunk by chunk: a chunk that takes the split-K, small, ring or float kernels keeps whole rows.  -1: where
+ *     RML_OPT_SPARSE_ROWS' grid rule holds and the stores were measured to cost (csrc/rml_internal.h rml_sparse_stores); 0: whole
+ *     rows everywhere; 1: wherever the chunk's plan is sparse and the kernel can skip.  The same bits either way. */
 #define RML_OPT_PROJECT_SHARE_CU 1
 #define RML_OPT_WAVEFRAME 2
 #define RML_OPT_LINPLANE 3
@@ -151,6 +157,7 @@ int rml_ctx_device(const rml_ctx* ctx);
 #define RML_CONV7_DEFAULT 3
 #define RML_OPT_ZOOM_ROWS 14
 #define RML_OPT_SPARSE_ROWS 15
+#define RML_OPT_SPARSE_STORES 16
 int rml_ctx_set_option(rml_ctx* ctx, int option, int value);
 int rml_ctx_get_option(const rml_ctx* ctx, int option, int* value);
 
@@ -189,12 +196,20 @@ int rml_code_rmw_default(int64_t D, int64_t frame_bytes, int derive, int u8);
  * rml_svm_sv_occupancy copies the model's words (M rounded up to 128 rows; the added rows are all occupied) to the HOST array `out`
  * (synchronises).  rml_project_occupancy is rml_project's code-row output (128-byte aligned rows, ld_q a multiple of 128) with the
  * rows' words into the device array occ[B][occ_words]: from the projection's own code stage where the kernel has one, all ones
- * elsewhere.  rml_ctx_sparse_gemm_launches: how many sparse GEMM launches the context has issued so far. */
+ * elsewhere.  rml_project_sparse_rows is the same launch with RML_OPT_SPARSE_STORES' producer side (skip_clear != 0): a line whose
+ * bit stays clear is left as feat_q held it where the kernel can skip it, every set bit's line is stored in full.
+ * rml_ctx_sparse_gemm_launches: how many sparse GEMM launches the context has issued so far. */
 int rml_svm_sv_occupancy(rml_ctx* ctx, const rml_svm* m, uint32_t* out, int64_t n_words);
 int rml_project_occupancy(rml_ctx* ctx, const void* V, int vdtype, int64_t B, int X, int Y, int Z, int mode, float scale_div,
                           uint32_t mask, uint8_t* feat_q, int64_t ld_q, int32_t* row_isum, int64_t* row_isq, int32_t* row_flags,
                           uint32_t* occ, int occ_words, void* stream);
+int rml_project_sparse_rows(rml_ctx* ctx, const void* V, int vdtype, int64_t B, int X, int Y, int Z, int mode, float scale_div,
+                            uint32_t mask, uint8_t* feat_q, int64_t ld_q, int32_t* row_isum, int64_t* row_isq, int32_t* row_flags,
+                            uint32_t* occ, int occ_words, int skip_clear, void* stream);
 int64_t rml_ctx_sparse_gemm_launches(const rml_ctx* ctx);
+/* how many projection launches the context has issued with skip_clear set on a kernel that writes its own occupancy words (and
+ * therefore leaves clear lines unstored): the witness of RML_OPT_SPARSE_STORES' producer side */
+int64_t rml_ctx_sparse_store_launches(const rml_ctx* ctx);
 
 /* Feature-row length for a grid and mask: X*Z + Y*Z + X*Y over the selected planes
  * (train_svc.log:19 "Feature vector length: 10010" at (22,31,176)). */

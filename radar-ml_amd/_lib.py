@@ -190,9 +190,12 @@ SIGNATURES = {
                                   c_void_p, c_void_p]),
     "rml_code_rmw_default": (c_int, [c_int64, c_int64, c_int, c_int]),
     "rml_ctx_sparse_gemm_launches": (c_int64, [c_void_p]),
+    "rml_ctx_sparse_store_launches": (c_int64, [c_void_p]),
     "rml_svm_sv_occupancy": (c_int, [c_void_p, c_void_p, c_void_p, c_int64]),
     "rml_project_occupancy": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_int, c_int, c_float, c_uint32, c_void_p, c_int64,
                                       c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
+    "rml_project_sparse_rows": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_int, c_int, c_float, c_uint32, c_void_p, c_int64,
+                                        c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
     "rml_probe_stream": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p]),
     "rml_synth_volumes": (c_int, [c_void_p, c_uint64, c_int64, c_int64, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
                                   c_void_p]),
@@ -200,7 +203,7 @@ SIGNATURES = {
 
 MODE_MAX, MODE_SLICE, MODE_SUM, MODE_MAX_NAN = 0, 1, 2, 3
 # rml_ctx_set_option ids (include/radarml.h RML_OPT_*)
-OPT_PROJECT_SHARE_CU, OPT_WAVEFRAME, OPT_LINPLANE, OPT_STAGE_CODES, OPT_SLICE_WAVE, OPT_DERIVE_FUSED, OPT_CODE_RMW, OPT_GEMM_BIG, OPT_CHUNK, OPT_C1_PK, OPT_SMO_LDS_ROWS, OPT_SGD_RESIDENT_D, OPT_CONV7, OPT_ZOOM_ROWS, OPT_SPARSE_ROWS = range(1, 16)
+OPT_PROJECT_SHARE_CU, OPT_WAVEFRAME, OPT_LINPLANE, OPT_STAGE_CODES, OPT_SLICE_WAVE, OPT_DERIVE_FUSED, OPT_CODE_RMW, OPT_GEMM_BIG, OPT_CHUNK, OPT_C1_PK, OPT_SMO_LDS_ROWS, OPT_SGD_RESIDENT_D, OPT_CONV7, OPT_ZOOM_ROWS, OPT_SPARSE_ROWS, OPT_SPARSE_STORES = range(1, 17)
 OPTIONS = {"project_share_cu": OPT_PROJECT_SHARE_CU, "waveframe": OPT_WAVEFRAME, "linplane": OPT_LINPLANE, "stage_codes": OPT_STAGE_CODES,
            "slice_wave": OPT_SLICE_WAVE, "derive_fused": OPT_DERIVE_FUSED, "code_rmw": OPT_CODE_RMW, "gemm_big": OPT_GEMM_BIG,
            "chunk": OPT_CHUNK, "c1_pk": OPT_C1_PK}
@@ -213,7 +216,8 @@ NN_OPTIONS = {"conv7": OPT_CONV7}
 ZOOM_OPTIONS = {"zoom_rows": OPT_ZOOM_ROWS}
 # whether the 128 x 128 int8 GEMM of the fused pipeline stages all-background code lines from one constant line (-1 by the measured rule,
 # 0 dense, 1 wherever it runs): an A/B knob with the same bits in every setting, kept apart like the ones above
-SVM_OPTIONS = {"sparse_rows": OPT_SPARSE_ROWS}
+# sparse_stores: whether the projection in front of such a chunk leaves the lines the GEMM never fetches unstored (-1 / 0 / 1 alike)
+SVM_OPTIONS = {"sparse_rows": OPT_SPARSE_ROWS, "sparse_stores": OPT_SPARSE_STORES}
 SMO_LDS_ROWS_MAX = 2768
 SGD_RESIDENT_D_MAX = 10240
 SGD_MAX_ROWS = 8192
@@ -225,7 +229,7 @@ DNN_TRAIN_MAX_BATCH = 64
 ENV_OPTIONS = {"RML_WAVE_SHARE": "project_share_cu", "RML_WAVEFRAME": "waveframe", "RML_LINPLANE": "linplane", "RML_STAGE_CODES": "stage_codes",
                "RML_SLICE_WAVE": "slice_wave", "RML_DERIVE_FUSED": "derive_fused", "RML_CODE_RMW": "code_rmw", "RML_GEMM_BIG": "gemm_big",
                "RML_CHUNK": "chunk", "RML_C1_PK": "c1_pk", "RML_SMO_LDS_ROWS": "smo_lds_rows", "RML_SGD_RESIDENT_D": "sgd_resident_d",
-               "RML_CONV7": "conv7", "RML_SPARSE_ROWS": "sparse_rows"}
+               "RML_CONV7": "conv7", "RML_SPARSE_ROWS": "sparse_rows", "RML_SPARSE_STORES": "sparse_stores"}
 AUG_ROTATE, AUG_ZOOM, AUG_NOISE = 0, 1, 2
 CHAIN_ROTATE, CHAIN_ZOOM, CHAIN_NOISE = 1, 2, 4
 VOL_F32, VOL_U8 = 0, 1

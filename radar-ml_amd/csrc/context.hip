@@ -301,6 +301,7 @@ static int* opt_slot(rml_opts& o, int option) {
         case RML_OPT_GEMM_BIG: return &o.gemm_big;
         case RML_OPT_C1_PK: return &o.c1_pk;
         case RML_OPT_SPARSE_ROWS: return &o.sparse_rows;
+        case RML_OPT_SPARSE_STORES: return &o.sparse_stores;
         default: return nullptr;
     }
 }
@@ -339,7 +340,7 @@ extern "C" int rml_ctx_set_option(rml_ctx* ctx, int option, int value) {
     RML_REQUIRE(slot != nullptr, RML_ERR_INVALID, "rml_ctx_set_option: unknown option %d", option);
     switch (option) {
         case RML_OPT_WAVEFRAME: RML_REQUIRE(value >= 0 && value <= 3, RML_ERR_INVALID, "rml_ctx_set_option: RML_OPT_WAVEFRAME is 0..3"); *slot = value; break;
-        case RML_OPT_CODE_RMW: case RML_OPT_GEMM_BIG: case RML_OPT_SPARSE_ROWS: *slot = value < 0 ? -1 : (value ? 1 : 0); break;
+        case RML_OPT_CODE_RMW: case RML_OPT_GEMM_BIG: case RML_OPT_SPARSE_ROWS: case RML_OPT_SPARSE_STORES: *slot = value < 0 ? -1 : (value ? 1 : 0); break;
         default: *slot = value ? 1 : 0;
     }
     return RML_OK;

@@ -387,9 +387,13 @@ __global__ __launch_bounds__(256, (NY + 2 * G) * 4 + 40 > 256 ? 1 : 2) void k_pr
         int lane_f = lane, Y_f = Y;
         asm volatile("" : "+v"(lane_f), "+s"(Y_f));
         const bool act_f = lane_f < ZQ;
+        // rows with holes (ProjOut::skip_clear; wave-uniform): a store of the full wave is two lines of the row, each kept back when it
+        // is background.  ONE loop with the flag handed down: two copies of it under a branch need more scalar registers than the
+        // kernel has left (the backend then fails on the "+s" operands above)
+        const bool holes_f = em.line32_ok(1, 4 * ZQ);
         static_for<NY>([&](auto jc) {
             constexpr int j = decltype(jc)::value;
-            if (j < Y_f && act_f) em.put4(1, (int64_t)j * Z + 4 * lane_f, yz[j]);
+            if (j < Y_f && act_f) em.put4_line32(1, (int64_t)j * Z + 4 * lane_f, yz[j], lane_f, holes_f);
         });
         em.flush_wave(lane_f);
         em.finish_wave(lane_f);
@@ -749,6 +753,7 @@ int rml_launch_project(rml_ctx* ctx, const void* V, int vdtype, int64_t B, int X
     const int num_cu = !ctx ? 256 : ctx->num_cu;
     const int rc = vdtype == RML_VOL_U8 ? launch_project_t<uint8_t>(pp, mode, num_cu, st) : launch_project_t<float>(pp, mode, num_cu, st);
     if (rc) return rc;
+    if (ctx && o.skip_clear && occ_done) ++ctx->sparse_store_launches;         // the kernel writes its own words: it leaves clear lines unstored
     if (o.occ && !occ_done) {
         const int64_t n = B * o.occ_words;
         hipLaunchKernelGGL(k_fill_u32, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, o.occ, n, 0xFFFFFFFFu);
@@ -1011,10 +1016,10 @@ static int project_rows(rml_ctx* ctx, const void* V, int vdtype, int64_t B, int 
     return rml_launch_project(ctx, V, vdtype, B, X, Y, Z, mode, ijk, o, static_cast<hipStream_t>(stream), tpf);
 }
 
-// rml_project's code rows (no float rows) together with their occupancy words
-extern "C" int rml_project_occupancy(rml_ctx* ctx, const void* V, int vdtype, int64_t B, int X, int Y, int Z, int mode, float scale_div,
-                                     uint32_t mask, uint8_t* feat_q, int64_t ld_q, int32_t* row_isum, int64_t* row_isq, int32_t* row_flags,
-                                     uint32_t* occ, int occ_words, void* stream) {
+// rml_project's code rows (no float rows) together with their occupancy words; skip_clear: ProjOut's (rows with holes)
+static int project_occupancy(rml_ctx* ctx, const void* V, int vdtype, int64_t B, int X, int Y, int Z, int mode, float scale_div,
+                             uint32_t mask, uint8_t* feat_q, int64_t ld_q, int32_t* row_isum, int64_t* row_isq, int32_t* row_flags,
+                             uint32_t* occ, int occ_words, int skip_clear, void* stream) {
     RML_REQUIRE(ctx && B >= 0 && X > 0 && Y > 0 && Z > 0, RML_ERR_INVALID, "rml_project_occupancy: bad arguments");
     if (B == 0) return RML_OK;
     RML_REQUIRE(V && feat_q && occ, RML_ERR_INVALID, "rml_project_occupancy: NULL argument");
@@ -1028,8 +1033,20 @@ extern "C" int rml_project_occupancy(rml_ctx* ctx, const void* V, int vdtype, in
     RML_HIP(hipSetDevice(ctx->device));
     ProjOut o{};
     rows_out(o, X, Y, Z, mask, scale_div, nullptr, 0, feat_q, ld_q, row_isum, row_isq, row_flags);
-    o.occ = occ; o.occ_words = occ_words;
+    o.occ = occ; o.occ_words = occ_words; o.skip_clear = skip_clear ? 1 : 0;
     return rml_launch_project(ctx, V, vdtype, B, X, Y, Z, mode, nullptr, o, static_cast<hipStream_t>(stream));
+}
+extern "C" int rml_project_occupancy(rml_ctx* ctx, const void* V, int vdtype, int64_t B, int X, int Y, int Z, int mode, float scale_div,
+                                     uint32_t mask, uint8_t* feat_q, int64_t ld_q, int32_t* row_isum, int64_t* row_isq, int32_t* row_flags,
+                                     uint32_t* occ, int occ_words, void* stream) {
+    return project_occupancy(ctx, V, vdtype, B, X, Y, Z, mode, scale_div, mask, feat_q, ld_q, row_isum, row_isq, row_flags, occ, occ_words, 0, stream);
+}
+// the same with ProjOut::skip_clear: lines whose bit stays clear are left as the caller's buffer had them (where the kernel can skip)
+extern "C" int rml_project_sparse_rows(rml_ctx* ctx, const void* V, int vdtype, int64_t B, int X, int Y, int Z, int mode, float scale_div,
+                                       uint32_t mask, uint8_t* feat_q, int64_t ld_q, int32_t* row_isum, int64_t* row_isq, int32_t* row_flags,
+                                       uint32_t* occ, int occ_words, int skip_clear, void* stream) {
+    return project_occupancy(ctx, V, vdtype, B, X, Y, Z, mode, scale_div, mask, feat_q, ld_q, row_isum, row_isq, row_flags, occ, occ_words,
+                             skip_clear, stream);
 }
 
 extern "C" int rml_project_planes(rml_ctx* ctx, const void* V, int vdtype, int64_t B, int X, int Y, int Z, int mode,

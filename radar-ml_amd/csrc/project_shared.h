@@ -109,10 +109,15 @@ struct Emitter {
     // clears them for the next frame.
     int occ_on = 0;
     int occ_off = 0;            // byte offset of the words in the stage
+    // ProjOut::skip_clear, honoured only where this kernel writes the words itself: a line whose bit stays clear is not stored (the
+    // sparse GEMM takes it from its constant line).  The eight lanes / the half-wave that hold one line decide together by a ballot;
+    // a store that does not cover a whole line of one plane always happens.
+    int skip = 0;
     __device__ __forceinline__ void set_stage(unsigned char* p, int xy_off) {
         stage = (lds_u8*)p; staged = 1; stage_xy = xy_off;
         if (a.o.occ) {
             occ_on = 1; occ_off = xy_off + ((a.X * a.Y + 15) & ~15);
+            skip = a.o.skip_clear;
             for (int w = threadIdx.x & 63; w < a.o.occ_words; w += 64) *(lds_u32*)(stage + occ_off + 4 * w) = 0u;
         }
     }
@@ -220,6 +225,26 @@ struct Emitter {
             }
         }
     }
+    // put4, or with `holes` (wave-uniform: line32_ok) its code store for a launch with `skip` set (codes only: no float row), then
+    // called by ALL 64 lanes of the wave with idx = base + 4 * lane, byte plane_at(pl) + base of the row a multiple of 128: a half-wave
+    // holds one line, which is stored only when one of its dwords is not background.  code() runs for every lane: the statistics
+    // and `ok` do not know about lines.
+    __device__ __forceinline__ void put4_line32(int pl, int64_t idx, float4 v, int lane, bool holes) {
+        if (!holes) { put4(pl, idx, v); return; }
+        if (!((a.o.sel >> pl) & 1u)) return;
+        uint32_t c0 = code(v.x), c1 = code(v.y), c2 = code(v.z), c3 = code(v.w);
+        if (a.o.q[pl]) {
+            const uint32_t packed = c0 | (c1 << 8) | (c2 << 16) | (c3 << 24);
+            const bool nz = packed != 0x80808080u;
+            const uint64_t line = __ballot(nz) >> (lane & 32);
+            if ((uint32_t)line) *reinterpret_cast<uint32_t*>(a.o.q[pl] + qb() * a.o.qstride + idx) = packed;
+            if (nz) occ_mark(plane_at(pl) + (int)idx);
+        }
+    }
+    // whether put4_line32 may take the frame-end stores of plane pl, `bytes` per wave store (wave-uniform)
+    __device__ __forceinline__ bool line32_ok(int pl, int bytes) const {
+        return skip && a.o.q[pl] && bytes == 256 && (plane_at(pl) & 127) == 0;
+    }
     // next frame of a persistent kernel
     __device__ __forceinline__ void reset(int64_t b_) { b = b_; isum = 0; isq = 0; ok = 1; nsq = 0.0; }
     // the staged xz / xy codes of frame b -> the code row, 16 bytes per lane and store where the row allows it (one wave: the DS unit
@@ -235,11 +260,25 @@ struct Emitter {
         for (int r = 0; r < 2; ++r) {
             int done = 0;
             if ((reinterpret_cast<uintptr_t>(dst[r]) & 15) == 0) {
-                for (int i = lane; i < (len[r] >> 4); i += 64) {
-                    const u32x4 v = ((lds_u128*)src[r])[i];
-                    reinterpret_cast<u32x4*>(dst[r])[i] = v;
-                    // (a 16-byte chunk at a 16-byte aligned offset of the row lies in one line)
-                    if (occ_on && ((v.x ^ 0x80808080u) | (v.y ^ 0x80808080u) | (v.z ^ 0x80808080u) | (v.w ^ 0x80808080u))) occ_mark(at[r] + 16 * i);
+                if (skip && (at[r] & 127) == 0) {
+                    // the plane starts on a line: chunks 8g .. 8g + 7 are one line, held by lanes 8g' .. 8g' + 7 of one trip.  A line
+                    // that is not wholly made of this loop's chunks (the plane's last one, shared with the tail loops, the next
+                    // plane or the padding) is always stored.
+                    const int whole = len[r] & ~127;
+                    for (int i = lane; i < (len[r] >> 4); i += 64) {
+                        const u32x4 v = ((lds_u128*)src[r])[i];
+                        const bool nz = ((v.x ^ 0x80808080u) | (v.y ^ 0x80808080u) | (v.z ^ 0x80808080u) | (v.w ^ 0x80808080u)) != 0u;
+                        const uint32_t line = (uint32_t)(__ballot(nz) >> (lane & 56)) & 0xFFu;
+                        if (line || 16 * i >= whole) reinterpret_cast<u32x4*>(dst[r])[i] = v;
+                        if (nz) occ_mark(at[r] + 16 * i);
+                    }
+                } else {
+                    for (int i = lane; i < (len[r] >> 4); i += 64) {
+                        const u32x4 v = ((lds_u128*)src[r])[i];
+                        reinterpret_cast<u32x4*>(dst[r])[i] = v;
+                        // (a 16-byte chunk at a 16-byte aligned offset of the row lies in one line)
+                        if (occ_on && ((v.x ^ 0x80808080u) | (v.y ^ 0x80808080u) | (v.z ^ 0x80808080u) | (v.w ^ 0x80808080u))) occ_mark(at[r] + 16 * i);
+                    }
                 }
                 done = len[r] & ~15;
             }

@@ -41,6 +41,7 @@ struct rml_opts {
     int conv7 = RML_CONV7_DEFAULT;  // RML_OPT_CONV7: bit 0 forward, bit 1 backward of the generator's output layer on csrc/gen.hip
     int sgd_resident_d = RML_SGD_RESIDENT_D_MAX;   // RML_OPT_SGD_RESIDENT_D: wider problems run on the workspace variant of k_sgd
     int sparse_rows = -1;       // RML_OPT_SPARSE_ROWS: -1 = the measured grid rule (rml_sparse_rows), 0 dense, 1 wherever occupancy words can be had (also in place of split-K)
+    int sparse_stores = -1;     // RML_OPT_SPARSE_STORES: -1 = the measured rule (rml_sparse_stores), 0 whole rows, 1 wherever the chunk's plan is sparse and the kernel can skip
     int zoom_rows = 0;          // RML_OPT_ZOOM_ROWS: k_zoom_rows 0 = one workgroup per (row, plane), 1 / 2 one per row: planes together / in turn
 };
 
@@ -60,7 +61,8 @@ struct rml_ctx {
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     hipEvent_t ev_proj[2] = {nullptr, nullptr}, ev_done[2] = {nullptr, nullptr};   // chunk pipeline of rml_project_svm (two workspaces)
     hipStream_t aux_stream = nullptr;   // second stream for overlapping GEMM with projection
-    mutable int64_t sparse_gemm_launches = 0;   // launches of k_svm_gemm<I8, PT, false, true> issued so far (rml_ctx_sparse_gemm_launches: the tests' witness)
+    int64_t sparse_store_launches = 0;          // projection launches with ProjOut::skip_clear on a kernel that honours it (rml_ctx_sparse_store_launches)
+    mutable int64_t sparse_gemm_launches = 0;  // launches of k_svm_gemm<I8, PT, false, true> issued so far (rml_ctx_sparse_gemm_launches: the tests' witness)
     uint8_t* bg_line = nullptr;         // 128 bytes of 0x80 (a line of background codes): what the sparse GEMM stager fetches for a clear occupancy bit
     // optional in-situ timing of the projection launches issued by rml_project_svm
     bool profiling = false;
@@ -196,6 +198,11 @@ struct ProjOut {
     // a launch of any other kernel fills the words with ones (rml_launch_project), which is always right.
     uint32_t* occ;
     int occ_words;
+    // Rows with holes: a line whose occupancy bit stays clear need not be stored -- its consumer, the sparse GEMM, takes it from the
+    // constant background line and never reads it from the row.  Honoured only by a kernel that writes `occ` itself (a launch that
+    // gets words of all ones stores everything); a set bit's line is always fully stored, a clear bit's line holds anything.  Only the
+    // producer of a chunk whose plan is sparse may set it (svm.hip front_chunked; ChunkOps::holes).
+    int skip_clear;
 };
 // rml_code_rmw: the default of ProjOut::q_rmw in the fused pipelines, for frames of frame_bytes volume bytes and D codes.  The
 // read-back costs its bytes (and, in a per-frame epilogue, its latency) whatever the rows hold; the stores it saves depend on the
@@ -228,6 +235,22 @@ inline int rml_code_rmw(int64_t D, int64_t frame_bytes, bool derive, bool u8) {
 // plane starts on a line -- background then comes in whole lines --, off elsewhere.
 inline int rml_sparse_rows(int X, int Y, int Z) {
     return (Z % 128 == 0 || 128 % Z == 0) && ((int64_t)X * Z) % 128 == 0 && ((int64_t)Y * Z) % 128 == 0;
+}
+
+// rml_sparse_stores: the default of RML_OPT_SPARSE_STORES (-1) for a grid -- whether the projection in front of a sparse chunk leaves
+// the lines whose occupancy bit is clear unstored (ProjOut::skip_clear).  What was measured at 64x64x128 (bench.py --gpus 1 --steps 20
+// --warmup 3, 65 536 frames, one box, alternating runs):
+//   the ceiling -- a timing-only arm that stores NO codes (tools/exp/sparse_stores_ablation.patch) against the library before, three
+//     pairs: 2.933 / 2.941 / 2.939 -> 3.153 / 3.121 / 3.126 M frames/s (+6.1 ... +7.5 %; the parent's max - min: 0.28 %), k_project_wave
+//     in situ 0.806 -> 0.857-0.864 of 8 TB/s;
+//   the kernel itself -- 69 % of the lines unstored, one burst of occupied lines per frame left -- against the commit before, five
+//     pairs: 2.993 / 2.985 / 2.994 / 2.997 / 2.997 -> 3.072 / 3.058 / 3.065 / 3.071 / 3.072 M frames/s (+2.4 ... +2.7 %, median
+//     +2.5 %; the parent's max - min: 0.43 %), same bits, 169.2 -> 54.0 MB written per launch (profiles/sparse_stores_bench.json,
+//     profiles/sparse_stores_pmc.txt): on.
+// A skipped line must be a whole line of ONE plane, so the rule is rml_sparse_rows' (every plane starts on a line; on the Walabot grid
+// only xz does and the rows stay dense anyway).
+inline int rml_sparse_stores(int X, int Y, int Z) {
+    return rml_sparse_rows(X, Y, Z);
 }
 
 // true when rml_launch_project would use the persistent wave-per-frame kernel for this shape (the fused pipeline then

@@ -161,9 +161,10 @@ struct DecisionOut {
 // The n rows of one chunk, already in place: code rows + their statistics (q NULL: none), per row "on the code grid?" (NULL: not
 // known per row), float rows of stride m->Df + squared norms (f32 NULL: none).  ws_rows: the first n rows of a chunk workspace.
 // occ: the occupancy words of the code rows (m->occ_words per row) when the chunk's producer wrote them, else NULL.
+// holes: the producer did not store the lines whose bit is clear (ProjOut::skip_clear): only a sparse plan may read these rows.
 struct ChunkOps { int64_t n; const uint8_t* q; int64_t ld_q; const int32_t* isum; const int64_t* isq; const int32_t* flags; const float* f32; const double* nsq;
-                  const uint32_t* occ; };
-ChunkOps ws_rows(const rml_svm* m, const ChunkWs& w, int64_t n) { return ChunkOps{n, w.q, m->Dq, w.isum, w.isq, w.flags, w.f32, w.nsq, nullptr}; }
+                  const uint32_t* occ; bool holes; };
+ChunkOps ws_rows(const rml_svm* m, const ChunkWs& w, int64_t n) { return ChunkOps{n, w.q, m->Dq, w.isum, w.isq, w.flags, w.f32, w.nsq, nullptr, false}; }
 
 // What to do with a chunk.  The entry point fills the first group (a ChunkPlan{} asks for nothing: set what is meant, by name);
 // plan_chunk derives the second from it, and is the only place that does.
@@ -293,6 +294,8 @@ int run_chunk(const rml_ctx* ctx, const rml_svm* m, const ChunkOps& x, const Chu
               hipStream_t st) {
     const ChunkPlan p = plan_chunk(ctx, m, asked, x, w);
     RML_REQUIRE(p.run_i8 || p.run_gen, RML_ERR_STATE, "svm: no usable operand path (model exact=%d)", (int)m->exact);
+    // every kernel but the sparse 128 x 128 GEMM reads whole code rows (tile flags, finish and the float paths read none)
+    RML_REQUIRE(!(x.holes && !p.sparse), RML_ERR_STATE, "svm: code rows with unstored background lines reached a dense plan");
     if (!p.tiles_done) {
         launch_tile_flags(m, x, p, w, nullptr, st);
         if (p.run_dig) launch_tile_dig(x, p, w, st);
@@ -520,6 +523,7 @@ extern "C" int rml_svm_sv_occupancy(rml_ctx* ctx, const rml_svm* m, uint32_t* ou
     return RML_OK;
 }
 extern "C" int64_t rml_ctx_sparse_gemm_launches(const rml_ctx* ctx) { return ctx ? ctx->sparse_gemm_launches : 0; }
+extern "C" int64_t rml_ctx_sparse_store_launches(const rml_ctx* ctx) { return ctx ? ctx->sparse_store_launches : 0; }
 extern "C" int rml_svm_is_exact(const rml_svm* m) { return m && m->exact ? 1 : 0; }
 extern "C" int64_t rml_svm_num_sv(const rml_svm* m) { return m ? m->M : 0; }
 extern "C" int64_t rml_svm_dim(const rml_svm* m) { return m ? m->D : 0; }
@@ -629,6 +633,7 @@ struct FrontCall {
     bool grid_ok;           // the code grid of the features is the model's: codes are the unscaled values
     int share_cu, q_rmw;    // ProjOut's: a GEMM runs beside the projections; read-compare-write of the code rows
     bool occ;               // the first projection pass also writes occupancy words (ChunkWs::occ) and the GEMM stage hands them on
+    bool skip_ok;           // RML_OPT_SPARSE_STORES allows rows with holes for this call; whether a chunk gets them: FrontChunk::holes
     bool use_dig; ChunkPlan plan;   // rows off the code grid go to the multi-digit int8 kernel; the plan of every chunk
     bool u8() const { return vdtype == RML_VOL_U8; }
     int64_t frame_bytes() const { return (int64_t)X * Y * Z * (u8() ? 1 : 4); }
@@ -636,7 +641,8 @@ struct FrontCall {
 };
 
 // projection pass 1 of a chunk: code rows + row statistics (uint8 volumes are on the code grid by construction: no row flags)
-ProjOut code_rows_out(const FrontCall& f, const ChunkWs& w) {
+// (holes: FrontChunk::holes -- every other producer of code rows stores whole rows)
+ProjOut code_rows_out(const FrontCall& f, const ChunkWs& w, bool holes = false) {
     ProjOut o{}; int64_t off = 0;
     for (int pl = 0; pl < 3; ++pl)
         if (f.mask & (1u << pl)) { o.q[pl] = w.q + off; off += f.plane_len(pl); }
@@ -644,7 +650,7 @@ ProjOut code_rows_out(const FrontCall& f, const ChunkWs& w) {
     o.qstride = f.m->Dq; o.qrow = w.q; o.qD = f.m->D;
     o.row_isum = w.isum; o.row_isq = w.isq; o.row_flags = f.u8() ? nullptr : w.flags; o.scale_div = f.scale_div;
     o.share_cu = f.share_cu; o.q_rmw = f.q_rmw;
-    if (f.occ && w.occ) { o.occ = w.occ; o.occ_words = f.m->occ_words; }
+    if (f.occ && w.occ) { o.occ = w.occ; o.occ_words = f.m->occ_words; o.skip_clear = holes ? 1 : 0; }
     return o;
 }
 // projection pass 2: float rows + norms, for the rows that left the code grid (or for a model that is not on it)
@@ -692,7 +698,15 @@ int front_single_tile(const FrontCall& f) {
 // ---- the chunked pipelines: projection(c + 1) on the caller's stream beside GEMM(c) on ctx->aux_stream, two workspaces in rotation
 struct FrontChunk {         // rows [r0, r0 + n) in w; "the rows are in w"; the frames, the given targets, where derived (i,j,k) go
     int64_t r0, n; const ChunkWs& w; hipEvent_t ev_proj; const void* V; const int32_t* ijk; int32_t* ijkd;
+    bool holes;             // the first pass leaves the clear-bit lines of the code rows unstored (front_chunked decides, per chunk)
 };
+// the chunk's rows as its GEMM stage reads them: the one description the producer's decision (front_chunked) and run_chunk share
+ChunkOps chunk_ops(const FrontCall& f, const FrontChunk& ck) {
+    ChunkOps x = ws_rows(f.m, ck.w, ck.n);
+    if (f.occ) x.occ = ck.w.occ;
+    x.holes = ck.holes;
+    return x;
+}
 
 // the caller's stream: a chunk's projection pass between the marks of the in-situ timing (and the digit planes of its float rows:
 // run_chunk decides the general tiles from their flags), then the GEMM stream takes the chunk over
@@ -711,8 +725,7 @@ int caller_stage(const FrontCall& f, const FrontChunk& ck, const ProjOut& po) {
 int gemm_stage(const FrontCall& f, const FrontChunk& ck) {
     hipStream_t aux = f.ctx->aux_stream;
     rml_prof_mark_gemm(f.ctx, aux);
-    ChunkOps x = ws_rows(f.m, ck.w, ck.n);
-    if (f.occ) x.occ = ck.w.occ;
+    const ChunkOps x = chunk_ops(f, ck);
     const int rc = run_chunk(f.ctx, f.m, x, f.plan, ck.w, f.out.at(ck.r0, f.m->C, f.m->P), aux);
     rml_prof_mark_gemm(f.ctx, aux);
     if (f.ctx->profiling) f.ctx->prof_ops_g += 2.0 * (double)ck.n * (double)f.m->M * (double)f.m->D;
@@ -722,7 +735,7 @@ int gemm_stage(const FrontCall& f, const FrontChunk& ck) {
 // uint8 volumes are on the code grid by construction: one projection pass (codes + statistics), the exact GEMM on
 // every tile, no flag kernels, no predicated second pass and no predicated float64 GEMM launch
 int chunk_u8(const FrontCall& f, const FrontChunk& ck) {
-    const int rc = caller_stage(f, ck, code_rows_out(f, ck.w));
+    const int rc = caller_stage(f, ck, code_rows_out(f, ck.w, ck.holes));
     return rc ? rc : gemm_stage(f, ck);
 }
 
@@ -739,9 +752,9 @@ int chunk_u8(const FrontCall& f, const FrontChunk& ck) {
 // persistent workgroup should go, and the projection pays for the imbalance.  The ~30 us of small kernels in front of the GEMM
 // are what lets the projection settle first.)
 int chunk_on_grid(const FrontCall& f, const FrontChunk& ck) {
-    int rc = caller_stage(f, ck, code_rows_out(f, ck.w));
+    int rc = caller_stage(f, ck, code_rows_out(f, ck.w, ck.holes));
     if (rc) return rc;
-    const ChunkOps x = ws_rows(f.m, ck.w, ck.n); hipStream_t aux = f.ctx->aux_stream;
+    const ChunkOps x = chunk_ops(f, ck); hipStream_t aux = f.ctx->aux_stream;
     launch_tile_flags(f.m, x, plan_chunk(f.ctx, f.m, f.plan, x, ck.w), ck.w, ck.w.all_exact, aux);      // at the group run_chunk's GEMMs read
     ProjOut of = float_rows_out(f, ck.w);
     of.no_pad = 1; of.skip_if_set = ck.w.all_exact;
@@ -804,6 +817,10 @@ int front_chunked(FrontCall f) {
     // code stage gets words of all ones: rml_launch_project).  The derive / slice emitters and the byte-native kernel never write them.
     f.occ = f.grid_ok && !f.derive && f.mode != RML_MODE_SLICE && ctx->opt.sparse_rows != 0 &&
             (ctx->opt.sparse_rows > 0 || (wave_proj && !f.u8() && rml_sparse_rows(f.X, f.Y, f.Z)));
+    // Rows with holes (RML_OPT_SPARSE_STORES): only float32 max / sum projections on the wave-per-frame kernels -- the producers
+    // that write their own words -- and, chunk by chunk below, only in front of a sparse plan
+    f.skip_ok = f.occ && wave_proj && !f.u8() && ctx->opt.sparse_stores != 0 &&
+                (ctx->opt.sparse_stores > 0 || rml_sparse_stores(f.X, f.Y, f.Z));
     need.q = f.grid_ok; need.f32 = true; need.dig = f.use_dig; need.ijk = f.derive && !f.ijk_out; need.occ = f.occ;     // the derived (i,j,k) stay in the chunk's workspace when the caller does not want them
     // workspaces in rotation: 2 (projection of chunk c+1 beside the GEMM of chunk c; a third one -- the projection two chunks
     // ahead -- changed nothing at 64x64x128 and cost 2 % at the Walabot grid: DESIGN.md 3.3)
@@ -823,8 +840,11 @@ int front_chunked(FrontCall f) {
     for (int64_t r0 = 0; r0 < f.B; r0 += CH, ++c) {
         const int b = (int)(c % NBUF);
         if (c >= NBUF) RML_HIP(hipStreamWaitEvent(f.caller, ctx->ev_done[b], 0));    // workspace reuse
-        const FrontChunk ck{r0, std::min(CH, f.B - r0), w2[b], ctx->ev_proj[b], static_cast<const unsigned char*>(f.V) + r0 * f.frame_bytes(),
-                            f.ijk ? f.ijk + r0 * 3 : nullptr, f.derive ? (f.ijk_out ? f.ijk_out + r0 * 3 : w2[b].ijk) : nullptr};
+        FrontChunk ck{r0, std::min(CH, f.B - r0), w2[b], ctx->ev_proj[b], static_cast<const unsigned char*>(f.V) + r0 * f.frame_bytes(),
+                      f.ijk ? f.ijk + r0 * 3 : nullptr, f.derive ? (f.ijk_out ? f.ijk_out + r0 * 3 : w2[b].ijk) : nullptr, false};
+        // per chunk, not per call: a short last chunk takes split-K and RML_OPT_CHUNK can send chunks to the small kernels -- both
+        // read every line (plan_chunk makes no HIP call: nothing changes for a stream capture)
+        ck.holes = f.skip_ok && plan_chunk(ctx, m, f.plan, chunk_ops(f, ck), ck.w).sparse;
         rc = !f.grid_ok ? chunk_off_grid(f, ck) : (f.u8() ? chunk_u8(f, ck) : chunk_on_grid(f, ck));
         if (rc) return rc;
         RML_HIP(hipEventRecord(ctx->ev_done[b], ctx->aux_stream));
