@@ -1,5 +1,9 @@
-// The 128 x 128 staged MFMA tile shared by k_svm_gemm, k_svm_gemm_splitk (svm_tile.h) and k_gram (gram.hip); the 256 x 256 ring
-// kernel (svm_ring.h) takes glds16, the source addresses and the C/D map from here and keeps its own schedule.
+// The 128 x 128 staged MFMA tile.  Who uses what:
+//   k_svm_gemm<PATH_I8 / PATH_F32> (svm_tile.h)   TileStager or SparseStager, tile_k_loop, Frag32, kstep_32
+//   k_svm_gemm<PATH_F64> (svm_tile.h)             TileStager, tile_k_loop, Frag64, kstep_f64
+//   k_svm_gemm_splitk (svm_tile.h)                TileStager, tile_k_loop over its K range, Frag32, kstep_i8_plain
+//   k_gram, k_gseg (gram.hip: gram_tile)          TileStager (no clamp), tile_k_loop over a segment's K range, Frag64, kstep_f64
+//   k_svm_gemm_ring (svm_ring.h, 256 x 256)       glds16, stage_src and the C/D map; it keeps its own schedule
 //
 // Workgroup tile 128 rows of A x 128 rows of B, 4 waves as 2 x 2.  K-step = 128 bytes per row (128 codes or 32 floats).  LDS image
 // of an operand tile: row-major [128 rows][128 B] with the 16-byte chunk index XOR-swizzled by (row >> 1) & 7, which makes the
@@ -55,6 +59,7 @@ struct TileStager {
             gb[q] = stage_src<CLAMP_B>(b, ldb, b0, b_rows, wave, q, lane);
         }
     }
+    __device__ __forceinline__ void take(int) {}    // nothing per block of 32 K-steps (SparseStager has)
     __device__ __forceinline__ void stage(unsigned char* smem, int kt, int buf) const {
         unsigned char* base = smem + buf * 2 * kTileBytes;
         const int64_t ko = (int64_t)kt * kStepBytes;
@@ -65,18 +70,6 @@ struct TileStager {
         }
     }
 };
-
-// The double-buffered K loop over steps [kt0, kt1): kstep(sA, sB) consumes one staged step.
-template <class KStep>
-__device__ __forceinline__ void tile_k_loop(const TileStager& sg, unsigned char* smem, int kt0, int kt1, KStep kstep) {
-    sg.stage(smem, kt0, 0);
-    for (int kt = kt0; kt < kt1; ++kt) {
-        __syncthreads();                            // DMA of step kt landed (vmcnt(0)) and visible; step kt-1's buffer is free
-        if (kt + 1 < kt1) sg.stage(smem, kt + 1, (kt + 1 - kt0) & 1);
-        const unsigned char* sA = smem + ((kt - kt0) & 1) * 2 * kTileBytes;
-        kstep(sA, sA + kTileBytes);
-    }
-}
 
 // Staging that honours occupancy words (k_svm_gemm<PATH_I8, PT, false, true> only).  Radar code rows are mostly the background code:
 // about two thirds of the 128-byte lines of a 64x64x128 row hold nothing else (tools/exp/README.md, "sparse code rows").  Every row
@@ -137,18 +130,19 @@ struct SparseStager {
     }
 };
 
-// tile_k_loop over steps [0, KT) with the sparse stager: the same barriers and the same stage / K-step order
-template <class KStep>
-__device__ __forceinline__ void tile_k_loop_sparse(SparseStager& sg, unsigned char* smem, int KT, KStep kstep) {
-    sg.take(0);
-    sg.stage(smem, 0, 0);
-    for (int kt = 0; kt < KT; ++kt) {
+// The double-buffered K loop over steps [kt0, kt1) with either stager: kstep(sA, sB) consumes one staged step.  The stager is told
+// (take) which block of 32 K-steps the next staged step opens; SparseStager's words start at bit 0, so its kt0 is a multiple of 32.
+template <class Stager, class KStep>
+__device__ __forceinline__ void tile_k_loop(Stager& sg, unsigned char* smem, int kt0, int kt1, KStep kstep) {
+    sg.take(kt0 >> 5);
+    sg.stage(smem, kt0, 0);
+    for (int kt = kt0; kt < kt1; ++kt) {
         __syncthreads();                            // DMA of step kt landed (vmcnt(0)) and visible; step kt-1's buffer is free
-        if (kt + 1 < KT) {
+        if (kt + 1 < kt1) {
             if (((kt + 1) & 31) == 0) sg.take((kt + 1) >> 5);      // the next step opens a block of 32
-            sg.stage(smem, kt + 1, (kt + 1) & 1);
+            sg.stage(smem, kt + 1, (kt + 1 - kt0) & 1);
         }
-        const unsigned char* sA = smem + (kt & 1) * 2 * kTileBytes;
+        const unsigned char* sA = smem + ((kt - kt0) & 1) * 2 * kTileBytes;
         kstep(sA, sA + kTileBytes);
     }
 }

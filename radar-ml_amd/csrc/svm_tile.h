@@ -23,6 +23,8 @@
 //        v_mfma_f64_16x16x4_f64: the float32 operands are widened to float64 in registers, the
 //        products and the accumulation are float64 -- the arithmetic class of libsvm itself, at
 //        the f64 matrix rate (78.6 TF).  This is what RML_PATH_AUTO uses for non-grid rows.
+//        It runs the staging, K loop and f64 K-step that k_gram runs (mfma_tile.h) at an accepted cost of up to two
+//        VGPRs on five of its ten instantiations, inside the 256 that two workgroups per CU leave a lane.
 //   F32  opt-in approximate path on v_mfma_f32_32x32x2_f32 (f32 accumulate, 2x the F64 rate;
 //        measured error of the decision values ~1e-4..1e-3, i.e. outside the 1e-5 bar).
 // Epilogue (float64): K = exp(-gamma d^2); per-pair weights W[p][m] (the libsvm pair loop
@@ -104,70 +106,15 @@ __global__ __launch_bounds__(256, 2) void k_svm_gemm(GemmArgs a) {
     };
 
     if constexpr (PATH == PATH_F64) {
-        // This path keeps its own copy of the staged K loop of mfma_tile.h (TileStager, tile_k_loop, kstep_f64: what k_gram runs).
-        // Through those functions five of its ten instantiations allocate one or two VGPRs more (202 -> 203/204, 203 -> 204/205:
-        // the stager costs them in PT = 3, the K-step function in PT = 1 and <6, KM>), and its epilogue keeps its loop for the
-        // same reason (chain_run: 203 -> 204 in <6, KM>).  A change to the staging or to the f64 K-step is made here as well.
-        const uint8_t* gsv[4];
-        const uint8_t* gx[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            int s = (wave * 4 + q) * 64 + lane;          // 16-byte slot in the LDS image
-            int r = s >> 3;
-            int c = (s & 7) ^ ((r >> 1) & 7);            // inverse swizzle on the source
-            gsv[q] = a.sv + (m0 + r) * a.ld_sv + c * 16;
-            int64_t xr = f0 + r; xr = xr < a.N ? xr : a.N - 1;
-            gx[q] = a.x + xr * a.ld_x + c * 16;
-        }
-        auto stage = [&](int kt, int buf) {
-            unsigned char* base = smem + buf * 2 * kTileBytes;
-            const int64_t ko = (int64_t)kt * kStepBytes;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                glds16(gsv[q] + ko, base + (wave * 4 + q) * 1024);
-                glds16(gx[q] + ko, base + kTileBytes + (wave * 4 + q) * 1024);
-            }
-        };
-        // accumulators: 4x4 tiles of 16x16 (4 doubles each); fragment addressing: lane = (row l&15, k-group l>>4) of a 16-row tile
+        TileStager sg;
+        sg.init<true>(a.sv, a.ld_sv, m0, a.x, a.ld_x, f0, a.N, wave, lane);
+        // accumulators: 4x4 tiles of 16x16 (4 doubles each)
+        Frag64 fa, fb;
+        fa.init(wr * 64, lane); fb.init(wc * 64, lane);
+        const int kgrp = lane >> 4;
         v4d accd[4][4];
         zero_acc(accd);
-        int doff_a[4], dsw_a[4], doff_b[4], dsw_b[4];
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-            int ra = wr * 64 + t * 16 + (lane & 15);
-            int rb = wc * 64 + t * 16 + (lane & 15);
-            doff_a[t] = ra * kStepBytes; dsw_a[t] = (ra >> 1) & 7;
-            doff_b[t] = rb * kStepBytes; dsw_b[t] = (rb >> 1) & 7;
-        }
-        const int kgrp = lane >> 4;
-        stage(0, 0);
-        for (int kt = 0; kt < a.KT; ++kt) {
-            __syncthreads();                       // DMA of step kt landed (vmcnt(0)) and visible
-            if (kt + 1 < a.KT) stage(kt + 1, (kt + 1) & 1);
-            const unsigned char* sA = smem + (kt & 1) * 2 * kTileBytes;
-            const unsigned char* sB = sA + kTileBytes;
-#pragma unroll
-            for (int hh = 0; hh < 2; ++hh) {
-                const int ch = 4 * hh + kgrp;
-                v4f af[4], bf[4];
-#pragma unroll
-                for (int t = 0; t < 4; ++t) {
-                    af[t] = *reinterpret_cast<const v4f*>(sA + doff_a[t] + ((ch ^ dsw_a[t]) << 4));
-                    bf[t] = *reinterpret_cast<const v4f*>(sB + doff_b[t] + ((ch ^ dsw_b[t]) << 4));
-                }
-#pragma unroll
-                for (int c = 0; c < 4; ++c) {
-                    double ad[4], bd[4];
-#pragma unroll
-                    for (int t = 0; t < 4; ++t) { ad[t] = (double)af[t][c]; bd[t] = (double)bf[t][c]; }
-#pragma unroll
-                    for (int i = 0; i < 4; ++i)
-#pragma unroll
-                        for (int j = 0; j < 4; ++j)
-                            accd[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(ad[i], bd[j], accd[i][j], 0, 0, 0);
-                }
-            }
-        }
+        tile_k_loop(sg, smem, 0, a.KT, [&](const unsigned char* sA, const unsigned char* sB) { kstep_f64(accd, sA, sB, fa, fb, kgrp); });
 
         const bool rbf = (a.kernel == RML_KERNEL_RBF);
         // float64 accumulators: 128 x 128 x 8 B = 128 KiB, so the LDS round trip is done in two column
@@ -194,16 +141,8 @@ __global__ __launch_bounds__(256, 2) void k_svm_gemm(GemmArgs a) {
             const int64_t nc = n < a.N ? n : a.N - 1;
             const double xt = rbf ? a.x_nsq[nc] : 0.0;
             double S[PT];
-#pragma unroll
-            for (int p = 0; p < PT; ++p) S[p] = 0.0;
-#pragma unroll 2
-            for (int mm = 0; mm < 32; ++mm) {
-                const int ml = qd * 32 + mm;
-                const double* e = svw + ml * (1 + PT);
-                const double kv = kernel_value<false>(rbf, gd[ml * 64 + nq], xt, e[0], a.gs, etab);
-                store_k(n, ml, kv);
-                chain_link<PT>(S, e + 1, 1, kv);
-            }
+            chain_run<PT, 32, false>(S, svw, qd * 32, rbf, xt, a.gs, etab, [&](int ml) { return gd[ml * 64 + nq]; },
+                                     [&](int ml, double kv) { store_k(n, ml, kv); });
             __syncthreads();                   // G half consumed: reuse its LDS for the exchange
             double* x4 = gd;                   // [4 quarters][64][PT]
 #pragma unroll
@@ -234,7 +173,7 @@ __global__ __launch_bounds__(256, 2) void k_svm_gemm(GemmArgs a) {
             __syncthreads();
             SparseStager sg;
             sg.init(a.sv, a.ld_sv, m0, a.x, a.ld_x, f0, a.N, occ_l, a.ow, a.bg_line, wave, lane);
-            tile_k_loop_sparse(sg, smem, a.KT, ks32);
+            tile_k_loop(sg, smem, 0, a.KT, ks32);
         } else {
             TileStager sg;
             sg.init<true>(a.sv, a.ld_sv, m0, a.x, a.ld_x, f0, a.N, wave, lane);

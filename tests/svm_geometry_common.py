@@ -263,3 +263,5 @@ def all_case_keys():
 
 
 KMAT_SHAPES = ((1, 1, 1), (129, 129, 129), (257, 1025, 300))        # (M, D, N) of the rml_svm_kernel_matrix checks
+# ... and of its float64 route at the other pair counts: kernel values only, no label is judged, so these are not among all_case_keys
+KMAT_F64_SHAPE, KMAT_F64_C = (129, 33, 129), (2, 4, 5, 6)

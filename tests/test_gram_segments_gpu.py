@@ -1,4 +1,4 @@
-"""rml_gram_segments / rml_gram_compose (csrc/gram_segments.hip): the per-segment inner products and norms of one set of float32
+"""rml_gram_segments / rml_gram_compose (csrc/gram.hip): the per-segment inner products and norms of one set of float32
 rows from one MFMA pass, and the kernel matrices of every union of segments composed from them, against a NumPy float64 oracle
 (per segment, and of the column subset for the composed matrices); symmetry, determinism, padding and argument errors."""
 import numpy as np

@@ -280,6 +280,31 @@ def test_kernel_matrix_values_and_bounds(rml, M, D, N):
         assert (full[:N, M:] == -7.25).all() and (full[N] == -7.25).all(), path
 
 
+@pytest.mark.parametrize("Cn", G.KMAT_F64_C)
+def test_kernel_matrix_f64_for_every_pair_count(rml, Cn):
+    """k_svm_gemm<PATH_F64, PT, KM> for PT = 1, 6, 10, 15 (KMAT_SHAPES runs PT = 3) at (M, D, N) = (129, 33, 129): two SV tiles and two
+    sample tiles, each with a one-row tail (padded SV rows, clamped sample rows), two K-steps; same bar and sentinel check as above"""
+    from radar_ml_amd import _lib
+    lib = _lib.load()
+    M, D, N = G.KMAT_F64_SHAPE
+    c = G.case(M, D, Cn, N)
+    svc = _svc(rml, c.model)
+    want = O.svm_kernel_values(c.Xoff, c.model["sv"], c.model["gamma"])
+    K = svc.kernel_matrix(c.Xoff, path="f64").cpu().numpy()
+    assert K.shape == (N, M)
+    err = float(np.abs(K - want).max())
+    print("GEOM %r kmat f64: max |K - ref| = %.3e (bar 1e-09)" % (c, err))
+    assert err <= 1e-9 * max(1.0, float(np.abs(want).max())), err
+    Xd = svc._rows(c.Xoff)
+    buf = torch.full((N + 1, M + 3), -7.25, dtype=torch.float64, device=Xd.device)
+    _lib.check(lib.rml_svm_kernel_matrix(svc._ctx, svc._h, _lib.PATHS["f64"], _lib.ptr(Xd), Xd.stride(0), N, _lib.ptr(buf), M + 3,
+                                         _lib.stream_ptr(Xd.device)), "rml_svm_kernel_matrix")
+    torch.cuda.synchronize()
+    full = buf.cpu().numpy()
+    assert np.array_equal(full[:N, :M], K)
+    assert (full[:N, M:] == -7.25).all() and (full[N] == -7.25).all()
+
+
 # ---- the fused front door ------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("chunk", [0, 128])
 @pytest.mark.parametrize("planes", ["xz+yz+xy", "xy"])
