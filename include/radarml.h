@@ -729,6 +729,13 @@ int rml_dnn_preprocess_slices(rml_ctx* ctx, const void* V, int vdtype, int64_t B
 int rml_dnn_trunk(rml_ctx* ctx, const void* xz, const void* yz, const void* xy, int in_bf16, int64_t B, int H, int W,
                   const float* w1, const float* b1, const uint16_t* w2t, const float* b2,
                   uint16_t* feat, void* stream);
+/* Host only, no context, no GPU: what rml_dnn_trunk would launch for B >= 1 samples of (H, W) planes on a device of num_cu compute
+ * units, answered by the launchers' own predicates.  out[0]: the kernel -- 0 unsupported (rml_dnn_trunk returns RML_ERR_UNSUPPORTED),
+ * 1 k_dnn_trunk_rf (conv1 image in registers; conv1 bias to float32 precision), 2 k_dnn_trunk (conv1 image in LDS; conv1 bias as one
+ * bf16); out[1], out[2]: k_dnn_trunk's conv2 rows per strip SR and workgroups per CU WPC (0 for rf); out[3]: 1 when k_dnn_trunk
+ * prefetches the next plane into registers; out[4]: 1 when k_dnn_trunk_rf gives a sample to a workgroup, 0 to a wave; out[5]:
+ * workgroups along the sample axis of the grid.  RML_ERR_INVALID for out == NULL, B outside [1, 2^31) or num_cu < 1. */
+int rml_dnn_trunk_path(int H, int W, int in_bf16, int64_t B, int num_cu, int out[6]);
 /* The same values in the layout rml_dnn_dense_tail streams best ("K-block"): feat[kb][b][64] bf16 with the K axis ordered (branch,
  * pixel, channel) -- element (branch, pixel, channel) of sample b at block kb = (branch * P + pixel) / 2, offset (pixel & 1) * 32 +
  * channel, P = (H/4) * (W/4) even.  A 128-sample tile of one K-step is then 16 KB of contiguous memory (row-major rows put those

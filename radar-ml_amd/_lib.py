@@ -111,6 +111,7 @@ SIGNATURES = {
                               c_void_p, c_void_p, c_void_p]),
     "rml_dnn_trunk_kblock": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p,
                                      c_void_p, c_void_p, c_void_p]),
+    "rml_dnn_trunk_path": (c_int, [c_int, c_int, c_int, c_int64, c_int, c_void_p]),
     "rml_dnn_trunk_kblock_supported": (c_int, [c_int, c_int]),
     "rml_dnn_trunk_x3_supported": (c_int, [c_int, c_int]),
     "rml_dnn_trunk_x3": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p,

@@ -93,6 +93,30 @@ struct TrunkLayout {        // LDS carve-up, shared by the kernel and the launch
     }
 };
 
+// The dispatch rules of k_dnn_trunk, each stated once: launch_trunk, the kernel (its prefetch switch) and rml_dnn_trunk_path ask these.
+// A plane fits strips of SR conv2 rows when a strip is at most MT tiles of 16 conv2 pixels, its conv1 image at most TPW tiles of 32
+// pixels per wave, and WPC workgroups' carve-ups sit in one CU's 160 KB (150 KB at the most for one)
+template <int SR, int MT, int WPC>
+inline bool trunk_fits(int H, int W) {
+    const TrunkLayout L(H, W, SR, MT);
+    if (SR * (W / 4) > 16 * MT || L.nt1 > 4 * TPW || L.total > 150 * 1024) return false;
+    return L.total * WPC <= 160 * 1024;
+}
+// the next plane travels in registers while this one is convolved when its 16-byte quads (4 float32 or 8 bf16 values of a row)
+// are at most the NLD loads per thread the register budget has room for
+template <bool INBF>
+__host__ __device__ __forceinline__ bool trunk_prefetches(int H, int W) {
+    constexpr int QE = INBF ? 8 : 4, NLD = INBF ? (PLD + 1) / 2 : PLD;
+    return H * (W / QE) <= 256 * NLD;
+}
+// persistent workgroups: a third of the resident slots per branch (grid y), no more than there are samples
+template <int WPC>
+inline int64_t trunk_grid(int64_t B, int num_cu) {
+    const int64_t slots = (int64_t)WPC * num_cu;                                     // workgroups resident at once
+    const int64_t gx = slots / 3 > 0 ? slots / 3 : 1;
+    return B < gx ? B : gx;
+}
+
 // MT = conv2 pixel tiles per strip, PF = prefetch the next plane into registers, WPC = workgroups per CU the register
 // budget is compiled for (2: 256 VGPRs, 3: 168)
 template <int SR, bool INBF, int MT, bool PF, int WPC>
@@ -128,7 +152,7 @@ __global__ __launch_bounds__(256, WPC) void k_dnn_trunk(TrunkArgs a) {
     constexpr int QE = INBF ? 8 : 4;        // elements per quad
     constexpr int NLD = INBF ? (PLD + 1) / 2 : PLD;
     const int WQ = W / QE, nquad = H * WQ;
-    const bool prefetch = PF && nquad <= 256 * NLD;
+    const bool prefetch = PF && trunk_prefetches<INBF>(H, W);
     int lofs[NLD];                          // LDS destination (bf16 units) of the thread's quads, -1 past the plane
 #pragma unroll
     for (int u = 0; u < NLD; ++u) {
@@ -337,13 +361,10 @@ __global__ __launch_bounds__(256, WPC) void k_dnn_trunk(TrunkArgs a) {
 
 template <int SR, bool INBF, int MT, bool PF, int WPC>
 int launch_trunk(const TrunkArgs& a, int num_cu, hipStream_t stream) {
+    if (!trunk_fits<SR, MT, WPC>(a.H, a.W)) return RML_ERR_UNSUPPORTED;
     const TrunkLayout L(a.H, a.W, SR, MT);
-    if (SR * (a.W / 4) > 16 * MT || L.nt1 > 4 * TPW || L.total > 150 * 1024) return RML_ERR_UNSUPPORTED;
-    if (L.total * WPC > 160 * 1024) return RML_ERR_UNSUPPORTED;
     RML_MAX_DYN_LDS(160 * 1024, &k_dnn_trunk<SR, INBF, MT, PF, WPC>);
-    const int64_t slots = (int64_t)WPC * num_cu;                                     // workgroups resident at once
-    const int64_t gx = slots / 3 > 0 ? slots / 3 : 1;
-    hipLaunchKernelGGL((k_dnn_trunk<SR, INBF, MT, PF, WPC>), dim3((unsigned)(a.B < gx ? a.B : gx), 3), dim3(256), L.total, stream, a);
+    hipLaunchKernelGGL((k_dnn_trunk<SR, INBF, MT, PF, WPC>), dim3((unsigned)trunk_grid<WPC>(a.B, num_cu), 3), dim3(256), L.total, stream, a);
     return RML_OK;
 }
 
@@ -388,6 +409,18 @@ struct RfLayout {
         total = off_bias + 128;
     }
 };
+
+// The dispatch rules of k_dnn_trunk_rf, each stated once (launch_trunk_rf, rml_dnn_trunk_kblock_supported, rml_dnn_trunk_path):
+// the eight wave-private planes + the weights within the 160 KB; at most two samples per CU: a workgroup per sample (see the kernel),
+// else a wave per sample; one persistent workgroup per CU, no more than the samples need
+// (no plane beyond 2^15 rows or columns fits any kernel here; asked first, so that the layouts' 32-bit arithmetic never sees more)
+inline bool trunk_plane_sane(int H, int W) { return H > 0 && W > 0 && H <= (1 << 15) && W <= (1 << 15); }
+inline bool trunk_rf_fits(int H, int W) { return trunk_plane_sane(H, W) && RfLayout(H, W).total <= 160 * 1024; }
+inline bool trunk_rf_split(int64_t B, int num_cu) { return B <= 2 * (int64_t)num_cu; }
+inline int64_t trunk_rf_grid(int64_t B, int num_cu) {
+    const int64_t need = trunk_rf_split(B, num_cu) ? B : (B + RF_WAVES - 1) / RF_WAVES;
+    return need < num_cu ? need : num_cu;
+}
 
 __device__ __forceinline__ int opaque(int v) { asm volatile("" : "+v"(v)); return v; }
 
@@ -607,13 +640,12 @@ __global__ __launch_bounds__(64 * RF_WAVES, 2) void k_dnn_trunk_rf(TrunkArgs a) 
 
 template <bool INBF>
 int launch_trunk_rf(const TrunkArgs& a, int num_cu, hipStream_t stream) {
+    if (!trunk_rf_fits(a.H, a.W)) return RML_ERR_UNSUPPORTED;
     const RfLayout L(a.H, a.W);
-    if (L.total > 160 * 1024) return RML_ERR_UNSUPPORTED;
     RML_MAX_DYN_LDS(160 * 1024, &k_dnn_trunk_rf<INBF>);
     TrunkArgs as = a;
-    as.split = a.B <= 2 * (int64_t)num_cu ? 1 : 0;      // at most two samples per CU: a workgroup per sample (see the kernel)
-    const int64_t need = as.split ? a.B : (a.B + RF_WAVES - 1) / RF_WAVES;
-    hipLaunchKernelGGL((k_dnn_trunk_rf<INBF>), dim3((unsigned)(need < num_cu ? need : num_cu)), dim3(64 * RF_WAVES), L.total, stream, as);
+    as.split = trunk_rf_split(a.B, num_cu) ? 1 : 0;
+    hipLaunchKernelGGL((k_dnn_trunk_rf<INBF>), dim3((unsigned)trunk_rf_grid(a.B, num_cu)), dim3(64 * RF_WAVES), L.total, stream, as);
     return RML_OK;
 }
 
@@ -621,27 +653,58 @@ int launch_trunk_rf(const TrunkArgs& a, int num_cu, hipStream_t stream) {
 
 // host only: the planes launch_trunk_rf takes in the K-block layout (trunk_entry's checks for bf16 planes + RfLayout within the LDS)
 extern "C" int rml_dnn_trunk_kblock_supported(int H, int W) {
-    if (H <= 0 || W <= 0 || H % 4 || W % 8 || ((H / 4) * (W / 4)) % 2) return 0;
-    return RfLayout(H, W).total <= 160 * 1024;
+    if (!trunk_plane_sane(H, W) || H % 4 || W % 8 || ((H / 4) * (W / 4)) % 2) return 0;
+    return trunk_rf_fits(H, W);
 }
 
 namespace {
+// the shapes of k_dnn_trunk in the order they are tried: try_(SR, WPC) as integral constants until one does not answer
+// RML_ERR_UNSUPPORTED (dispatch_trunk launches, rml_dnn_trunk_path only asks)
+template <typename F>
+int trunk_cascade(F&& try_) {
+    int rc = try_(std::integral_constant<int, 4>{}, std::integral_constant<int, 2>{});
+    if (rc == RML_ERR_UNSUPPORTED) rc = try_(std::integral_constant<int, 2>{}, std::integral_constant<int, 1>{});
+    if (rc == RML_ERR_UNSUPPORTED) rc = try_(std::integral_constant<int, 1>{}, std::integral_constant<int, 1>{});
+    return rc;
+}
+constexpr int TRUNK_MT = 5;                 // conv2 pixel tiles per strip of every dispatched k_dnn_trunk
+
 template <bool INBF>
 int dispatch_trunk(const TrunkArgs& a, int num_cu, hipStream_t st) {
-    int rc = RML_ERR_UNSUPPORTED;
-    rc = launch_trunk_rf<INBF>(a, num_cu, st);
+    const int rc = launch_trunk_rf<INBF>(a, num_cu, st);
     if (rc != RML_ERR_UNSUPPORTED || a.kblock) return rc;          // the K-block layout exists in the register-resident kernel only
     // (measured and dropped: a wave-specialised variant -- one 8-wave workgroup per CU, 4 producer waves doing conv1 and 4
     // consumer waves doing conv2 on a double-buffered conv1 image, one producer and one consumer per SIMD: 0.72 ms against
     // 0.675, archived as tools/exp/dnn_trunk_wave_specialised_kernel.hip.txt; and 2-row strips at three workgroups per CU -- 148 VGPRs, 49 KB LDS -- 0.78 ms against 0.69:
     // the extra conv1 rows, tile padding and barriers cost more than the third wave per SIMD hides)
     // strips of 4 conv2 rows while 4 rows are at most 80 pixels and two workgroups fit a CU, else 2 rows, else 1
-    if (rc == RML_ERR_UNSUPPORTED) rc = launch_trunk<4, INBF, 5, true, 2>(a, num_cu, st);
-    if (rc == RML_ERR_UNSUPPORTED) rc = launch_trunk<2, INBF, 5, true, 1>(a, num_cu, st);
-    if (rc == RML_ERR_UNSUPPORTED) rc = launch_trunk<1, INBF, 5, true, 1>(a, num_cu, st);
-    return rc;
+    return trunk_cascade([&](auto sr, auto wpc) { return launch_trunk<decltype(sr)::value, INBF, TRUNK_MT, true, decltype(wpc)::value>(a, num_cu, st); });
+}
+
+template <bool INBF>
+void trunk_path(int H, int W, int64_t B, int num_cu, int out[6]) {
+    if (trunk_rf_fits(H, W)) {
+        out[0] = 1; out[4] = trunk_rf_split(B, num_cu) ? 1 : 0; out[5] = (int)trunk_rf_grid(B, num_cu);
+        return;
+    }
+    trunk_cascade([&](auto sr, auto wpc) {
+        constexpr int SR = decltype(sr)::value, WPC = decltype(wpc)::value;
+        if (!trunk_fits<SR, TRUNK_MT, WPC>(H, W)) return (int)RML_ERR_UNSUPPORTED;
+        out[0] = 2; out[1] = SR; out[2] = WPC; out[3] = trunk_prefetches<INBF>(H, W) ? 1 : 0; out[5] = (int)trunk_grid<WPC>(B, num_cu);
+        return (int)RML_OK;
+    });
 }
 }  // namespace
+
+// host only, no context, no GPU: what rml_dnn_trunk would launch -- answered by the launchers' own predicates
+extern "C" int rml_dnn_trunk_path(int H, int W, int in_bf16, int64_t B, int num_cu, int out[6]) {
+    RML_REQUIRE(out && B >= 1 && B < (int64_t)1 << 31 && num_cu >= 1, RML_ERR_INVALID, "rml_dnn_trunk_path: out, B in [1, 2^31) and num_cu >= 1 expected");
+    for (int i = 0; i < 6; ++i) out[i] = 0;
+    if (!trunk_plane_sane(H, W) || H % 4 || W % (in_bf16 ? 8 : 4)) return RML_OK;      // trunk_entry's shape checks: unsupported
+    if (in_bf16) trunk_path<true>(H, W, B, num_cu, out);
+    else trunk_path<false>(H, W, B, num_cu, out);
+    return RML_OK;
+}
 
 static int trunk_entry(rml_ctx* ctx, const void* xz, const void* yz, const void* xy, int in_bf16, int64_t B, int H,
                        int W, const float* w1, const float* b1, const uint16_t* w2t, const float* b2,
@@ -652,6 +715,7 @@ static int trunk_entry(rml_ctx* ctx, const void* xz, const void* yz, const void*
     RML_REQUIRE(H % 4 == 0 && W % (in_bf16 ? 8 : 4) == 0, RML_ERR_UNSUPPORTED,
                 "rml_dnn_trunk: H must be a multiple of 4 and W of %d (got %dx%d)", in_bf16 ? 8 : 4, H, W);
     RML_REQUIRE(B < (int64_t)1 << 31, RML_ERR_UNSUPPORTED, "rml_dnn_trunk: B too large");
+    RML_REQUIRE(trunk_plane_sane(H, W), RML_ERR_UNSUPPORTED, "rml_dnn_trunk: plane %dx%d does not fit the LDS-resident trunk", H, W);
     RML_REQUIRE((reinterpret_cast<uintptr_t>(w2t) & 15) == 0 && (reinterpret_cast<uintptr_t>(feat) & 15) == 0 &&
                 (reinterpret_cast<uintptr_t>(xz) & 15) == 0 && (reinterpret_cast<uintptr_t>(yz) & 15) == 0 &&
                 (reinterpret_cast<uintptr_t>(xy) & 15) == 0, RML_ERR_INVALID,

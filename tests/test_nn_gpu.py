@@ -456,7 +456,10 @@ def test_dnn_fused_trunk_vs_fp32_cpu(rml):
     print("dnn fused trunk: features max err %.3e (max |f| %.2f), mean err %.2e; proba max |dp| %.2e"
           % (err.max(), np.abs(want).max(), err.mean(), np.abs(p_got - p_want).max()))
     assert np.abs(p_got - p_want).max() < DNN_BF16_RANDOM_INIT_TOL
-    # other sizes: strips of 4 / 2 conv2 rows, a partial last strip (24 rows -> 6 conv2 rows), sgan's 128x128
+    # other sizes.  Since the register-resident kernel became the default every one of them except 128x128 runs on k_dnn_trunk_rf
+    # (one to twelve tiles of 32 conv2 pixels, the last partial); sgan's 128x128 is the LDS-image kernel in strips of 2 conv2 rows,
+    # no prefetch, one sample per workgroup.  The other instantiations, partial strips, the prefetch and batches beyond the grid are
+    # swept bit for bit in tests/test_dnn_trunk_gpu.py (rml_dnn_trunk_path says which kernel a plane takes)
     for (h_, w_) in ((48, 64), (24, 16), (128, 128), (44, 36), (4, 4)):
         small = dnn.Classifier([(h_, w_, 1)] * 3, 3).eval()
         for mod in small.modules():

@@ -60,6 +60,19 @@ static void phase_a_arguments() {
         CHECK(rml_ctx_get_option(nullptr, RML_OPT_CHUNK, &v) < 0 && rml_ctx_reserve_workspace(nullptr, 1 << 20) < 0 && rml_ctx_workspace_bytes(nullptr) == 0);
         CHECK(rml_dnn_trunk_x3_supported(80, 80) == 1 && rml_dnn_trunk_x3_supported(128, 128) == 0 && rml_dnn_trunk_x3_supported(81, 80) == 0);
         CHECK(rml_dnn_trunk_kblock_supported(80, 80) == 1 && rml_dnn_trunk_kblock_supported(96, 80) == 0 && rml_dnn_trunk_kblock_supported(80, 84) == 0);
+        {
+            int path[6] = {9, 9, 9, 9, 9, 9};
+            CHECK(rml_dnn_trunk_path(80, 80, 0, 1, 256, nullptr) == RML_ERR_INVALID && rml_dnn_trunk_path(80, 80, 0, 0, 256, path) == RML_ERR_INVALID &&
+                  rml_dnn_trunk_path(80, 80, 0, 1, 0, path) == RML_ERR_INVALID && path[0] == 9);
+            CHECK(rml_dnn_trunk_path(80, 80, 1, 512, 256, path) == RML_OK && path[0] == 1 && path[1] == 0 && path[4] == 1 && path[5] == 256);
+            CHECK(rml_dnn_trunk_path(80, 80, 1, 513, 256, path) == RML_OK && path[0] == 1 && path[4] == 0 && path[5] == 65);
+            CHECK(rml_dnn_trunk_path(124, 64, 1, 1000, 256, path) == RML_OK && path[0] == 2 && path[1] == 4 && path[2] == 2 && path[3] == 1 && path[5] == 170);
+            CHECK(rml_dnn_trunk_path(36, 256, 0, 3, 256, path) == RML_OK && path[0] == 2 && path[1] == 1 && path[2] == 1 && path[3] == 0 && path[5] == 3);
+            CHECK(rml_dnn_trunk_path(40, 264, 0, 3, 256, path) == RML_OK && path[0] == 0 && path[5] == 0);
+            // planes whose layouts would overflow 32-bit arithmetic: refused before any layout is computed
+            CHECK(rml_dnn_trunk_path(2147483644, 2147483644, 0, 3, 256, path) == RML_OK && path[0] == 0);
+            CHECK(rml_dnn_trunk_kblock_supported(2147483644, 2147483640) == 0 && rml_dnn_trunk_kblock_supported(65536, 65536) == 0);
+        }
         CHECK(rml_dnn_trunk_x3(nullptr, &f, &f, &f, 1, 80, 80, &f, &f, &f, &f, 2, &f, nullptr) < 0);
         CHECK(rml_dnn_exact_features_scratch_bytes(RML_VOL_F32, 10, 22, 31, 176, 80, 80, 1) > 10 * 22 * 31 * 176 * 4);
         CHECK(rml_dnn_exact_features(nullptr, &f, RML_VOL_F32, nullptr, 1, 2, 2, 4, RML_MODE_MAX, 80, 80, &f, &f, &f, &f, 2, &f, 1, &f, nullptr) < 0);
